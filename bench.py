@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- images/sec of the M3DSSD hot path (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
 A "step" is one pass of the hot path over one batch of synthetic frames already resident in HBM:
 RPN.forward (DLA-34 + DCNv2 alignment + ANAB + heads, fp32) -> output bundling -> decode -> top-3000 ->
@@ -9,13 +9,18 @@ NMS -> fixed-size detection blocks, and for N > 1 the single RCCL all-gather of 
 Workload = BASELINE.json configs[1]: full M3d_inference_align, bs = 8 per GPU, 1280x384, fp32; weak scaling
 (per-GPU batch fixed, images shard naturally, weights replicated).
 
-Reported alongside `value`:
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...); with
+--dump-outputs DIR it also writes the detections of the last timed step (DIR/detections.npy, DIR/counts.npy, float32; the
+inputs are seeded, so two builds can be compared output for output).
+
+Reported alongside `value` with --full (each figure takes passes of its own):
   roofline     -- dominant kernel (the igemm instantiation with the largest share of GPU time): algorithmic
                   FLOPs of its launches / their HIP-event duration measured on the launch stream inside the
                   timed region, vs the 157.3 TFLOP/s dense fp32 MFMA peak of MI355X (MI355X_MICROARCH.md).
   cpu_baseline -- the CPU restatement of the reference (oracle/, kind "port": the reference has no CPU DCNv2)
                   timed on this host on bounded samples (~10 s each at bs = 8 and bs = 1), rank 0 at N = 1 only; the
                   CPU model string, the host's core count and the threads used are reported.
+  dropin, feed_u8, configs2_bf16, configs3_shard32 (N = 1, f32) and rccl (N > 1) -- the side legs described at their functions.
 """
 import argparse
 import json
@@ -483,7 +488,7 @@ def emit(out, detail_path, fd):
     os.write(fd, (compact_line(out, shown) + "\n").encode())
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 200 for f32 bs=8, 60 for bf16 bs=64: ~1.2 s timed)")
@@ -512,7 +517,18 @@ def parse_args():
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="do not overlap decode/top-k/NMS of batch k with the forward of batch k+1")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the detections of the last one as DIR/detections.npy "
+                         "[images, nms_topN_post, 14] and DIR/counts.npy [images] (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: instrumented step, roofline and kernel-family tables, "
+                         "shader clock, drop-in / feed_u8 / configs2 / configs3 legs, CPU baseline (N = 1), RCCL proof (N > 1)")
+    args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.dump_layers or args.dump_launches) and not args.full:
+        ap.error("--dump-layers / --dump-launches read the instrumented step: add --full")
+    return args
 
 
 def main():
@@ -544,8 +560,8 @@ def _main(args, real_stdout):
         os.environ.setdefault("OMP_NUM_THREADS", "8")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.dup2(real_stdout, 1)                    # the launcher and its ranks inherit the real stdout (rank 0 prints the line)
-        os.execv(sys.executable, cmd)
+        import subprocess                          # (a child process: the ranks run under their own launcher)
+        raise SystemExit(subprocess.call(cmd, stdout=real_stdout))   # the ranks inherit the real stdout (rank 0 prints the line)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback on the product path)")
     backend = os.environ.get("M3D_DIST_BACKEND")          # None: init_from_env's own default (nccl = RCCL when a GPU is visible)
@@ -559,12 +575,14 @@ def _main(args, real_stdout):
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
 
+    full = args.full
     out, sd = run_config(args, args.dtype, args.steps, args.batch, rank, world, dev, mdist, dump_layers=args.dump_layers,
-                         feed=(world == 1 and args.dtype == "f32" and args.batch is None and not args.no_feed))
+                         feed=(full and world == 1 and args.dtype == "f32" and args.batch is None and not args.no_feed),
+                         full=full, dump_dir=args.dump_outputs)
     if rank == 0:
         if world > 1:
             out["dist_backend"] = mdist.backend_name()
-        if world == 1 and args.dtype == "f32" and args.batch is None and not args.no_configs2:
+        if full and world == 1 and args.dtype == "f32" and args.batch is None and not args.no_configs2:
             # BASELINE.json configs[2] (bs = 64, bf16 storage + MFMA) on the same clock as the headline line: same step
             # definition, same timed-region bracket, its own roofline objects.
             torch.cuda.empty_cache()
@@ -576,7 +594,7 @@ def _main(args, real_stdout):
                                                         "launch", "roofline", "step_roofline", "gpu_ms_by_kernel_one_step", "dropin", "work_in_timed_region",
                                                         "mfma_kernel_families", "helper_kernels", "mfma_time_weighted_frac",
                                                         "sclk_under_step_ghz", "roofline_frac_at_held_clock", "error") if k in c2}
-        if world == 1 and args.dtype == "f32" and args.batch is None and not args.no_configs3:
+        if full and world == 1 and args.dtype == "f32" and args.batch is None and not args.no_configs3:
             # BASELINE.json configs[3]: bs = 256 sharded 32 per GPU over 8 MI355X.  One GPU measures its shard (32 images per
             # step, both precisions, same bracket) and the one-rank RCCL cost of the [32, 41, 14] block every rank contributes;
             # `python bench.py --gpus 8 --batch 32` is the full shape when a node is available.
@@ -590,7 +608,7 @@ def _main(args, real_stdout):
             c3["allgather_us_one_rank_rccl"] = rccl_one_rank_allgather_us(32, 40, dev)
             c3["allgather_bytes_per_rank"] = 32 * 41 * 14 * 4
             out["configs3_shard32"] = c3
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             try:                                   # a reported side figure: its failure must not take the headline line with it
                 out["cpu_baseline"] = cpu_baseline(sd)
             except Exception as e:                 # noqa: BLE001
@@ -751,8 +769,27 @@ def shard_leg(dtype, B, steps, dev):
     return out
 
 
-def run_config(args, dtype, steps, batch, rank, world, dev, mdist, dump_layers=None, feed=False):
-    """Warm up, instrument, time `steps` steps of one (dtype, batch) configuration; returns (JSON dict or None off rank 0, state dict)."""
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all arrays together
+
+
+def dump_outputs(dump_dir, res, post):
+    """What the timed path returned for its last step -> DIR/detections.npy [images, post, 14] and DIR/counts.npy [images], float32.
+    `res` is (dets or the [.., post + 1, 14] gather block, counts) as the launch mode returns it."""
+    import numpy as np
+    dets, counts = res[0], res[1]
+    if dets.shape[1] == post + 1:                         # the block form: row `post` carries the counts
+        dets = dets[:, :post]
+    arrays = {"detections": dets.float().cpu().numpy(), "counts": counts.float().cpu().numpy()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would exceed %d bytes" % DUMP_LIMIT_BYTES)
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def run_config(args, dtype, steps, batch, rank, world, dev, mdist, dump_layers=None, feed=False, full=True, dump_dir=None):
+    """Warm up, (full: instrument,) time `steps` steps of one (dtype, batch) configuration; returns (JSON dict or None off rank 0,
+    state dict).  Without `full` only the headline keys are measured: no instrumented or roofline passes, no clock probe."""
     from m3dssd_amd import synth
     from m3dssd_amd.host.detect import detect_device, select_block
     from model.M3d_inference_align import build
@@ -774,55 +811,60 @@ def run_config(args, dtype, steps, batch, rank, world, dev, mdist, dump_layers=N
             return mdist.gather_block(block)
         return block[:, :-1], counts
 
-    # ---- warm-up: first step builds the plan; one fully instrumented step finds the dominant kernel ----
-    for _ in range(max(1, args.warmup - 1)):
+    if not full:
+        # ---- warm-up: the first step builds the plan ----
+        for _ in range(max(1, args.warmup)):
+            step()
+    else:
+        # ---- warm-up: first step builds the plan; one fully instrumented step finds the dominant kernel ----
+        for _ in range(max(1, args.warmup - 1)):
+            step()
+        eng.profile = []
         step()
-    eng.profile = []
-    step()
-    torch.cuda.synchronize()
-    eng.flush_profile()
-    if dump_layers and rank == 0:
-        with open(dump_layers, "w") as f:
-            f.write("name,kernel,gflop,ms,tflops\n")
+        torch.cuda.synchronize()
+        eng.flush_profile()
+        if dump_layers and rank == 0:
+            with open(dump_layers, "w") as f:
+                f.write("name,kernel,gflop,ms,tflops\n")
+                for name, kind, flops, ms in eng.profile:
+                    f.write("%s,\"%s\",%.3f,%.4f,%.1f\n" % (name, kind, flops / 1e9, ms, flops / 1e9 / max(ms, 1e-6)))
+        if args.dump_launches and rank == 0:
+            seq = []
             for name, kind, flops, ms in eng.profile:
-                f.write("%s,\"%s\",%.3f,%.4f,%.1f\n" % (name, kind, flops / 1e9, ms, flops / 1e9 / max(ms, 1e-6)))
-    if args.dump_launches and rank == 0:
-        seq = []
+                if kind.startswith(MFMA_FAMILIES):
+                    seq.append([kind, kernel_symbol(kind).split("(", 1)[0].split("<", 1)[0].replace("void ", "").strip()])
+                    if kind.startswith("bf16_dcn_patch"):        # the gated implicit-GEMM fallback is launched right behind it
+                        seq.append([kind + "/fallback", "bf16_conv_kernel"])
+            json.dump(seq, open(args.dump_launches, "w"))
+        per_kind = {}
         for name, kind, flops, ms in eng.profile:
-            if kind.startswith(MFMA_FAMILIES):
-                seq.append([kind, kernel_symbol(kind).split("(", 1)[0].split("<", 1)[0].replace("void ", "").strip()])
-                if kind.startswith("bf16_dcn_patch"):        # the gated implicit-GEMM fallback is launched right behind it
-                    seq.append([kind + "/fallback", "bf16_conv_kernel"])
-        json.dump(seq, open(args.dump_launches, "w"))
-    per_kind = {}
-    for name, kind, flops, ms in eng.profile:
-        a = per_kind.setdefault(kind, [0.0, 0.0, 0])
-        a[0] += ms
-        a[1] += flops
-        a[2] += 1
-    # MFMA-bound kernel families (everything else is a small HBM/latency-bound helper)
-    igemm = {k: v for k, v in per_kind.items() if k.startswith(MFMA_FAMILIES)}
-    # The dominant KERNEL is chosen by symbol, not by engine family: one symbol serves several families (conv_wave_kernel<true, 4>
-    # = the full-size deformable layers and their three split-K forms), and the headline roofline belongs to the symbol with the
-    # largest share of GPU time (VERDICT r4 #4 / #3a: by family the second-largest kernel won).
-    by_symbol = {}
-    for k, v in igemm.items():
-        by_symbol.setdefault(kernel_symbol(k), []).append(k)
-    dom_symbol = max(by_symbol, key=lambda sy: sum(igemm[k][0] for k in by_symbol[sy]))
-    dom_kinds = sorted(by_symbol[dom_symbol], key=lambda k: -igemm[k][0])
-    dominant = dom_kinds[0]                     # the largest family of the dominant symbol (labels, Winograd divisor)
-    gpu_ms_all = sum(v[0] for v in per_kind.values())
-    breakdown = {k: round(v[0], 3) for k, v in sorted(per_kind.items(), key=lambda kv: -kv[1][0])}
+            a = per_kind.setdefault(kind, [0.0, 0.0, 0])
+            a[0] += ms
+            a[1] += flops
+            a[2] += 1
+        # MFMA-bound kernel families (everything else is a small HBM/latency-bound helper)
+        igemm = {k: v for k, v in per_kind.items() if k.startswith(MFMA_FAMILIES)}
+        # The dominant KERNEL is chosen by symbol, not by engine family: one symbol serves several families (conv_wave_kernel<true, 4>
+        # = the full-size deformable layers and their three split-K forms), and the headline roofline belongs to the symbol with the
+        # largest share of GPU time (VERDICT r4 #4 / #3a: by family the second-largest kernel won).
+        by_symbol = {}
+        for k, v in igemm.items():
+            by_symbol.setdefault(kernel_symbol(k), []).append(k)
+        dom_symbol = max(by_symbol, key=lambda sy: sum(igemm[k][0] for k in by_symbol[sy]))
+        dom_kinds = sorted(by_symbol[dom_symbol], key=lambda k: -igemm[k][0])
+        dominant = dom_kinds[0]                     # the largest family of the dominant symbol (labels, Winograd divisor)
+        gpu_ms_all = sum(v[0] for v in per_kind.values())
+        breakdown = {k: round(v[0], 3) for k, v in sorted(per_kind.items(), key=lambda kv: -kv[1][0])}
 
-    # ---- roofline pass: a few eager steps with HIP events around the dominant kernel's launches ---------
-    eng.profile, eng.profile_kinds = [], set(dom_kinds)
-    ROOF_REPS = 5
-    for _ in range(ROOF_REPS):
-        step()
-    torch.cuda.synchronize()
-    eng.flush_profile()
-    roof_rows = eng.profile
-    eng.profile, eng.profile_kinds = None, None
+        # ---- roofline pass: a few eager steps with HIP events around the dominant kernel's launches ---------
+        eng.profile, eng.profile_kinds = [], set(dom_kinds)
+        ROOF_REPS = 5
+        for _ in range(ROOF_REPS):
+            step()
+        torch.cuda.synchronize()
+        eng.flush_profile()
+        roof_rows = eng.profile
+        eng.profile, eng.profile_kinds = None, None
 
     # ---- timed region: K steps.  The launch-bound sequence (~170 launches) is captured once in a hipGraph
     # and replayed; the graph contains exactly the work of step() (forward, bundle, top-k, decode, NMS, and
@@ -879,13 +921,46 @@ def run_config(args, dtype, steps, batch, rank, world, dev, mdist, dump_layers=N
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        timed_step()
+        last = timed_step()
     if flush is not None:
-        flush()
+        last = flush()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last, int(conf.nms_topN_post))
+    if world > 1:
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        dt = float(t.item())
+    out = None
+    if rank == 0:
+        value = world * B * steps / dt
+        out = {
+            "metric": ("images/sec at 1280x384 bs=8, 1/2/4/8 MI355X; 3D-box Linf vs ref" if not bf16 else
+                       "images/sec at 1280x384 bs=64 bf16 (BASELINE.json configs[2]), 1/2/4/8 MI355X"),
+            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / steps, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+            "config": {"workload": "BASELINE.json configs[%d]: full M3d_inference_align (DLA-34 + DCNv2 align + ANAB) "
+                                   "forward + decode + top-3000 + NMS, bs=%d/GPU, 1280x384, %s, random-init "
+                                   "synthetic weights and frames" % (3 if B == 32 else (2 if bf16 else 1), B,
+                                                                     "bf16 storage + bf16 MFMA, fp32 "
+                                                                     "accumulation / epilogues" if bf16 else "fp32"),
+                       "per_gpu_batch": B, "global_batch": B * world, "resolution": [CROP[1], CROP[0]],
+                       "parallelism": "dp%d (batch sharded, 1 all-gather of [B,40,14] detections)" % world},
+            "launch": ("hipGraph replay, detect(k-1) overlapped with forward(k); the timed graph decodes from the planar head outputs (sort keys "
+                       "written by anchor_select) where the eager per-kernel breakdown below shows `bundle`" if use_pipe else
+                       "hipGraph replay" if use_graph else "eager"),
+        }
+        work = ("forward + decode + top-%d + NMS + select of K batches; bundle_outputs %s" %
+                (int(conf.nms_topN_pre), "NOT run (decode reads the planar head outputs; `dropin` is the bundled reference call sequence)"
+                 if use_pipe else "run"))
+    if not full:
+        if out is not None:
+            out["work_in_timed_region"] = work
+        return out, sd
     # ---- shader clock under the step (outside the timed region): one wave on a side stream samples the cycle counter against the
     # 100 MHz wall clock over a 30 ms window while the step replays next to it
     sclk = None
@@ -907,10 +982,6 @@ def run_config(args, dtype, steps, batch, rank, world, dev, mdist, dump_layers=N
     except Exception:
         sclk = None
     eng.profile = roof_rows
-    if world > 1:
-        t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        dt = float(t.item())
     # per launch of the dominant family: the MEDIAN of its HIP-event durations over the instrumented steps (an eager step now and
     # then catches a launch behind a host hiccup: the mean read 5 % above rocprofv3's average on one lease, the median agrees)
     by_name = {}
@@ -981,25 +1052,9 @@ def run_config(args, dtype, steps, batch, rank, world, dev, mdist, dump_layers=N
     mfma_weighted = sum(v["ms_per_step"] * v["frac_of_mfma_peak"] for v in families.values()) / mfma_ms if mfma_ms > 0 else 0.0
 
     if rank == 0:
-        value = world * B * steps / dt
         achieved = dom_flops / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
         wino_div = 4.0 if dominant.startswith("wino44") else (2.25 if dominant.startswith("wino") else 1.0)
-        out = {
-            "metric": ("images/sec at 1280x384 bs=8, 1/2/4/8 MI355X; 3D-box Linf vs ref" if not bf16 else
-                       "images/sec at 1280x384 bs=64 bf16 (BASELINE.json configs[2]), 1/2/4/8 MI355X"),
-            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / steps, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-            "config": {"workload": "BASELINE.json configs[%d]: full M3d_inference_align (DLA-34 + DCNv2 align + ANAB) "
-                                   "forward + decode + top-3000 + NMS, bs=%d/GPU, 1280x384, %s, random-init "
-                                   "synthetic weights and frames" % (3 if B == 32 else (2 if bf16 else 1), B,
-                                                                     "bf16 storage + bf16 MFMA, fp32 "
-                                                                     "accumulation / epilogues" if bf16 else "fp32"),
-                       "per_gpu_batch": B, "global_batch": B * world, "resolution": [CROP[1], CROP[0]],
-                       "parallelism": "dp%d (batch sharded, 1 all-gather of [B,40,14] detections)" % world},
-            "launch": ("hipGraph replay, detect(k-1) overlapped with forward(k); the timed graph decodes from the planar head outputs (sort keys "
-                       "written by anchor_select) where the eager per-kernel breakdown below shows `bundle`" if use_pipe else
-                       "hipGraph replay" if use_graph else "eager"),
+        out.update({
             # Winograd F(2x2,3x3) launches: `achieved` counts the MFMA FLOPs the kernel EXECUTES (16 multiplies per 2x2 output
             # tile and channel pair = the direct-convolution count / 2.25), so frac is the MFMA-pipe utilisation and cannot
             # exceed 1; the direct-convolution-equivalent rate is reported next to it.
@@ -1033,11 +1088,8 @@ def run_config(args, dtype, steps, batch, rank, world, dev, mdist, dump_layers=N
             # 2.4 GHz datasheet figure; peak x sclk / 2.4 is what the matrix pipes offered in this run
             "sclk_under_step_ghz": round(sclk, 3) if sclk else None,
             "roofline_frac_at_held_clock": round(achieved / wino_div / (peak_tf * sclk / 2.4), 4) if sclk else None,
-        }
-        out["work_in_timed_region"] = (
-            "forward + decode + top-%d + NMS + select of K batches; bundle_outputs %s" %
-            (int(conf.nms_topN_pre), "NOT run (decode reads the planar head outputs; `dropin` is the bundled reference call sequence)"
-             if use_pipe else "run"))
+        })
+        out["work_in_timed_region"] = work
         if world == 1 and not args.no_dropin:
             try:                                   # (side leg: never part of `value`)
                 out["dropin"] = dropin_leg(net, x, conf, args.dropin_steps or max(5, min(steps, 60 if not bf16 else 30)))

@@ -225,7 +225,9 @@ _lib = None
 
 def build(force=False, verbose=False):
     """Compile every HIP source for gfx950 into csrc/build/libm3dssd_hip.so (make, hipcc)."""
-    cmd = ["make", "-C", CSRC, "-j", str(os.cpu_count() or 4)] + (["-B"] if force else [])
+    # (os.cpu_count() is the whole host's count, not what this process may use: at most 16 jobs, MAX_JOBS lowers it)
+    jobs = min(16, int(os.environ.get("MAX_JOBS") or 0) or os.cpu_count() or 4)
+    cmd = ["make", "-C", CSRC, "-j", str(jobs)] + (["-B"] if force else [])
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or res.returncode != 0:
         print(res.stdout)

@@ -121,3 +121,32 @@ def test_stdout_line_sheds_optional_blocks_rather_than_growing():
     r = json.loads(bench.compact_line(rec, "bench_detail.json"))
     assert len(json.dumps(r, separators=(",", ":"))) < 4096
     assert r["value"] == 1349.62 and "roofline" in r and "cpu_baseline" in r
+
+
+def test_plain_run_is_the_default_and_side_measurements_need_full():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--steps", "3", "--full", "--dump-outputs", "d", "--dump-layers", "l.csv"])
+    assert a.full is True and a.dump_outputs == "d" and a.dump_layers == "l.csv"
+    for bad in (["--steps", "0"], ["--dump-layers", "l.csv"], ["--dump-launches", "l.json"]):
+        try:
+            bench.parse_args(bad)
+        except SystemExit as e:
+            assert e.code == 2, bad
+        else:
+            raise AssertionError(bad)
+
+
+def test_dump_outputs_writes_the_detections_of_either_launch_form(tmp_path):
+    """The pipelined path returns the [B, post + 1, 14] gather block, the others [B, post, 14] detections: the files are the same."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    block = torch.randn(3, 41, 14, generator=g)
+    counts = torch.tensor([5, 0, 40], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "a"), (block, counts), 40)
+    bench.dump_outputs(str(tmp_path / "b"), (block[:, :-1], counts), 40)
+    for d in ("a", "b"):
+        dets, cnt = np.load(tmp_path / d / "detections.npy"), np.load(tmp_path / d / "counts.npy")
+        assert dets.dtype == np.float32 and cnt.dtype == np.float32
+        assert np.array_equal(dets, block[:, :-1].numpy()) and np.array_equal(cnt, [5.0, 0.0, 40.0])

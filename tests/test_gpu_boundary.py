@@ -221,7 +221,7 @@ def test_bench_two_ranks_gloo_emits_one_parseable_line(tmp_path):
     pipelined graph, the per-step gather_block, the barriers and the all_reduce(MAX) of the elapsed time; rank 0 prints ONE
     compact JSON line for the whole job and writes the full record to the detail file."""
     det = tmp_path / "detail.json"
-    rc, out, err = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--detail", str(det)],
+    rc, out, err = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--detail", str(det)],
                               {"M3D_DIST_BACKEND": "gloo"})
     assert rc == 0, err[-3000:]
     r, full = _bench_line_and_detail(out, det)
@@ -370,11 +370,11 @@ def test_bench_nccl_refuses_more_ranks_than_devices():
 
 
 def test_bench_default_line_is_compact_and_carries_configs2_dropin_and_roofline(tmp_path):
-    """The driver's command (`python bench.py`, N = 1): ONE line < 4 KB holding the f32 headline, the dominant kernel's roofline,
+    """`python bench.py --full`, N = 1: ONE line < 4 KB holding the f32 headline, the dominant kernel's roofline,
     the bs = 64 bf16 measurement, the configs[3] shard and the drop-in leg (the reference's own call sequence, eager and as one
     graph, VERDICT r5 #1 / #5); the kernel-family tables are in the detail file, not on stdout."""
     det = tmp_path / "detail.json"
-    rc, out, err = _run_bench(["--steps", "5", "--warmup", "2", "--configs2-steps", "3", "--configs3-steps", "2", "--dropin-steps", "3",
+    rc, out, err = _run_bench(["--steps", "5", "--warmup", "2", "--full", "--configs2-steps", "3", "--configs3-steps", "2", "--dropin-steps", "3",
                                "--no-cpu-baseline", "--detail", str(det)], {})
     assert rc == 0, err[-3000:]
     r, full = _bench_line_and_detail(out, det)
@@ -398,6 +398,35 @@ def test_bench_default_line_is_compact_and_carries_configs2_dropin_and_roofline(
     assert "mfma_kernel_families" not in r and "helper_kernels" not in r and "gpu_ms_by_kernel_one_step" not in r
     assert len(full["mfma_kernel_families"]) > 5 and "step_roofline" in full["configs2_bf16"]
     assert full["configs2_bf16"]["config"]["per_gpu_batch"] == 64 and len(full["configs2_bf16"]["mfma_kernel_families"]) > 5
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR`: the headline keys and nothing that takes passes of its own; DIR holds
+    the detections of the last timed step, equal to one detection pass of the same seeded frames in this process."""
+    from m3dssd_amd.host.detect import detect_device, select_block
+    from model.M3d_inference_align import build
+    import bench
+    det, dump = tmp_path / "detail.json", tmp_path / "out"
+    rc, out, err = _run_bench(["--steps", "4", "--warmup", "2", "--dump-outputs", str(dump), "--detail", str(det)], {})
+    assert rc == 0, err[-3000:]
+    r, full = _bench_line_and_detail(out, det)
+    assert r["steps"] == 4 and r["warmup"] == 2 and r["dtype"] == "f32" and r["config"]["per_gpu_batch"] == 8
+    assert r["value"] > 0 and abs(r["value"] - 8 * 4 / (r["ms_per_step"] * 4e-3)) / r["value"] < 0.01
+    for k in ("dropin", "configs2_bf16", "configs3_shard32", "feed_u8", "cpu_baseline", "step_roofline", "sclk_under_step_ghz"):
+        assert k not in r and k not in full, k
+    assert r["roofline"] is None and "mfma_kernel_families" not in full
+    dets, counts = np.load(dump / "detections.npy"), np.load(dump / "counts.npy")
+    assert dets.dtype == np.float32 and counts.dtype == np.float32
+    conf = synth.synth_conf(bench.CROP, 0, batch_size=8, device="cuda:0")
+    net = build(conf, "test")
+    net.load_state_dict(synth.synth_state_dict(0), strict=True)
+    net = net.to(_dev())
+    x = synth.synth_frames(8, bench.CROP, 1234).to(_dev())
+    with torch.no_grad():
+        block, cnt = select_block(*detect_device(net, x, conf), conf)
+    assert dets.shape == (8, int(conf.nms_topN_post), 14) and counts.shape == (8,)
+    assert np.array_equal(counts, cnt.float().cpu().numpy()) and counts.sum() > 0
+    assert np.array_equal(dets, block[:, :-1].cpu().numpy())
 
 
 def test_fp32_forward_is_bit_identical_over_100_runs_at_the_bench_size():

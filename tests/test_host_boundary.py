@@ -33,7 +33,8 @@ def test_module_prefixed_checkpoint_loads_into_the_bare_module(net_and_sd):
     for k in ("base.base.level2.tree1.conv1.weight", "cls.6.bias", "shape_align.align.weight"):
         assert torch.equal(got[k], sd[k])
     # a checkpoint taken from a DataParallel wrapper carries _metadata with 'module.'-prefixed module names too
-    dp_sd = nn.DataParallel(net).state_dict()
+    # (a copy: with one visible GPU, DataParallel moves the module it wraps to cuda:0, and the fixture's module stays on the CPU)
+    dp_sd = nn.DataParallel(copy.deepcopy(net)).state_dict()
     assert all(k.startswith("module.") for k in dp_sd)
     net2 = build(synth.synth_conf(CROP, 0, batch_size=1, device="cpu"), "test")
     net2.load_state_dict(dp_sd, strict=True)
@@ -56,9 +57,11 @@ def test_every_nn_module_load_path_invalidates_the_packed_engine(net_and_sd):
     net.load_state_dict(sd)
     assert net._engine is None
     # through a wrapper: nn.Module.load_state_dict recurses via child._load_from_state_dict, never child.load_state_dict
+    dp = nn.DataParallel(net)                      # (with one visible GPU this moves the module to cuda:0: wrap before planting)
     net._engine = _Sentinel()
-    nn.DataParallel(net).load_state_dict(collections.OrderedDict(("module." + k, v) for k, v in sd.items()))
+    dp.load_state_dict(collections.OrderedDict(("module." + k, v) for k, v in sd.items()))
     assert net._engine is None
+    net.cpu()                                      # back where the fixture built it
     # through a container
     net._engine = _Sentinel()
     holder = nn.ModuleDict({"det": net})

@@ -81,7 +81,7 @@ def main(d, out, launches=None):
         print("pmc_traffic: no source record of the library (%s): bench.py will report this pass as stale" % (e,))
     json.dump({"csrc_files": csrc_files,
                "method": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate runs of "
-                         "`bench.py --steps 3 --warmup 2 --no-graph`; bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB "
+                         "`bench.py --full --steps 3 --warmup 2 --no-graph`; bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB "
                          "(factors calibrated per access width in profiles/r04_pmc_calibration.txt: 2.000 / 1.000 for every width); `families` = the same rows averaged per "
                          "engine family label (aligned with bench.py --dump-launches by dispatch order)",
                "families": fam, "kernels": res},
