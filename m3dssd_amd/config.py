@@ -6,6 +6,11 @@ same access patterns (attribute, ``in``, ``[]``) without the easydict dependency
 ``Config()`` fills the fields RPN/DLASeg read (M3d_inference_align.py:41-63,138-168,
 pose_dla_dcn.py:529) with the shipped values, except ``back_bone`` which this path
 fixes to ``dla34`` (BASELINE.json north_star).
+
+The reference ships three configurations of the one model file; they differ in the three
+flags of ``CONFIG_FLAGS`` (scripts/config/kitti_3d_base.py, kitti_3d_anab.py,
+kitti_3d_anab_fullalign.py: lines 14-18).  ``Config()`` is the fullalign one;
+``Config("base")`` / ``Config("anab")`` give the other two.
 """
 import numpy as np
 
@@ -24,13 +29,27 @@ class Conf(dict):
         return Conf(dict.copy(self))
 
 
-def Config():
+CONFIG_FLAGS = {
+    "base": dict(attention=None, center_align=False, shape_align=False),
+    "anab": dict(attention="ANAB", center_align=False, shape_align=False),
+    "anab_fullalign": dict(attention="ANAB", center_align=True, shape_align=True),
+}
+
+
+def model_flags(conf):
+    """(shape_align, center_align, anab) of a conf, read the way RPN.__init__ / forward of the reference read them
+    (M3d_inference_align.py:138-168,241-277): any ``attention`` other than "ANAB" means no attention block."""
+    attention = conf["attention"] if "attention" in conf else None
+    return bool(conf["shape_align"]), bool(conf["center_align"]), attention == "ANAB"
+
+
+def Config(name="anab_fullalign"):
+    if name not in CONFIG_FLAGS:
+        raise ValueError("unknown configuration %r (one of %s)" % (name, ", ".join(sorted(CONFIG_FLAGS))))
     conf = Conf()
     conf.model = "M3d_inference_align"
     conf.ida_dcnv2 = True
-    conf.attention = "ANAB"
-    conf.center_align = True
-    conf.shape_align = True
+    conf.update(CONFIG_FLAGS[name])
     conf.image_means = [0.485, 0.456, 0.406]
     conf.image_stds = [0.229, 0.224, 0.225]
     conf.feat_stride = 8

@@ -22,6 +22,7 @@ import torch
 
 from . import _hip
 from ._hip import ConvDesc, MlpDesc
+from .config import model_flags
 
 BN_EPS = 1e-5
 SELECT_KEYS = os.environ.get("M3D_SELECT_KEYS", "1") != "0"     # anchor_select also writes the detection stage's sort keys
@@ -220,6 +221,8 @@ class Engine:
         self.A = int(np.asarray(conf.anchors).shape[0]) if not backbone_only else 0
         self.NC = len(conf.lbls) + 1 if not backbone_only else 0
         self.stride = int(conf.feat_stride)
+        # (shape_align, center_align, anab): which stages the plan runs (M3d_inference_align.py:241-277)
+        self.flags = model_flags(conf) if not backbone_only else (False, False, False)
         with torch.cuda.device(self.device):
             self._pack(sd)
         self.plans = {}
@@ -319,15 +322,17 @@ class Engine:
                           "bbox_h3d", "bbox_l3d", "bbox_rY3d"]
         for h in ["cls"] + self.box_heads:
             head(h)
-        for p in ("shape_align", "center_align2d", "center_align3d"):
+        with_shape, with_center, with_anab = self.flags
+        for p in ("shape_align",) * with_shape + ("center_align2d", "center_align3d") * with_center:
             P[p] = PackedConv(self, sd[p + ".align.weight"], sd[p + ".align.bias"], None, cout_pad_to=64)
 
-        a = "bbox_z3d_gl.0"
-        self._pack_anab(P, sd[a + ".query_conv.weight"], sd[a + ".key_conv.weight"], sd[a + ".value_conv.weight"],
-                        sd[a + ".spatial_conv.weight"])
-        g, be, m, v = (t.detach().to(dev, torch.float32) for t in self._bn("bbox_z3d_gl.1"))
-        s = g / torch.sqrt(v + BN_EPS)
-        P["anab.bn.scale"], P["anab.bn.shift"] = s.contiguous(), (be - m * s).contiguous()
+        if with_anab:
+            a = "bbox_z3d_gl.0"
+            self._pack_anab(P, sd[a + ".query_conv.weight"], sd[a + ".key_conv.weight"], sd[a + ".value_conv.weight"],
+                            sd[a + ".spatial_conv.weight"])
+            g, be, m, v = (t.detach().to(dev, torch.float32) for t in self._bn("bbox_z3d_gl.1"))
+            s = g / torch.sqrt(v + BN_EPS)
+            P["anab.bn.scale"], P["anab.bn.shift"] = s.contiguous(), (be - m * s).contiguous()
 
         # constants of the align stages
         anchors = torch.as_tensor(np.asarray(self.conf.anchors), dtype=torch.float32)
@@ -710,17 +715,19 @@ class Engine:
         def box_ptr(k):
             return box_pl.data_ptr() + 4 * k * A * HW          # image 0; per-image stride handled via [B][11][A][HW]
 
-        # shape_align
-        om_sa = self._buf(plan, B, fh, fw, 27, 28)
-        self._op(plan, "shape_align.offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
-            0, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, P["shape.table"].data_ptr(), None, None, None, 0.0, 1.0, 0.0,
-            1.0, om_sa.ptr, om_sa.cs, B, A, HW, 9, 0, st)), nbytes=B * HW * (2 + 28) * 4)
-        feats = self._buf(plan, B, fh, fw, 128, name="feats")
-        self._conv(plan, "shape_align.dcn", P["shape_align"], feats0, feats, 1, 1, act=0, res=feats0, om=om_sa)
-        # heads are grouped by the feature map they read (M3d_inference_align.py:139-176): the four centre heads first,
-        # then both centre alignments, then the six size / orientation heads.
-        heads([("bbox_x", feats, box_planar(0)), ("bbox_y", feats, box_planar(1)),
-               ("bbox_x3d", feats, box_planar(4)), ("bbox_y3d", feats, box_planar(5))])
+        # the stages the configuration has (M3d_inference_align.py:241-277): without shape_align the heads read feats0, without
+        # center_align the size heads read `feats`, without ANAB the z3d head reads feats_align3d; an absent stage's map is
+        # published under its reference name as an alias of the map that stands in for it
+        with_shape, with_center, with_anab = self.flags
+        if with_shape:
+            om_sa = self._buf(plan, B, fh, fw, 27, 28)
+            self._op(plan, "shape_align.offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
+                0, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, P["shape.table"].data_ptr(), None, None, None, 0.0, 1.0, 0.0,
+                1.0, om_sa.ptr, om_sa.cs, B, A, HW, 9, 0, st)), nbytes=B * HW * (2 + 28) * 4)
+            feats = self._buf(plan, B, fh, fw, 128, name="feats")
+            self._conv(plan, "shape_align.dcn", P["shape_align"], feats0, feats, 1, 1, act=0, res=feats0, om=om_sa)
+        else:
+            feats = plan.named["feats"] = feats0
 
         def center_align(p, x, kx, ky, mi, out):
             om = self._buf(plan, B, fh, fw, 3, 4)
@@ -730,18 +737,30 @@ class Engine:
                 float(stds[mi + 1]), om.ptr, om.cs, B, A, HW, 1, 11 * A * HW, st)), nbytes=B * HW * (2 + 2 + 4) * 4)
             self._conv(plan, p + ".dcn", P[p], x, out, 1, 0, act=0, res=x, om=om)
 
-        f2d = self._buf(plan, B, fh, fw, 128, name="feats_align2d")
-        center_align("center_align2d", feats, 0, 1, 0, f2d)
-        f3d = self._buf(plan, B, fh, fw, 128, name="feats_align3d")
-        center_align("center_align3d", feats, 4, 5, 4, f3d)
-        heads([("bbox_w", f2d, box_planar(2)), ("bbox_h", f2d, box_planar(3)),
-               ("bbox_w3d", f3d, box_planar(7)), ("bbox_h3d", f3d, box_planar(8)),
-               ("bbox_l3d", f3d, box_planar(9)), ("bbox_rY3d", f3d, box_planar(10))])
+        # heads are grouped by the feature map they read (M3d_inference_align.py:139-176): the four centre heads first,
+        # then both centre alignments, then the six size / orientation heads (+ z3d without ANAB).  Without the centre
+        # alignments every box head but an ANAB-fed z3d reads `feats`: one launch.
+        z3d_now = [] if with_anab else ["bbox_z3d"]
+        if with_center:
+            heads([("bbox_x", feats, box_planar(0)), ("bbox_y", feats, box_planar(1)),
+                   ("bbox_x3d", feats, box_planar(4)), ("bbox_y3d", feats, box_planar(5))])
+            f2d = self._buf(plan, B, fh, fw, 128, name="feats_align2d")
+            center_align("center_align2d", feats, 0, 1, 0, f2d)
+            f3d = self._buf(plan, B, fh, fw, 128, name="feats_align3d")
+            center_align("center_align3d", feats, 4, 5, 4, f3d)
+            heads([("bbox_w", f2d, box_planar(2)), ("bbox_h", f2d, box_planar(3))] +
+                  [(h, f3d, box_planar(self.box_heads.index(h))) for h in z3d_now + ["bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d"]])
+        else:
+            f2d = f3d = plan.named["feats_align2d"] = plan.named["feats_align3d"] = feats
+            heads([(h, feats, box_planar(k)) for k, h in enumerate(self.box_heads) if h != "bbox_z3d" or not with_anab])
 
         # ---- ANAB ---------------------------------------------------------------------
-        gl = self._buf(plan, B, fh, fw, 128, name="feats_gl")
-        self._anab_ops(plan, f3d, gl, P["anab.bn.scale"], P["anab.bn.shift"], act=1, res_mode=1)
-        head("bbox_z3d", gl, box_planar(6))
+        if with_anab:
+            gl = self._buf(plan, B, fh, fw, 128, name="feats_gl")
+            self._anab_ops(plan, f3d, gl, P["anab.bn.scale"], P["anab.bn.shift"], act=1, res_mode=1)
+            head("bbox_z3d", gl, box_planar(6))
+        else:
+            plan.named["feats_gl"] = f3d
 
         # ---- outputs ------------------------------------------------------------------
         cls = torch.empty(B, R, NC, device=self.device, dtype=torch.float32)

@@ -284,20 +284,22 @@ class EngineBF16(Engine):
             P[p + ".0"] = self._pc(p + ".0", p + ".1")
             P[p + ".3"] = self._pc(p + ".3", p + ".4")
             P[p + ".6"] = self._pc(p + ".6", cout_pad=_rup(sd[p + ".6.weight"].shape[0], 64))
-        for p in ("shape_align", "center_align2d", "center_align3d"):
+        with_shape, with_center, with_anab = self.flags
+        for p in ("shape_align",) * with_shape + ("center_align2d", "center_align3d") * with_center:
             P[p] = PackedBf16(self, sd[p + ".align.weight"], sd[p + ".align.bias"], None)
-        a = "bbox_z3d_gl.0"
-        wq, wk, wv, ws = (sd[a + n].detach().cpu().float() for n in
-                          (".query_conv.weight", ".key_conv.weight", ".value_conv.weight", ".spatial_conv.weight"))
-        self.ck, self.cv, self.ns = wq.shape[0], wv.shape[0], ws.shape[0]
-        self.ck_pad = _rup(self.ck, 64)                                  # K of the logits GEMM
-        P["anab.q"] = PackedBf16(self, wq, None, None, cout_pad=self.ck_pad)
-        P["anab.kvs"] = PackedBf16(self, torch.cat([wk, wv, ws], 0), None, None)
-        P["anab.kv"] = PackedBf16(self, torch.cat([wk, wv], 0), None, None)          # bf16 K|V map + fp32 gates (KV_BF16)
-        P["anab.s"] = PackedBf16(self, ws, None, None)
-        g, be, m, v = (t.detach().to(dev, torch.float32) for t in self._bn("bbox_z3d_gl.1"))
-        s = g / torch.sqrt(v + BN_EPS)
-        P["anab.bn.scale"], P["anab.bn.shift"] = s.contiguous(), (be - m * s).contiguous()
+        if with_anab:
+            a = "bbox_z3d_gl.0"
+            wq, wk, wv, ws = (sd[a + n].detach().cpu().float() for n in
+                              (".query_conv.weight", ".key_conv.weight", ".value_conv.weight", ".spatial_conv.weight"))
+            self.ck, self.cv, self.ns = wq.shape[0], wv.shape[0], ws.shape[0]
+            self.ck_pad = _rup(self.ck, 64)                                  # K of the logits GEMM
+            P["anab.q"] = PackedBf16(self, wq, None, None, cout_pad=self.ck_pad)
+            P["anab.kvs"] = PackedBf16(self, torch.cat([wk, wv, ws], 0), None, None)
+            P["anab.kv"] = PackedBf16(self, torch.cat([wk, wv], 0), None, None)          # bf16 K|V map + fp32 gates (KV_BF16)
+            P["anab.s"] = PackedBf16(self, ws, None, None)
+            g, be, m, v = (t.detach().to(dev, torch.float32) for t in self._bn("bbox_z3d_gl.1"))
+            s = g / torch.sqrt(v + BN_EPS)
+            P["anab.bn.scale"], P["anab.bn.shift"] = s.contiguous(), (be - m * s).contiguous()
         anchors = torch.as_tensor(np.asarray(self.conf.anchors), dtype=torch.float32)
         aw = (anchors[:, 2] - anchors[:, 0])
         ah = (anchors[:, 3] - anchors[:, 1])
@@ -630,6 +632,23 @@ class EngineBF16(Engine):
                          planar=(box_pl, 11 * A * HW, first_box_index * A), groups=G, in_goff=256, wgt_goff=cp * 256,
                          out_goff=A * HW, ss_goff=A, cin=256)
 
+        def anab_z3d(x):
+            """ANAB + the z3d head behind it (reads x = feats_align3d, writes its own planar rows); returns its first op."""
+            b0 = len(plan.ops)
+            gl = self._buf16(plan, B, fh, fw, 128, name="feats_gl")
+            self._anab_bf16(plan, x, gl)
+            heads(["bbox_z3d"], gl, 6)
+            return b0
+
+        # the stages the configuration has (M3d_inference_align.py:241-277); an absent stage's map is published under its
+        # reference name as an alias of the map that stands in for it
+        with_shape, with_center, with_anab = self.flags
+        branch = None
+        if with_anab and not (with_shape or with_center):
+            # ANAB reads feats0: its side branch starts where feats0 is ready, beside the cls head and the box heads
+            b0 = anab_z3d(feats0)
+            branch = (b0, len(plan.ops))
+
         # cls head: 3x3 128 -> 256, 1x1 256 -> 256, 1x1 256 -> NC*A (planar fp32)
         c1 = self._buf16(plan, B, fh, fw, 256)
         self._pconv(plan, "cls.0", P["cls.0"], feats0, c1, 1, 1, act=1)
@@ -675,43 +694,60 @@ class EngineBF16(Engine):
         def box_ptr(k):
             return box_pl.data_ptr() + 4 * k * A * HW
 
-        om_sa = self._buf16(plan, B, fh, fw, 27, 28, dtype=torch.float32)
-        self._op(plan, "shape_align.offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
-            0, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, P["shape.table"].data_ptr(), None, None, None, 0.0, 1.0, 0.0,
-            1.0, om_sa.ptr, om_sa.cs, B, A, HW, 9, 0, st)))
-        feats = self._buf16(plan, B, fh, fw, 128, name="feats")
-        self._pconv(plan, "shape_align.dcn", P["shape_align"], feats0, feats, 1, 1, act=0, res=feats0, om=om_sa,
-                    patch=SHAPE_PATCH)   # anchor-shaped offsets (up to half an anchor): which tiles fit the LDS window is decided per tile
-        heads(["bbox_x", "bbox_y"], feats, 0)
-        heads(["bbox_x3d", "bbox_y3d"], feats, 4)
+        if with_shape:
+            om_sa = self._buf16(plan, B, fh, fw, 27, 28, dtype=torch.float32)
+            self._op(plan, "shape_align.offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
+                0, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, P["shape.table"].data_ptr(), None, None, None, 0.0, 1.0, 0.0,
+                1.0, om_sa.ptr, om_sa.cs, B, A, HW, 9, 0, st)))
+            feats = self._buf16(plan, B, fh, fw, 128, name="feats")
+            self._pconv(plan, "shape_align.dcn", P["shape_align"], feats0, feats, 1, 1, act=0, res=feats0, om=om_sa,
+                        patch=SHAPE_PATCH)   # anchor-shaped offsets (up to half an anchor): which tiles fit the LDS window is decided per tile
+        else:
+            feats = plan.named["feats"] = feats0
 
-        def center_align(p, x, kx, ky, mi, out):
-            om = self._buf16(plan, B, fh, fw, 3, 4, dtype=torch.float32)
-            self._op(plan, p + ".offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
-                1, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, None, box_ptr(kx), box_ptr(ky),
-                P["anchor_wh"].data_ptr(), float(means[mi]), float(stds[mi]), float(means[mi + 1]),
-                float(stds[mi + 1]), om.ptr, om.cs, B, A, HW, 1, 11 * A * HW, st)))
-            self._pconv(plan, p + ".dcn", P[p], x, out, 1, 0, act=0, res=x, om=om)
+        if with_center:
+            heads(["bbox_x", "bbox_y"], feats, 0)
+            heads(["bbox_x3d", "bbox_y3d"], feats, 4)
 
-        f2d = self._buf16(plan, B, fh, fw, 128, name="feats_align2d")
-        center_align("center_align2d", feats, 0, 1, 0, f2d)
-        f3d = self._buf16(plan, B, fh, fw, 128, name="feats_align3d")
-        center_align("center_align3d", feats, 4, 5, 4, f3d)
+            def center_align(p, x, kx, ky, mi, out):
+                om = self._buf16(plan, B, fh, fw, 3, 4, dtype=torch.float32)
+                self._op(plan, p + ".offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
+                    1, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, None, box_ptr(kx), box_ptr(ky),
+                    P["anchor_wh"].data_ptr(), float(means[mi]), float(stds[mi]), float(means[mi + 1]),
+                    float(stds[mi + 1]), om.ptr, om.cs, B, A, HW, 1, 11 * A * HW, st)))
+                self._pconv(plan, p + ".dcn", P[p], x, out, 1, 0, act=0, res=x, om=om)
+
+            f2d = self._buf16(plan, B, fh, fw, 128, name="feats_align2d")
+            center_align("center_align2d", feats, 0, 1, 0, f2d)
+            f3d = self._buf16(plan, B, fh, fw, 128, name="feats_align3d")
+            center_align("center_align3d", feats, 4, 5, 4, f3d)
+        else:
+            f2d = f3d = plan.named["feats_align2d"] = plan.named["feats_align3d"] = feats
         # ANAB + the z3d head (reads feats_align3d, writes its own planar rows) next to the six size / orientation heads: the pooling and
         # attention launches leave most of the chip idle (a reduction over pixels, 337 keys) -- as a side branch of the plan they run
         # beside the head launches (Engine._run_plan; M3D_BF16_BRANCH=0: one stream)
         # Measured again with the planar detector (tools/ab_replay.sh, one lease): 10.35-10.40 ms with the branch, without it, and with a
         # reordered tail that puts the pooling beside the x / y heads + the 2-D alignment: the head kernel is persistent and owns every
         # register of every CU, so a side branch only fills the wind-down of its launches -- the step is the SUM of its kernels.
-        b0 = len(plan.ops)
-        gl = self._buf16(plan, B, fh, fw, 128, name="feats_gl")
-        self._anab_bf16(plan, f3d, gl)
-        heads(["bbox_z3d"], gl, 6)
-        b1 = len(plan.ops)
-        heads(["bbox_w", "bbox_h"], f2d, 2)
-        heads(["bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d"], f3d, 7)
-        if BRANCH:
-            plan.branches.append((b0, b1, len(plan.ops)))
+        if with_anab and branch is None:
+            b0 = anab_z3d(f3d)
+            branch = (b0, len(plan.ops))
+        if with_center:
+            heads(["bbox_w", "bbox_h"], f2d, 2)
+            if with_anab:
+                heads(["bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d"], f3d, 7)
+            else:
+                heads(["bbox_z3d", "bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d"], f3d, 6)
+        elif with_anab:
+            # every box head but z3d reads `feats`: planar rows 0-5 and 7-10 (a launch takes consecutive rows)
+            heads(self.box_heads[0:6], feats, 0)
+            heads(self.box_heads[7:11], feats, 7)
+        else:
+            heads(self.box_heads, feats, 0)
+        if not with_anab:
+            plan.named["feats_gl"] = f3d
+        elif BRANCH:
+            plan.branches.append(branch + (len(plan.ops),))
 
         cls = torch.empty(B, R, NC, device=self.device, dtype=torch.float32)
         prob = torch.empty(B, R, NC, device=self.device, dtype=torch.float32)

@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from .. import rpn_util
+from ..config import model_flags
 from ..engine import Engine
 from .align import center_align, shape_align
 from .attention import ANAB
@@ -49,23 +50,31 @@ class RPN(nn.Module):
         self.rois = self.rois.float().to(self.device)
         from .detect import check_conf
         check_conf(conf)
-        if not (conf.center_align and conf.shape_align and self.attention == "ANAB"):
-            raise NotImplementedError("this build implements the anab_fullalign configuration "
-                                      "(center_align, shape_align, attention='ANAB')")
+        # the sub-modules exist as in the reference (M3d_inference_align.py:138-189): the align stages only when their flag is
+        # on, the attention block only for attention == "ANAB"; the engine builds its plan from the same flags
+        with_shape, with_center, with_anab = model_flags(conf)
         c, m, a = self.base_channels, self.head_channels, self.num_anchors
         self.cls = _head(c, m, a * self.num_classes, 3)
         for h in BOX_HEADS_A:
             setattr(self, h, _head(c, m, a, 1))
-        self.center_align2d = center_align(c, self.anchors, xy_mean=self.bbox_means[0:2], xy_std=self.bbox_stds[0:2],
-                                           feat_stride=self.feat_stride, feat_size=self.feat_size, kernel_size=1, k=1,
-                                           thresh=0.5)
-        self.center_align3d = center_align(c, self.anchors, xy_mean=self.bbox_means[4:6], xy_std=self.bbox_stds[4:6],
-                                           feat_stride=self.feat_stride, feat_size=self.feat_size, kernel_size=1, k=1,
-                                           thresh=0.5)
-        self.shape_align = shape_align(c, self.anchors, feat_stride=self.feat_stride, feat_size=self.feat_size,
-                                       kernel_size=3, k=1, thresh=0.5)
+        if with_center:
+            self.center_align2d = center_align(c, self.anchors, xy_mean=self.bbox_means[0:2], xy_std=self.bbox_stds[0:2],
+                                               feat_stride=self.feat_stride, feat_size=self.feat_size, kernel_size=1, k=1,
+                                               thresh=0.5)
+            self.center_align3d = center_align(c, self.anchors, xy_mean=self.bbox_means[4:6], xy_std=self.bbox_stds[4:6],
+                                               feat_stride=self.feat_stride, feat_size=self.feat_size, kernel_size=1, k=1,
+                                               thresh=0.5)
+        else:
+            self.center_align2d = None
+            self.center_align3d = None
+        if with_shape:
+            self.shape_align = shape_align(c, self.anchors, feat_stride=self.feat_stride, feat_size=self.feat_size,
+                                           kernel_size=3, k=1, thresh=0.5)
+        else:
+            self.shape_align = None
         self.bbox_z3d = _head(c, m, a, 1)
-        self.bbox_z3d_gl = nn.Sequential(ANAB(c, 1), nn.BatchNorm2d(c), nn.LeakyReLU(inplace=True))
+        if with_anab:
+            self.bbox_z3d_gl = nn.Sequential(ANAB(c, 1), nn.BatchNorm2d(c), nn.LeakyReLU(inplace=True))
         for h in BOX_HEADS_B:
             setattr(self, h, _head(c, m, a, 1))
         self.softmax = nn.Softmax(dim=1)

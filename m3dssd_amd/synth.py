@@ -5,7 +5,8 @@ The reference ships no trained weights, no KITTI data and no pickled ``conf``
 parity tests all use a deterministic synthetic recipe (numpy PCG64, one stream per
 tensor keyed by crc32 of its state_dict name, so values do not depend on order):
 
-* ``param_spec`` lists every state_dict entry of ``RPN(dla34)`` -- 542 tensors, the
+* ``param_spec`` lists every state_dict entry of ``RPN(dla34)`` -- 542 tensors (fullalign;
+  526 for base, 535 for anab), the
   contract in SURVEY.md 8b; tools/gen_golden.py asserts it equals the reference
   model's own ``state_dict()`` keys and shapes.
 * conv_offset_mask is re-randomised (the reference zero-inits it,
@@ -21,7 +22,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .config import Config
+from .config import CONFIG_FLAGS, Config
 from . import rpn_util
 
 HEADS = ["cls", "bbox_x", "bbox_y", "bbox_w", "bbox_h", "bbox_x3d", "bbox_y3d"]
@@ -94,8 +95,10 @@ def _head(spec, p, ci, co, k0):
     _conv(spec, p + ".6", co, 256, 1, True)
 
 
-def param_spec(num_anchors=36, num_classes=4):
-    """OrderedDict name -> shape, in the reference's registration order."""
+def param_spec(num_anchors=36, num_classes=4, shape_align=True, center_align=True, attention="ANAB"):
+    """OrderedDict name -> shape, in the reference's registration order.  The flags drop the sub-modules the reference does not
+    create (M3d_inference_align.py:138-168): the align modules when their flag is off, bbox_z3d_gl unless attention == "ANAB";
+    the defaults give the fullalign model."""
     s = OrderedDict()
     ch = [16, 32, 64, 128, 256, 512]
     b = "base.base"
@@ -115,18 +118,21 @@ def param_spec(num_anchors=36, num_classes=4):
     _head(s, "cls", 128, num_anchors * num_classes, 3)
     for h in HEADS[1:]:
         _head(s, h, 128, num_anchors, 1)
-    for p in ("center_align2d", "center_align3d"):
-        s[p + ".align.weight"] = (128, 128, 1, 1)
-        s[p + ".align.bias"] = (128,)
-    s["shape_align.align.weight"] = (128, 128, 3, 3)
-    s["shape_align.align.bias"] = (128,)
-    s["shape_align.proj.weight"] = (128, 256, 1, 1)
+    if center_align:
+        for p in ("center_align2d", "center_align3d"):
+            s[p + ".align.weight"] = (128, 128, 1, 1)
+            s[p + ".align.bias"] = (128,)
+    if shape_align:
+        s["shape_align.align.weight"] = (128, 128, 3, 3)
+        s["shape_align.align.bias"] = (128,)
+        s["shape_align.proj.weight"] = (128, 256, 1, 1)
     _head(s, "bbox_z3d", 128, num_anchors, 1)
-    s["bbox_z3d_gl.0.value_conv.weight"] = (128, 128, 1, 1)
-    s["bbox_z3d_gl.0.spatial_conv.weight"] = (4, 128, 1, 1)
-    s["bbox_z3d_gl.0.key_conv.weight"] = (168, 128, 1, 1)
-    s["bbox_z3d_gl.0.query_conv.weight"] = (168, 128, 1, 1)
-    _bn(s, "bbox_z3d_gl.1", 128)
+    if attention == "ANAB":
+        s["bbox_z3d_gl.0.value_conv.weight"] = (128, 128, 1, 1)
+        s["bbox_z3d_gl.0.spatial_conv.weight"] = (4, 128, 1, 1)
+        s["bbox_z3d_gl.0.key_conv.weight"] = (168, 128, 1, 1)
+        s["bbox_z3d_gl.0.query_conv.weight"] = (168, 128, 1, 1)
+        _bn(s, "bbox_z3d_gl.1", 128)
     for h in HEADS_TAIL2:
         _head(s, h, 128, num_anchors, 1)
     return s
@@ -147,8 +153,16 @@ def _bilinear_up(shape):
     return w
 
 
-def synth_state_dict(seed=0, num_anchors=36, num_classes=4):
-    spec = param_spec(num_anchors, num_classes)
+def config_flags(name):
+    """The flag keywords of param_spec / synth_state_dict / synth_conf for a shipped configuration
+    ("base", "anab", "anab_fullalign")."""
+    return dict(CONFIG_FLAGS[name])
+
+
+def synth_state_dict(seed=0, num_anchors=36, num_classes=4, shape_align=True, center_align=True, attention="ANAB"):
+    """Every tensor is drawn from its own stream keyed by its name: a configuration without some sub-modules gets the same
+    values for the keys it shares with the fullalign dict."""
+    spec = param_spec(num_anchors, num_classes, shape_align, center_align, attention)
     sd = OrderedDict()
     for name, shape in spec.items():
         g = _rng(seed, name)
@@ -199,11 +213,13 @@ def synth_state_dict(seed=0, num_anchors=36, num_classes=4):
     return sd
 
 
-def synth_conf(crop_size=(384, 1280), seed=0, batch_size=1, device="cuda:0"):
+def synth_conf(crop_size=(384, 1280), seed=0, batch_size=1, device="cuda:0", shape_align=True, center_align=True,
+               attention="ANAB"):
     """Stand-in for the pickled training conf: 2-D anchors from the reference recipe
     (lib/rpn_util.py:39-52,167-183), seeded 3-D anchor columns and bbox_means/stds."""
     rng = np.random.Generator(np.random.PCG64([seed, 0xC0F]))
     conf = Config()
+    conf.attention, conf.center_align, conf.shape_align = attention, center_align, shape_align
     conf.crop_size = list(crop_size)
     conf.batch_size = batch_size
     conf.device = device

@@ -1,0 +1,106 @@
+#!/usr/bin/env python
+"""Generate tests/golden/model_{base,anab}_128x320_b2.npz by running the REFERENCE's own model file for the two shipped
+configurations other than fullalign (scripts/config/kitti_3d_base.py, kitti_3d_anab.py).
+
+Build-container only, like tools/gen_golden.py (whose stubs it reuses): needs the reference tree and never travels to the GPU
+box.  Per configuration it builds ``model.M3d_inference_align.build(conf, 'test')`` with the configuration's flags, loads the
+seed-0 synthetic state_dict filtered to that configuration with strict=True (the key list of the reference's own module must
+equal ``synth.param_spec`` with the same flags, in order), runs B=2 frames of 128x320 and writes, in the layout of
+model_128x320_b2.npz:
+
+* ``cls`` / ``prob`` / ``bbox_2d`` / ``bbox_3d``: every ``row_stride``-th row, ``feat_size``; ``chk.*`` float64 checksums
+  (sum, sum |.|, size) of the full outputs and rois;
+* ``tap.feats0`` (and ``tap.feats_gl`` with ANAB): every 8th channel, ``chk.*`` of the full maps;
+* ``keys`` / ``key_shapes``: the reference module's state_dict keys and shapes;
+* ``aboxes``: the reference's im_detect_3d rows of image 0 (torch .cuda() shimmed to a no-op), as detect_128x320.npz.
+
+Run:  python tools/gen_golden_configs.py [OUT_DIR]       (default tests/golden; about a minute)
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gen_golden  # noqa: E402
+
+CONFIGS = ("base", "anab")
+CROP, BATCH, ROW_STRIDE = (128, 320), 2, 4
+TAPS = {"base": "feats0", "bbox_z3d_gl": "feats_gl"}
+
+
+def golden_name(config):
+    return "model_%s_%dx%d_b%d.npz" % (config, CROP[0], CROP[1], BATCH)
+
+
+def main(out_dir):
+    gen_golden._install_stubs()
+    import torch
+    torch.set_num_threads(8)
+    from m3dssd_amd import synth
+    import lib.rpn_util as ref_rpn
+    import model.M3d_inference_align as ref_model
+    from easydict import EasyDict
+
+    os.makedirs(out_dir, exist_ok=True)
+    checks = gen_golden._checks
+    for config in CONFIGS:
+        flags = synth.config_flags(config)
+        conf = synth.synth_conf(CROP, 0, batch_size=BATCH, device="cpu", **flags)
+        sd = synth.synth_state_dict(0, **flags)
+        net = ref_model.build(EasyDict(dict(conf)), "test")
+        net.load_state_dict(sd, strict=True)
+        ref_keys = [(k, tuple(v.shape)) for k, v in net.state_dict().items()]
+        assert ref_keys == [(k, tuple(v.shape)) for k, v in sd.items()], "state_dict contract mismatch (%s)" % config
+        x = synth.synth_frames(BATCH, CROP, 1234)
+        taps, hooks = {}, []
+        mods = dict(net.named_modules())
+        for mname, tname in TAPS.items():
+            if mname in mods:
+                hooks.append(mods[mname].register_forward_hook(
+                    lambda m, i, o, tname=tname: taps.__setitem__(tname, o.detach().clone())))
+        with torch.no_grad():
+            out = net(x)
+        for h in hooks:
+            h.remove()
+        cls, prob, b2, b3, fs, rois = out
+        rs = ROW_STRIDE
+        g = {"row_stride": np.array(rs), "cls": cls[:, ::rs].numpy(), "prob": prob[:, ::rs].numpy(),
+             "bbox_2d": b2[:, ::rs].numpy(), "bbox_3d": b3[:, ::rs].numpy(), "feat_size": fs.numpy()}
+        for name, t in (("cls", cls), ("prob", prob), ("bbox_2d", b2), ("bbox_3d", b3), ("rois", rois)):
+            g["chk." + name] = checks(t)
+        for k, v in taps.items():
+            g["tap." + k] = v[:, ::8].numpy()
+            g["chk." + k] = checks(v)
+        g["keys"] = np.array([k for k, _ in ref_keys])
+        g["key_shapes"] = np.array([",".join(str(d) for d in s) for _, s in ref_keys])
+
+        # im_detect_3d on the reference outputs (image 0), .cuda() shimmed away
+        cuda, float_tensor = torch.Tensor.cuda, getattr(torch.cuda, "FloatTensor", None)
+        torch.Tensor.cuda = lambda self, *a, **k: self
+        torch.cuda.FloatTensor = torch.FloatTensor
+
+        class Obj:
+            imH, imW, p2, scale_factor = CROP[0], CROP[1], np.eye(4), 1.0
+
+        class FakeNet:
+            def eval(self):
+                return self
+
+            def __call__(self, im):
+                return tuple(o.clone() for o in out)
+        try:
+            g["aboxes"] = ref_rpn.im_detect_3d(x[:1], FakeNet(), EasyDict(dict(conf)), Obj())
+        finally:
+            torch.Tensor.cuda = cuda
+            torch.cuda.FloatTensor = float_tensor
+        path = os.path.join(out_dir, golden_name(config))
+        np.savez_compressed(path, **g)
+        fg = (1 - prob[:, :, 0]).view(BATCH, -1, CROP[0] // 8, CROP[1] // 8).max(dim=1)[0]
+        print("%-5s %d keys, hard-mask fraction %.3f, %d detections, %s %.1f KB"
+              % (config, len(ref_keys), (fg > 0.5).float().mean().item(), g["aboxes"].shape[0], path,
+                 os.path.getsize(path) / 1024))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1] if len(sys.argv) > 1 else gen_golden.OUT)
