@@ -379,8 +379,8 @@ int m3d_softmax_rows_bf16(const float *x, int rows, int valid, int cs, void *out
 /* ------------------------------------------------------------------------------------------
  * Fused RPN head (model/M3d_inference_align.py:77-210): per-pixel MLP
  *   [1x1 Cin->256 + affine + LeakyReLU] -> 1x1 256->256 + affine + LeakyReLU -> 1x1 256->Cout + affine
- * in ONE launch; hidden activations stay in LDS.  Cin = 128 with w1 given (3 layers) or Cin = 256 with
- * w1 = NULL (2 layers: `in` is already the first hidden activation, e.g. after the 3x3 cls conv).
+ * in ONE launch; hidden activations stay in LDS.  Cin = 128 or 256 with w1 given (3 layers; 256: the DLA-102 heads) or
+ * Cin = 256 with w1 = NULL (2 layers: `in` is already the first hidden activation, e.g. after the 3x3 cls conv).
  * Weights are packed in MFMA-fragment order: element W[J*32 + r][G*8 + h*4 + t] (row-tile J, k-group G,
  * r < 32, h < 2, t < 4) at float index ((J*(K/8) + G)*64 + h*32 + r)*4 + t; rows zero-padded to 256 for
  * w1/w2 and to Cout_pad in {64, 256} for w3.  Output is planar: out[n*out_img_stride + c*HW + p].
@@ -399,7 +399,7 @@ typedef struct m3d_mlp_desc {
     int HW;
 } m3d_mlp_desc;
 int m3d_head_mlp_forward(const m3d_mlp_desc *d, m3d_stream_t stream);
-/* n (<= 16) independent heads of the same depth, M and Cout_pad in ONE launch (grid.y = head): the regression heads
+/* n (<= 16) independent heads of the same depth, M, Cin and Cout_pad in ONE launch (grid.y = head): the regression heads
  * that read the same aligned feature map (M3d_inference_align.py:139-176) have no mutual dependency. */
 int m3d_head_mlp_forward_batched(const m3d_mlp_desc *d, int n, m3d_stream_t stream);
 
@@ -519,7 +519,8 @@ int m3d_anab_pool_nested_bf16_ex(const void *kv, int kv_cs, const float *s, int 
  * block): out[p] = act(softmax_k(q[p] . khat[k]) @ vhat (+ res[p], scale, shift)) per image, replacing the logits GEMM, the row softmax
  * and the P.V GEMM (the logits never reach memory; one pass over the keys with a running maximum).  q [B*HW][q_cs] (first Ck
  * channels), khat [B][keys_pad][k_cs] and vhatT [B][Cv][keys_pad] row-major as m3d_anab_pool_nested / _finish write them with
- * frag = 0; Ck in {64, 128, 168}, Cv = 128, HW % 128 == 0, keys_pad % 32 == 0; res_mode as in m3d_conv_desc (0: + res behind the
+ * frag = 0; Ck in {64, 128, 168} with Cv = 128, or Ck = 168 with Cv = 256 (DLA-102: two workgroups per pixel tile, one per
+ * half of the value channels), HW % 128 == 0, keys_pad % 32 == 0; res_mode as in m3d_conv_desc (0: + res behind the
  * affine, 1: before it); scale / shift / res may be NULL.
  * PRECONDITION (not checked): khat rows [keys, keys_pad) and vhatT columns [keys, keys_pad) hold finite values (zeros), as for
  * m3d_anab_attend_bf16. */

@@ -4,8 +4,9 @@ The reference passes an ``EasyDict`` (scripts/config/kitti_3d_anab_fullalign.py:
 re-read from a pickle at test time, scripts/test_rpn_3d.py:27).  ``Conf`` gives the
 same access patterns (attribute, ``in``, ``[]``) without the easydict dependency;
 ``Config()`` fills the fields RPN/DLASeg read (M3d_inference_align.py:41-63,138-168,
-pose_dla_dcn.py:529) with the shipped values, except ``back_bone`` which this path
-fixes to ``dla34`` (BASELINE.json north_star).
+pose_dla_dcn.py:529) with the shipped values, except ``back_bone`` which defaults to
+``dla34`` (BASELINE.json north_star); the shipped configurations' ``dla102`` is
+``Config(back_bone="dla102")`` (fp32 only, see BACK_BONES).
 
 The reference ships three configurations of the one model file; they differ in the three
 flags of ``CONFIG_FLAGS`` (scripts/config/kitti_3d_base.py, kitti_3d_anab.py,
@@ -29,6 +30,8 @@ class Conf(dict):
         return Conf(dict.copy(self))
 
 
+BACK_BONES = ("dla34", "dla102")
+
 CONFIG_FLAGS = {
     "base": dict(attention=None, center_align=False, shape_align=False),
     "anab": dict(attention="ANAB", center_align=False, shape_align=False),
@@ -43,9 +46,11 @@ def model_flags(conf):
     return bool(conf["shape_align"]), bool(conf["center_align"]), attention == "ANAB"
 
 
-def Config(name="anab_fullalign"):
+def Config(name="anab_fullalign", back_bone="dla34"):
     if name not in CONFIG_FLAGS:
         raise ValueError("unknown configuration %r (one of %s)" % (name, ", ".join(sorted(CONFIG_FLAGS))))
+    if back_bone not in BACK_BONES:
+        raise ValueError("unknown back_bone %r (one of %s)" % (back_bone, ", ".join(BACK_BONES)))
     conf = Conf()
     conf.model = "M3d_inference_align"
     conf.ida_dcnv2 = True
@@ -53,7 +58,7 @@ def Config(name="anab_fullalign"):
     conf.image_means = [0.485, 0.456, 0.406]
     conf.image_stds = [0.229, 0.224, 0.225]
     conf.feat_stride = 8
-    conf.back_bone = "dla34"
+    conf.back_bone = back_bone
     conf.pre_train = False
     conf.test_scale = [384, 1280]
     conf.crop_size = [384, 1280]

@@ -16,6 +16,12 @@
 //       operand reads vhat^T[cv][8i + 4h + j]: the exponentials ARE the B operands, no exchange; the A operands are four runs of
 //       four consecutive keys per lane.
 //   Per tile and wave 84 + 64 MFMAs (9 472 cycles): the kernel is MFMA-bound by construction; two workgroups per CU.
+//
+//   Cv = 256 (DLA-102: the value channels are the backbone's 256): NSPLIT = 2 workgroups per pixel tile (grid.y) own 128 value
+//   channels each and both compute the same logits.  Holding all 256 channels in one workgroup would double the P.V accumulators
+//   (o[8]: 128 registers) on top of q (84 at Ck = 168), the logit tile and the staging registers -- past the 256 registers a lane
+//   may hold at two waves per SIMD, i.e. one workgroup per CU and no overlap of one workgroup's softmax with the other's MFMAs.  The
+//   split repeats QK (0.43 GMAC per 384x1280 image) beside 0.66 GMAC of P.V and keeps the Cv = 128 register budget and occupancy.
 #include <stdlib.h>
 
 #include "common.h"
@@ -30,7 +36,7 @@ struct AnabF32Args {
     int q_cs, k_cs, HW, Ck, keys, keys_pad, res_cs, out_cs, res_mode, act;
 };
 
-template <int CK>                        // key / query channels (multiple of 8)
+template <int CK, int NSPLIT = 1>      // key / query channels (multiple of 8); value-channel groups of AF_CV (grid.y)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void anab_attend_f32_kernel(const AnabF32Args a)
 {
     constexpr int KROW = CK * 4 + 16;    // bytes per khat tile row in LDS (+16: rows of 8 neighbouring keys start in different banks)
@@ -52,7 +58,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int t = 0; t < NS4; ++t) qf[t] = *reinterpret_cast<const f32x4 *>(qp + 8 * t);
     }
     const float *kimg = a.khat + (size_t)img * a.keys_pad * a.k_cs;
-    const float *vimg = a.vhat + (size_t)img * AF_CV * a.keys_pad;
+    const int cv0 = NSPLIT > 1 ? (int)blockIdx.y * AF_CV : 0;    // this workgroup's value channels: cv0 .. cv0 + AF_CV
+    const float *vimg = a.vhat + ((size_t)img * NSPLIT * AF_CV + cv0) * a.keys_pad;
 
     // staging: khat tile = 32 rows x CK / 4 pieces of 16 B; vhat^T tile = 128 rows x 8 pieces
     constexpr int KP = AF_KT * (CK / 4), KPT = (KP + 255) / 256;
@@ -147,8 +154,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     // ---- epilogue: lane = pixel, register r of block j = channel 32 j + 8 (r / 4) + 4 h + r % 4: 16-byte pieces -------------------
     const float slope = a.act ? M3D_LEAKY_SLOPE : 1.f;
-    float *op = a.out + (size_t)mq * a.out_cs;
-    const float *rp = a.res ? a.res + (size_t)mq * a.res_cs : nullptr;
+    float *op = a.out + (size_t)mq * a.out_cs + cv0;
+    const float *rp = a.res ? a.res + (size_t)mq * a.res_cs + cv0 : nullptr;
+    const float *scp = a.scale ? a.scale + cv0 : nullptr, *shp = a.shift ? a.shift + cv0 : nullptr;
 #pragma unroll
     for (int j = 0; j < AF_CV / 32; ++j)
 #pragma unroll
@@ -156,8 +164,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int c = 32 * j + 8 * i + 4 * lh;
             f32x4 v = {o[j][4 * i] * inv, o[j][4 * i + 1] * inv, o[j][4 * i + 2] * inv, o[j][4 * i + 3] * inv};
             f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-            if (a.scale) sc = *reinterpret_cast<const f32x4 *>(a.scale + c);
-            if (a.shift) sh = *reinterpret_cast<const f32x4 *>(a.shift + c);
+            if (scp) sc = *reinterpret_cast<const f32x4 *>(scp + c);
+            if (shp) sh = *reinterpret_cast<const f32x4 *>(shp + c);
             if (rp) {
                 const f32x4 rv = *reinterpret_cast<const f32x4 *>(rp + c);
                 v = a.res_mode ? (v + rv) * sc + sh : v * sc + sh + rv;
@@ -174,7 +182,8 @@ extern "C" int m3d_anab_attend_f32(const float *q, int q_cs, const float *khat, 
                                    const float *shift, int act, float *out, int out_cs, m3d_stream_t stream)
 {
     M3D_REQUIRE(q && khat && vhatT && out, "anab_attend_f32: null pointer");
-    M3D_REQUIRE((Ck == 168 || Ck == 64 || Ck == 128) && Cv == AF_CV, "anab_attend_f32: built for Ck in {64, 128, 168}, Cv = %d (got %d, %d)", AF_CV, Ck, Cv);
+    M3D_REQUIRE((Ck == 168 || Ck == 64 || Ck == 128) && (Cv == AF_CV || Cv == 2 * AF_CV),
+                "anab_attend_f32: built for Ck in {64, 128, 168}, Cv in {%d, %d} (got %d, %d)", AF_CV, 2 * AF_CV, Ck, Cv);
     M3D_REQUIRE(B >= 1 && HW >= 128 && HW % 128 == 0, "anab_attend_f32: H*W must be a multiple of 128 (got %d)", HW);
     M3D_REQUIRE(keys >= 1 && keys <= keys_pad && keys_pad % 32 == 0, "anab_attend_f32: keys <= keys_pad, keys_pad %% 32 == 0");
     M3D_REQUIRE(q_cs % 4 == 0 && q_cs >= Ck && k_cs % 4 == 0 && k_cs >= Ck && out_cs % 4 == 0 && (!res || res_cs % 4 == 0),
@@ -186,6 +195,12 @@ extern "C" int m3d_anab_attend_f32(const float *q, int q_cs, const float *khat, 
     a.q = q; a.khat = khat; a.vhat = vhatT; a.res = res; a.scale = scale; a.shift = shift; a.out = out;
     a.q_cs = q_cs; a.k_cs = k_cs; a.HW = HW; a.Ck = Ck; a.keys = keys; a.keys_pad = keys_pad; a.res_cs = res_cs; a.out_cs = out_cs;
     a.res_mode = res_mode; a.act = act ? 1 : 0;
+    if (Cv == 2 * AF_CV) {                                     // two value-channel halves per pixel tile (see the top of the file)
+        M3D_REQUIRE(Ck == 168, "anab_attend_f32: Cv = %d is built for Ck = 168 (got %d)", 2 * AF_CV, Ck);
+        hipLaunchKernelGGL((anab_attend_f32_kernel<168, 2>), dim3(B * (HW / 128), 2), dim3(256), 0, (hipStream_t)stream, a);
+        M3D_LAUNCH_CHECK();
+        return M3D_OK;
+    }
     const dim3 grid(B * (HW / 128));
     if (Ck == 168) hipLaunchKernelGGL(anab_attend_f32_kernel<168>, grid, dim3(256), 0, (hipStream_t)stream, a);
     else if (Ck == 128) hipLaunchKernelGGL(anab_attend_f32_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, a);

@@ -60,7 +60,9 @@ struct MlpBatch {
     MlpArgs head[MLP_MAX_HEADS];                      // blockIdx.y selects the head (same M for all of them)
 };
 
-template <bool HAS_L1, int N3>
+// CIN: input channels of the staged tile -- 128 (DLA-34, three layers), 256 (two layers, or the three-layer heads of DLA-102, whose
+// first layer reads the 256-channel tile and overwrites it in place like the second does)
+template <bool HAS_L1, int N3, int CIN = HAS_L1 ? 128 : 256>
 __global__ __launch_bounds__(256) void head_mlp_kernel(const MlpBatch batch)
 {
     const MlpArgs &a = batch.head[blockIdx.y];
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(256) void head_mlp_kernel(const MlpBatch batch)
     // per MFMA slot (tools/head_probe.py HEAD_TRACE=1 showed 20-30k cycles for the old index arithmetic), so: one
     // per-thread offset, buffer loads that differ only in the SGPR offset (rows past M read 0.0f), immediate LDS offsets.
     {
-        constexpr int CIN = HAS_L1 ? 128 : 256;       // enforced by m3d_head_mlp_forward*
+        static_assert(CIN == 128 || CIN == 256, "head_mlp: staged Cin");   // == a.Cin, enforced by m3d_head_mlp_forward*
         constexpr int C4N = CIN / 4, RPP = 256 / C4N, NP = MLP_BM / RPP;
         const int row0 = tid / C4N, c4 = tid % C4N;
         const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.in, (unsigned)a.M * (unsigned)a.in_cs * 4u);
@@ -316,11 +318,11 @@ __global__ __launch_bounds__(256) void head_mlp_kernel(const MlpBatch batch)
     TRACE();
 }
 
-template <bool HAS_L1, int N3>
+template <bool HAS_L1, int N3, int CIN = HAS_L1 ? 128 : 256>
 static int launch_mlp(const MlpBatch &b, int n, hipStream_t stream)
 {
     constexpr size_t smem = (size_t)(MLP_BM * MLP_LDA) * sizeof(float);
-    auto kern = head_mlp_kernel<HAS_L1, N3>;
+    auto kern = head_mlp_kernel<HAS_L1, N3, CIN>;
     static bool attr_set = false;
     if (!attr_set) {
         M3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -336,8 +338,8 @@ static int fill_mlp_args(const m3d_mlp_desc *d, MlpArgs &a)
 {
     M3D_REQUIRE(d->in && d->w2 && d->w3 && d->out, "head_mlp: null pointer");
     M3D_REQUIRE(d->s2 && d->t2 && d->s3 && d->t3, "head_mlp: scale/shift of layers 2 and 3 are required");
-    M3D_REQUIRE((d->Cin == 128 && d->w1 && d->s1 && d->t1) || (d->Cin == 256 && !d->w1),
-                "head_mlp: Cin must be 128 (3 layers, w1 given) or 256 (2 layers, w1 NULL)");
+    M3D_REQUIRE(((d->Cin == 128 || d->Cin == 256) && d->w1 && d->s1 && d->t1) || (d->Cin == 256 && !d->w1),
+                "head_mlp: Cin must be 128 or 256 (3 layers, w1 given) or 256 (2 layers, w1 NULL)");
     M3D_REQUIRE(d->in_cs % 4 == 0 && d->in_cs >= d->Cin && ((uintptr_t)d->in & 15) == 0, "head_mlp: input alignment");
     M3D_REQUIRE(d->Cout >= 1 && d->Cout <= d->Cout_pad && (d->Cout_pad == 64 || d->Cout_pad == 256),
                 "head_mlp: Cout_pad must be 64 or 256 (got %d)", d->Cout_pad);
@@ -364,13 +366,18 @@ extern "C" int m3d_head_mlp_forward_batched(const m3d_mlp_desc *d, int n, m3d_st
     for (int i = 0; i < n; ++i) {
         const int rc = fill_mlp_args(d + i, b.head[i]);
         if (rc != M3D_OK) return rc;
-        M3D_REQUIRE(d[i].M == d[0].M && (d[i].w1 != nullptr) == (d[0].w1 != nullptr) && d[i].Cout_pad == d[0].Cout_pad,
-                    "head_mlp: heads of one launch must share M, depth and Cout_pad (head %d differs)", i);
+        M3D_REQUIRE(d[i].M == d[0].M && (d[i].w1 != nullptr) == (d[0].w1 != nullptr) && d[i].Cout_pad == d[0].Cout_pad &&
+                        d[i].Cin == d[0].Cin,
+                    "head_mlp: heads of one launch must share M, Cin, depth and Cout_pad (head %d differs)", i);
     }
     for (int i = n; i < MLP_MAX_HEADS; ++i) b.head[i] = b.head[0];
 #ifdef HEAD_TRACE
     b.trace = g_head_trace;
 #endif
+    if (d->w1 && d->Cin == 256) {
+        if (d->Cout_pad == 64) return launch_mlp<true, 64, 256>(b, n, stream);
+        return launch_mlp<true, 256, 256>(b, n, stream);
+    }
     if (d->w1) {
         if (d->Cout_pad == 64) return launch_mlp<true, 64>(b, n, stream);
         return launch_mlp<true, 256>(b, n, stream);

@@ -9,7 +9,8 @@ Design (MI355X-first):
     built once per input shape (``_Plan``) and replayed; PyTorch only owns device memory + streams.
 
 Reference graph being executed: model/M3d_inference_align.py:215-313 (RPN.forward),
-model/pose_dla_dcn.py:391-397,314-327,546-578,687-696 (DLA-34, Tree, IDAUp, DLAUp, DLASeg),
+model/pose_dla_dcn.py:391-397,314-327,546-578,687-696 (DLA-34, Tree, IDAUp, DLAUp, DLASeg), :162-200,261-269,435-441
+(DLA-102: Bottleneck, residual Root),
 model/DCNv2/dcn_v2.py:64-70 (DCN), model/module/feturealign_mgpu.py:48-99,153-208,
 model/module/attention.py:183-216.
 """
@@ -27,6 +28,9 @@ from .config import model_flags
 BN_EPS = 1e-5
 SELECT_KEYS = os.environ.get("M3D_SELECT_KEYS", "1") != "0"     # anchor_select also writes the detection stage's sort keys
 PSP_SIZES = (1, 4, 8, 16)
+# channels of the stem, level0 .. level5 (pose_dla_dcn.py:419-440); channels[3] is the width of feats0 and every map after it
+BACKBONE_CHANNELS = {"dla34": (16, 32, 64, 128, 256, 512), "dla102": (16, 32, 128, 256, 512, 1024)}
+DLA102_LEVELS = (1, 1, 1, 3, 4, 1)
 
 
 def _rup(a, b):
@@ -216,6 +220,11 @@ class Engine:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.conf = conf
+        self.back_bone = str(conf.back_bone) if "back_bone" in conf else "dla34"
+        if self.back_bone not in BACKBONE_CHANNELS:
+            raise NotImplementedError("back_bone %r: the engine runs %s" % (self.back_bone, " / ".join(BACKBONE_CHANNELS)))
+        if getattr(self, "compute_dtype", "f32") == "bf16" and self.back_bone != "dla34":
+            raise NotImplementedError("the bf16 engine runs the dla34 backbone only; run back_bone %r in fp32" % self.back_bone)
         sd = {k[7:] if k.startswith("module.") else k: v for k, v in state_dict.items()}
         self.sd = sd
         self.A = int(np.asarray(conf.anchors).shape[0]) if not backbone_only else 0
@@ -267,11 +276,32 @@ class Engine:
             if (p + ".project.0.weight") in sd:
                 P[p + ".project"] = self._pc(p + ".project.0", p + ".project.1")
 
-        tree1(b + ".level2")
-        for lv in (3, 4):
-            tree1("%s.level%d.tree1" % (b, lv))
-            tree1("%s.level%d.tree2" % (b, lv))
-        tree1(b + ".level5")
+        def bottleneck(p):
+            for i in (1, 2, 3):
+                P["%s.conv%d" % (p, i)] = self._pc("%s.conv%d" % (p, i), "%s.bn%d" % (p, i))
+
+        def tree(p, levels):
+            """Any Tree of Bottlenecks (DLA-102): leaves carry the blocks, the root and the project.  The project of a Tree of
+            depth > 1 is computed by the reference and then ignored (its tree1 computes its own): not packed."""
+            if levels == 1:
+                bottleneck(p + ".tree1")
+                bottleneck(p + ".tree2")
+                P[p + ".root"] = self._pc(p + ".root.conv", p + ".root.bn")
+                if (p + ".project.0.weight") in sd:
+                    P[p + ".project"] = self._pc(p + ".project.0", p + ".project.1")
+            else:
+                tree(p + ".tree1", levels - 1)
+                tree(p + ".tree2", levels - 1)
+
+        if self.back_bone == "dla102":
+            for lv in (2, 3, 4, 5):
+                tree("%s.level%d" % (b, lv), DLA102_LEVELS[lv])
+        else:
+            tree1(b + ".level2")
+            for lv in (3, 4):
+                tree1("%s.level%d.tree1" % (b, lv))
+                tree1("%s.level%d.tree2" % (b, lv))
+            tree1(b + ".level5")
 
         def deform(p):
             P[p + ".om"] = self._pc(p + ".conv.conv_offset_mask")
@@ -508,7 +538,7 @@ class Engine:
     def _build_plan(self, B, H, W):
         L, P = self.L, self.P
         plan = _Plan()
-        chs = [16, 32, 64, 128, 256, 512]
+        chs = BACKBONE_CHANNELS[self.back_bone]
         b = "base.base"
         in_ptr = [0]                      # set by forward(): the caller's NCHW tensor is read in place
         plan.named["input_ptr"] = in_ptr
@@ -548,66 +578,69 @@ class Engine:
             self._op(plan, name, "maxpool", lambda st: _hip.check(L.m3d_maxpool2x2(
                 x.ptr, x.cs, out.ptr, out.cs, x.n, x.h, x.w, x.c, st)), nbytes=x.n * x.h * x.w * x.c * 5)
 
-        def block(p, x, res, out, stride):
-            co = P[p + ".conv1"].cout
-            t = self._buf(plan, B, out.h, out.w, co)
-            self._conv(plan, p + ".conv1", P[p + ".conv1"], x, t, stride, 1, act=1)
-            self._conv(plan, p + ".conv2", P[p + ".conv2"], t, out, 1, 1, act=1, res=res)
+        if self.back_bone == "dla102":
+            l3, l4, l5 = self._dla102_levels(plan, l1, maxpool)
+        else:
+            def block(p, x, res, out, stride):
+                co = P[p + ".conv1"].cout
+                t = self._buf(plan, B, out.h, out.w, co)
+                self._conv(plan, p + ".conv1", P[p + ".conv1"], x, t, stride, 1, act=1)
+                self._conv(plan, p + ".conv2", P[p + ".conv2"], t, out, 1, 1, act=1, res=res)
 
-        def tree1(p, x, co, stride, out, bottom=None):
-            """Tree(levels=1, level_root=False): pose_dla_dcn.py:314-323; root input = (x2, x1)."""
-            h, w = x.h // stride, x.w // stride
-            cat = self._buf(plan, B, h, w, 2 * co)
-            x2v, x1v = cat.slice(0, co), cat.slice(co, co)
-            if stride == 1:
-                bottom = x
-            elif bottom is None:
-                bottom = self._buf(plan, B, h, w, x.c)
+            def tree1(p, x, co, stride, out, bottom=None):
+                """Tree(levels=1, level_root=False): pose_dla_dcn.py:314-323; root input = (x2, x1)."""
+                h, w = x.h // stride, x.w // stride
+                cat = self._buf(plan, B, h, w, 2 * co)
+                x2v, x1v = cat.slice(0, co), cat.slice(co, co)
+                if stride == 1:
+                    bottom = x
+                elif bottom is None:
+                    bottom = self._buf(plan, B, h, w, x.c)
+                    maxpool(p + ".downsample", x, bottom)
+                if (p + ".project") in P:
+                    res = self._buf(plan, B, h, w, co)
+                    self._conv(plan, p + ".project", P[p + ".project"], bottom, res, 1, 0, act=0)
+                else:
+                    res = bottom
+                block(p + ".tree1", x, res, x1v, stride)
+                block(p + ".tree2", x1v, x1v, x2v, 1)
+                self._conv(plan, p + ".root", P[p + ".root"], cat, out, 1, 0, act=1)
+
+            # level2: Tree(1, 32 -> 64, stride 2)
+            l2 = self._buf(plan, B, H // 4, W // 4, 64, name="level2")
+            tree1(b + ".level2", l1, 64, 2, l2)
+
+            def tree2(p, x, co, out):
+                """Tree(levels=2, level_root=True): pose_dla_dcn.py:314-327."""
+                ci = x.c
+                h, w = x.h // 2, x.w // 2
+                # tree2's root input: (x2'', x1'', bottom, X1)
+                catb = self._buf(plan, B, h, w, 2 * co + ci + co)
+                bottom = catb.slice(2 * co, ci)
+                X1 = catb.slice(2 * co + ci, co)
                 maxpool(p + ".downsample", x, bottom)
-            if (p + ".project") in P:
-                res = self._buf(plan, B, h, w, co)
-                self._conv(plan, p + ".project", P[p + ".project"], bottom, res, 1, 0, act=0)
-            else:
-                res = bottom
-            block(p + ".tree1", x, res, x1v, stride)
-            block(p + ".tree2", x1v, x1v, x2v, 1)
-            self._conv(plan, p + ".root", P[p + ".root"], cat, out, 1, 0, act=1)
+                tree1(p + ".tree1", x, co, 2, X1, bottom=bottom)
+                # tree2 = Tree(1, co -> co, stride 1) writing x2'', x1'' into catb[0:2co]
+                x2v, x1v = catb.slice(0, co), catb.slice(co, co)
+                block(p + ".tree2.tree1", X1, X1, x1v, 1)
+                block(p + ".tree2.tree2", x1v, x1v, x2v, 1)
+                self._conv(plan, p + ".tree2.root", P[p + ".tree2.root"], catb, out, 1, 0, act=1)
 
-        # level2: Tree(1, 32 -> 64, stride 2)
-        l2 = self._buf(plan, B, H // 4, W // 4, 64, name="level2")
-        tree1(b + ".level2", l1, 64, 2, l2)
-
-        def tree2(p, x, co, out):
-            """Tree(levels=2, level_root=True): pose_dla_dcn.py:314-327."""
-            ci = x.c
-            h, w = x.h // 2, x.w // 2
-            # tree2's root input: (x2'', x1'', bottom, X1)
-            catb = self._buf(plan, B, h, w, 2 * co + ci + co)
-            bottom = catb.slice(2 * co, ci)
-            X1 = catb.slice(2 * co + ci, co)
-            maxpool(p + ".downsample", x, bottom)
-            tree1(p + ".tree1", x, co, 2, X1, bottom=bottom)
-            # tree2 = Tree(1, co -> co, stride 1) writing x2'', x1'' into catb[0:2co]
-            x2v, x1v = catb.slice(0, co), catb.slice(co, co)
-            block(p + ".tree2.tree1", X1, X1, x1v, 1)
-            block(p + ".tree2.tree2", x1v, x1v, x2v, 1)
-            self._conv(plan, p + ".tree2.root", P[p + ".tree2.root"], catb, out, 1, 0, act=1)
-
-        l3 = self._buf(plan, B, H // 8, W // 8, 128, name="level3")
-        tree2(b + ".level3", l2, 128, l3)
-        l4 = self._buf(plan, B, H // 16, W // 16, 256, name="level4")
-        tree2(b + ".level4", l3, 256, l4)
-        # level5: Tree(1, 256 -> 512, stride 2, level_root): root input (x2, x1, bottom)
-        l5 = self._buf(plan, B, H // 32, W // 32, 512, name="level5")
-        h5, w5 = H // 32, W // 32
-        cat5 = self._buf(plan, B, h5, w5, 1024 + 256)
-        bottom5 = cat5.slice(1024, 256)
-        maxpool(b + ".level5.downsample", l4, bottom5)
-        res5 = self._buf(plan, B, h5, w5, 512)
-        self._conv(plan, b + ".level5.project", P[b + ".level5.project"], bottom5, res5, 1, 0, act=0)
-        block(b + ".level5.tree1", l4, res5, cat5.slice(512, 512), 2)
-        block(b + ".level5.tree2", cat5.slice(512, 512), cat5.slice(512, 512), cat5.slice(0, 512), 1)
-        self._conv(plan, b + ".level5.root", P[b + ".level5.root"], cat5, l5, 1, 0, act=1)
+            l3 = self._buf(plan, B, H // 8, W // 8, 128, name="level3")
+            tree2(b + ".level3", l2, 128, l3)
+            l4 = self._buf(plan, B, H // 16, W // 16, 256, name="level4")
+            tree2(b + ".level4", l3, 256, l4)
+            # level5: Tree(1, 256 -> 512, stride 2, level_root): root input (x2, x1, bottom)
+            l5 = self._buf(plan, B, H // 32, W // 32, 512, name="level5")
+            h5, w5 = H // 32, W // 32
+            cat5 = self._buf(plan, B, h5, w5, 1024 + 256)
+            bottom5 = cat5.slice(1024, 256)
+            maxpool(b + ".level5.downsample", l4, bottom5)
+            res5 = self._buf(plan, B, h5, w5, 512)
+            self._conv(plan, b + ".level5.project", P[b + ".level5.project"], bottom5, res5, 1, 0, act=0)
+            block(b + ".level5.tree1", l4, res5, cat5.slice(512, 512), 2)
+            block(b + ".level5.tree2", cat5.slice(512, 512), cat5.slice(512, 512), cat5.slice(0, 512), 1)
+            self._conv(plan, b + ".level5.root", P[b + ".level5.root"], cat5, l5, 1, 0, act=1)
 
         # ---- DLAUp / IDAUp ------------------------------------------------------------
         def deform(p, x, out):
@@ -628,10 +661,11 @@ class Engine:
             deform("%s.node_%d" % (p, i), summed, node)
             return node
 
-        L5a = ida_step("base.dla_up.ida_0", 1, l5, l4, 256)            # 256 @ H/16
-        L4b = ida_step("base.dla_up.ida_1", 1, l4, l3, 128)            # 128 @ H/8
-        L5b = ida_step("base.dla_up.ida_1", 2, L5a, L4b, 128)          # 128 @ H/8
-        feats0 = ida_step("base.ida_up", 1, L5a, L5b, 128)             # 128 @ H/8
+        c3, c4 = chs[3], chs[4]                                        # DLA-34: 128 / 256, DLA-102: 256 / 512
+        L5a = ida_step("base.dla_up.ida_0", 1, l5, l4, c4)             # c4 @ H/16
+        L4b = ida_step("base.dla_up.ida_1", 1, l4, l3, c3)             # c3 @ H/8
+        L5b = ida_step("base.dla_up.ida_1", 2, L5a, L4b, c3)           # c3 @ H/8
+        feats0 = ida_step("base.ida_up", 1, L5a, L5b, c3)              # c3 @ H/8
         plan.named["feats0"] = feats0
 
         plan.feat = (feats0.h, feats0.w)
@@ -724,7 +758,7 @@ class Engine:
             self._op(plan, "shape_align.offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
                 0, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, P["shape.table"].data_ptr(), None, None, None, 0.0, 1.0, 0.0,
                 1.0, om_sa.ptr, om_sa.cs, B, A, HW, 9, 0, st)), nbytes=B * HW * (2 + 28) * 4)
-            feats = self._buf(plan, B, fh, fw, 128, name="feats")
+            feats = self._buf(plan, B, fh, fw, c3, name="feats")
             self._conv(plan, "shape_align.dcn", P["shape_align"], feats0, feats, 1, 1, act=0, res=feats0, om=om_sa)
         else:
             feats = plan.named["feats"] = feats0
@@ -744,9 +778,9 @@ class Engine:
         if with_center:
             heads([("bbox_x", feats, box_planar(0)), ("bbox_y", feats, box_planar(1)),
                    ("bbox_x3d", feats, box_planar(4)), ("bbox_y3d", feats, box_planar(5))])
-            f2d = self._buf(plan, B, fh, fw, 128, name="feats_align2d")
+            f2d = self._buf(plan, B, fh, fw, c3, name="feats_align2d")
             center_align("center_align2d", feats, 0, 1, 0, f2d)
-            f3d = self._buf(plan, B, fh, fw, 128, name="feats_align3d")
+            f3d = self._buf(plan, B, fh, fw, c3, name="feats_align3d")
             center_align("center_align3d", feats, 4, 5, 4, f3d)
             heads([("bbox_w", f2d, box_planar(2)), ("bbox_h", f2d, box_planar(3))] +
                   [(h, f3d, box_planar(self.box_heads.index(h))) for h in z3d_now + ["bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d"]])
@@ -756,7 +790,7 @@ class Engine:
 
         # ---- ANAB ---------------------------------------------------------------------
         if with_anab:
-            gl = self._buf(plan, B, fh, fw, 128, name="feats_gl")
+            gl = self._buf(plan, B, fh, fw, c3, name="feats_gl")
             self._anab_ops(plan, f3d, gl, P["anab.bn.scale"], P["anab.bn.shift"], act=1, res_mode=1)
             head("bbox_z3d", gl, box_planar(6))
         else:
@@ -780,6 +814,78 @@ class Engine:
         return plan
 
 
+    def _dla102_levels(self, plan, l1, maxpool):
+        """level2 .. level5 of DLA-102 (pose_dla_dcn.py:162-200,261-327): Trees of Bottlenecks of depth 1, 3, 4, 1 with residual
+        roots.  The walk follows Tree.forward for any depth: a Tree of depth > 1 hands its `children` (the downsampled input when it
+        is a level root, then the output of every tree1 on the way down) to its tree2, and the leaf at the end of the tree2 chain
+        concatenates (x2, x1, *children) for its root.  That concatenation is one buffer, allocated by the outermost Tree of the
+        chain; every child is written straight into its slice of it."""
+        P = self.P
+        B = l1.n
+        b = "base.base"
+        chs = BACKBONE_CHANNELS["dla102"]
+
+        def bottleneck(p, x, res, out, stride):
+            """1x1 (at the input resolution) -> 3x3 (stride) -> 1x1 + residual, each with BN + LeakyReLU."""
+            cb = P[p + ".conv1"].cout
+            t1 = self._buf(plan, B, x.h, x.w, cb)
+            self._conv(plan, p + ".conv1", P[p + ".conv1"], x, t1, 1, 0, act=1)
+            t2 = self._buf(plan, B, out.h, out.w, cb)
+            self._conv(plan, p + ".conv2", P[p + ".conv2"], t1, t2, stride, 1, act=1)
+            self._conv(plan, p + ".conv3", P[p + ".conv3"], t2, out, 1, 0, act=1, res=res)
+
+        def tree(p, levels, x, co, stride, out, level_root=False, root_dim=0, cat=None, pos=None, bottom=None):
+            """Tree.forward writing its result into `out`.  cat / pos: the root concatenation this Tree ends in and the list
+            holding its next free channel (None: this Tree starts a chain and allocates it); bottom: the downsampled input,
+            when an enclosing Tree has already computed it (tree1 pools the same input as its parent)."""
+            ci = x.c
+            if root_dim == 0:
+                root_dim = 2 * co
+            if level_root:
+                root_dim += ci
+            h, w = x.h // stride, x.w // stride
+            if cat is None:
+                # width of the leaf root at the end of the tree2 chain: each level down adds one child of width co
+                cat = self._buf(plan, B, h, w, root_dim + co * (levels - 1))
+                pos = [2 * co]
+            if stride == 1:
+                bottom = x
+            elif bottom is None:
+                if level_root:                                       # children.append(bottom): pooled into its slice
+                    bottom = cat.slice(pos[0], ci)
+                    pos[0] += ci
+                else:
+                    bottom = self._buf(plan, B, h, w, ci)
+                maxpool(p + ".downsample", x, bottom)
+            if levels == 1:
+                if (p + ".project") in P:
+                    res = self._buf(plan, B, h, w, co)
+                    self._conv(plan, p + ".project", P[p + ".project"], bottom, res, 1, 0, act=0)
+                else:
+                    res = bottom
+                assert cat.c == root_dim, (p, cat.c, root_dim)
+                x2v, x1v = cat.slice(0, co), cat.slice(co, co)
+                bottleneck(p + ".tree1", x, res, x1v, stride)
+                bottleneck(p + ".tree2", x1v, x1v, x2v, 1)
+                # Root with residual: BN(conv(cat)) + children[0] (= x2), LeakyReLU
+                self._conv(plan, p + ".root", P[p + ".root"], cat, out, 1, 0, act=1, res=x2v)
+                return
+            # (the project of a Tree of depth > 1 is computed by the reference and then ignored: its tree1 computes its own)
+            x1 = cat.slice(pos[0], co)                                # children.append(x1) after tree1
+            pos[0] += co
+            tree(p + ".tree1", levels - 1, x, co, stride, x1, bottom=bottom if stride > 1 else None)
+            tree(p + ".tree2", levels - 1, x1, co, 1, out, root_dim=root_dim + co, cat=cat, pos=pos)
+
+        outs = []
+        x = l1
+        for lv in (2, 3, 4, 5):
+            h, w = x.h // 2, x.w // 2
+            out = self._buf(plan, B, h, w, chs[lv], name="level%d" % lv)
+            tree("%s.level%d" % (b, lv), DLA102_LEVELS[lv], x, chs[lv], 2, out, level_root=lv > 2)
+            outs.append(out)
+            x = out
+        return outs[1], outs[2], outs[3]
+
     def _anab_ops(self, plan, x, out, scale, shift, act, res_mode):
         """Append the ANAB launches: fused QKVS 1x1 conv -> weighted pyramid pooling -> logits GEMM (per-image
         pooled keys as weights) -> row softmax -> P.V GEMM with the residual (+ optional BN/LeakyReLU) epilogue."""
@@ -793,7 +899,8 @@ class Engine:
         n_bins, max_slots = len(bin_scale), int(bin_slots.max())
         # the two per-image GEMMs go to the wave-granular kernel when they yield enough waves; their weights (pooled keys /
         # values) are then written in MFMA-fragment order by the pooling finish and the key count is padded to 128
-        fused = FUSED_ANAB and self.cv == 128 and self.ck in (64, 128, 168) and HW % 128 == 0
+        fused = FUSED_ANAB and ((self.cv == 128 and self.ck in (64, 128, 168)) or (self.cv == 256 and self.ck == 168)) \
+            and HW % 128 == 0
         wave_ok = (not fused) and USE_ANAB_WAVE and USE_CONV_WAVE and HW % 32 == 0 and self.ck_pad % 32 == 0 and self.cv % 128 == 0
         nw = B * HW // 32
         wave_logits = wave_ok and nw * (_rup(n_bins, 128) // 128) >= 900
@@ -947,7 +1054,7 @@ class Engine:
             plan.named["input_u8"][0] = 0
 
     def forward_backbone(self, x):
-        """Backbone + DCN up-sampling only (DLASeg.forward): returns the NHWC View of the 128-channel map."""
+        """Backbone + DCN up-sampling only (DLASeg.forward): returns the NHWC View of the 128-channel (DLA-102: 256) map."""
         B, _, H, W = x.shape
         plan = self.plan_for(B, H, W)
         x = x.contiguous()

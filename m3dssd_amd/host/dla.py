@@ -1,11 +1,12 @@
-"""DLA-34 backbone + DCN up-sampling modules with the reference's interface and state_dict keys
-(model/pose_dla_dcn.py: BasicBlock :93-121, Root :251-269, Tree :272-327, DLA :330-397,
-dla34 :419-425, DeformConv :471-485, IDAUp :519-552, DLAUp :556-578, DLASeg :641-696).
+"""DLA-34 / DLA-102 backbones + DCN up-sampling modules with the reference's interface and state_dict keys
+(model/pose_dla_dcn.py: BasicBlock :93-121, Bottleneck :162-200, Root :251-269, Tree :272-327, DLA :330-397,
+dla34 :419-425, dla102 :435-441, DeformConv :471-485, IDAUp :519-552, DLAUp :556-578, DLASeg :641-696).
 
 The modules are parameter containers; the arithmetic runs in the HIP engine
 (m3dssd_amd/engine.py) -- ``DLASeg.forward`` executes the backbone part of the engine plan,
 ``DeformConv.forward`` the fused offset-conv + DCN + BN + LeakyReLU launches."""
 import math
+import warnings
 
 import numpy as np
 import torch
@@ -24,6 +25,22 @@ class BasicBlock(nn.Module):
         self.relu = nn.LeakyReLU(inplace=True)
         self.conv2 = nn.Conv2d(planes, planes, 3, stride=1, padding=1, bias=True, dilation=dilation)
         self.bn2 = nn.BatchNorm2d(planes, momentum=BN_MOMENTUM)
+        self.stride = stride
+
+
+class Bottleneck(nn.Module):
+    expansion = 2
+
+    def __init__(self, inplanes, planes, stride=1, dilation=1):
+        super().__init__()
+        bottle_planes = planes // Bottleneck.expansion
+        self.conv1 = nn.Conv2d(inplanes, bottle_planes, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(bottle_planes, momentum=BN_MOMENTUM)
+        self.conv2 = nn.Conv2d(bottle_planes, bottle_planes, 3, stride=stride, padding=dilation, bias=False, dilation=dilation)
+        self.bn2 = nn.BatchNorm2d(bottle_planes, momentum=BN_MOMENTUM)
+        self.conv3 = nn.Conv2d(bottle_planes, planes, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes, momentum=BN_MOMENTUM)
+        self.relu = nn.LeakyReLU(inplace=True)
         self.stride = stride
 
 
@@ -91,6 +108,20 @@ def dla34(pretrained=False, **kwargs):
     return DLA([1, 1, 1, 2, 2, 1], [16, 32, 64, 128, 256, 512], block=BasicBlock, **kwargs)
 
 
+def dla102(pretrained=None, **kwargs):
+    # The shipped configurations (scripts/config/kitti_3d_*.py) set pre_train = True next to back_bone = 'dla102', and the conf
+    # the reference pickles at training time carries it: at test time the reference then loads the trained checkpoint over every
+    # backbone tensor.  So a truthy `pretrained` builds the module with its own initialisation and warns; the ImageNet weights
+    # (dla102-d94d9790.pth, pose_dla_dcn.py:435-441) are never downloaded -- load them with load_state_dict if they are wanted.
+    if pretrained:
+        warnings.warn("dla102(pretrained=%r): ImageNet weights are not downloaded; the backbone keeps its initialisation until "
+                      "a checkpoint is loaded with load_state_dict" % (pretrained,), stacklevel=2)
+    return DLA([1, 1, 1, 3, 4, 1], [16, 32, 128, 256, 512, 1024], block=Bottleneck, residual_root=True, **kwargs)
+
+
+BACKBONES = {"dla34": dla34, "dla102": dla102}
+
+
 def fill_up_weights(up):
     w = up.weight.data
     f = math.ceil(w.size(2) / 2)
@@ -145,13 +176,13 @@ class DLASeg(nn.Module):
     def __init__(self, base_name, pretrained, down_ratio, final_kernel, last_level, head_conv, conf, out_channel=0):
         super().__init__()
         assert down_ratio in [2, 4, 8, 16]
-        if base_name != "dla34":
-            raise NotImplementedError("back_bone %r: this build accelerates the dla34 path only" % base_name)
+        if base_name not in BACKBONES:
+            raise NotImplementedError("back_bone %r: this build accelerates %s only" % (base_name, " / ".join(BACKBONES)))
         if down_ratio != 8 or last_level != 5:
             raise NotImplementedError("the HIP engine is laid out for feat_stride 8 / last_level 5")
         self.first_level = int(np.log2(down_ratio))
         self.last_level = last_level
-        self.base = dla34(pretrained=pretrained)
+        self.base = BACKBONES[base_name](pretrained=pretrained)
         channels = self.base.channels
         scales = [2 ** i for i in range(len(channels[self.first_level:]))]
         self.dla_up = DLAUp(self.first_level, channels[self.first_level:], scales, conf=conf)

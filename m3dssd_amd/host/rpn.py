@@ -26,6 +26,12 @@ def _head(cin, mid, cout, k0):
                          nn.Conv2d(mid, cout, 1))
 
 
+def _check_dtype(back_bone, compute_dtype):
+    if compute_dtype == "bf16" and back_bone != "dla34":
+        raise NotImplementedError("compute_dtype 'bf16' runs the dla34 backbone only; back_bone %r runs in fp32 "
+                                  "(compute_dtype 'f32')" % (back_bone,))
+
+
 def _invalidate_after_load(module, incompatible_keys):
     module.refresh_engine()
 
@@ -85,6 +91,7 @@ class RPN(nn.Module):
         self.register_load_state_dict_post_hook(_invalidate_after_load)
         self.compute_dtype = str(conf.compute_dtype) if "compute_dtype" in conf else "f32"
         self.reuse_outputs = bool(conf.reuse_outputs) if "reuse_outputs" in conf else False
+        _check_dtype(self.back_bone, self.compute_dtype)
 
     # -- engine management: parameters are folded / packed once and re-packed when they change --------------------------------
     # Everything that replaces or moves parameters through the nn.Module API marks the packed engine stale:
@@ -168,6 +175,7 @@ class RPN(nn.Module):
     def set_compute_dtype(self, dtype):
         """'f32' (default: the reference's arithmetic) or 'bf16' (bf16 storage / MFMA, fp32 accumulation; see engine_bf16.py)."""
         if str(dtype) != self.compute_dtype:
+            _check_dtype(self.back_bone, str(dtype))
             self.compute_dtype = str(dtype)
             self._engine = None
         return self

@@ -6,7 +6,7 @@ parity tests all use a deterministic synthetic recipe (numpy PCG64, one stream p
 tensor keyed by crc32 of its state_dict name, so values do not depend on order):
 
 * ``param_spec`` lists every state_dict entry of ``RPN(dla34)`` -- 542 tensors (fullalign;
-  526 for base, 535 for anab), the
+  526 for base, 535 for anab; ``back_bone="dla102"``: 944 / 928 / 937), the
   contract in SURVEY.md 8b; tools/gen_golden.py asserts it equals the reference
   model's own ``state_dict()`` keys and shapes.
 * conv_offset_mask is re-randomised (the reference zero-inits it,
@@ -54,19 +54,30 @@ def _block(spec, p, ci, co):
     _bn(spec, p + ".bn2", co)
 
 
-def _tree(spec, p, levels, ci, co, level_root, root_dim=0):
+def _bottleneck(spec, p, ci, co):
+    """Bottleneck (pose_dla_dcn.py:162-200, expansion 2): 1x1 ci -> co/2, 3x3, 1x1 co/2 -> co, no biases."""
+    cb = co // 2
+    _conv(spec, p + ".conv1", cb, ci, 1, False)
+    _bn(spec, p + ".bn1", cb)
+    _conv(spec, p + ".conv2", cb, cb, 3, False)
+    _bn(spec, p + ".bn2", cb)
+    _conv(spec, p + ".conv3", co, cb, 1, False)
+    _bn(spec, p + ".bn3", co)
+
+
+def _tree(spec, p, levels, ci, co, level_root, root_dim=0, block=_block):
     if root_dim == 0:
         root_dim = 2 * co
     if level_root:
         root_dim += ci
     if levels == 1:
-        _block(spec, p + ".tree1", ci, co)
-        _block(spec, p + ".tree2", co, co)
+        block(spec, p + ".tree1", ci, co)
+        block(spec, p + ".tree2", co, co)
         _conv(spec, p + ".root.conv", co, root_dim, 1, False)
         _bn(spec, p + ".root.bn", co)
     else:
-        _tree(spec, p + ".tree1", levels - 1, ci, co, False, 0)
-        _tree(spec, p + ".tree2", levels - 1, co, co, False, root_dim + co)
+        _tree(spec, p + ".tree1", levels - 1, ci, co, False, 0, block)
+        _tree(spec, p + ".tree2", levels - 1, co, co, False, root_dim + co, block)
     if ci != co:
         _conv(spec, p + ".project.0", co, ci, 1, False)
         _bn(spec, p + ".project.1", co)
@@ -95,12 +106,28 @@ def _head(spec, p, ci, co, k0):
     _conv(spec, p + ".6", co, 256, 1, True)
 
 
-def param_spec(num_anchors=36, num_classes=4, shape_align=True, center_align=True, attention="ANAB"):
+# per backbone (pose_dla_dcn.py:419-440): level depths, channels, block, residual root
+BACKBONES = {
+    "dla34": dict(levels=(1, 1, 1, 2, 2, 1), channels=(16, 32, 64, 128, 256, 512), block="basic", residual_root=False),
+    "dla102": dict(levels=(1, 1, 1, 3, 4, 1), channels=(16, 32, 128, 256, 512, 1024), block="bottleneck", residual_root=True),
+}
+
+
+def backbone(name):
+    if name not in BACKBONES:
+        raise NotImplementedError("back_bone %r: this build runs %s" % (name, " / ".join(BACKBONES)))
+    return BACKBONES[name]
+
+
+def param_spec(num_anchors=36, num_classes=4, shape_align=True, center_align=True, attention="ANAB", back_bone="dla34"):
     """OrderedDict name -> shape, in the reference's registration order.  The flags drop the sub-modules the reference does not
     create (M3d_inference_align.py:138-168): the align modules when their flag is off, bbox_z3d_gl unless attention == "ANAB";
-    the defaults give the fullalign model."""
+    the defaults give the fullalign model.  ``back_bone="dla102"``: Bottleneck trees of depth [1, 1, 1, 3, 4, 1] and channels
+    [16, 32, 128, 256, 512, 1024], so every map from DLAUp on (heads, alignment, ANAB) is 256 channels wide instead of 128."""
     s = OrderedDict()
-    ch = [16, 32, 64, 128, 256, 512]
+    bb = backbone(back_bone)
+    ch, lv = list(bb["channels"]), bb["levels"]
+    blk = _bottleneck if bb["block"] == "bottleneck" else _block
     b = "base.base"
     _conv(s, b + ".base_layer.0", ch[0], 3, 7, False)
     _bn(s, b + ".base_layer.1", ch[0])
@@ -108,33 +135,33 @@ def param_spec(num_anchors=36, num_classes=4, shape_align=True, center_align=Tru
     _bn(s, b + ".level0.1", ch[0])
     _conv(s, b + ".level1.0", ch[1], ch[0], 3, False)
     _bn(s, b + ".level1.1", ch[1])
-    _tree(s, b + ".level2", 1, ch[1], ch[2], False)
-    _tree(s, b + ".level3", 2, ch[2], ch[3], True)
-    _tree(s, b + ".level4", 2, ch[3], ch[4], True)
-    _tree(s, b + ".level5", 1, ch[4], ch[5], True)
-    _ida(s, "base.dla_up.ida_0", 256, [256, 512])
-    _ida(s, "base.dla_up.ida_1", 128, [128, 256, 256])
-    _ida(s, "base.ida_up", 128, [128, 256])
-    _head(s, "cls", 128, num_anchors * num_classes, 3)
+    for i in range(2, 6):
+        _tree(s, "%s.level%d" % (b, i), lv[i], ch[i - 1], ch[i], i > 2, block=blk)
+    c3, c4, c5 = ch[3], ch[4], ch[5]
+    _ida(s, "base.dla_up.ida_0", c4, [c4, c5])
+    _ida(s, "base.dla_up.ida_1", c3, [c3, c4, c4])
+    _ida(s, "base.ida_up", c3, [c3, c4])
+    c = c3                                                     # base_channels: the width of feats0 and every map after it
+    _head(s, "cls", c, num_anchors * num_classes, 3)
     for h in HEADS[1:]:
-        _head(s, h, 128, num_anchors, 1)
+        _head(s, h, c, num_anchors, 1)
     if center_align:
         for p in ("center_align2d", "center_align3d"):
-            s[p + ".align.weight"] = (128, 128, 1, 1)
-            s[p + ".align.bias"] = (128,)
+            s[p + ".align.weight"] = (c, c, 1, 1)
+            s[p + ".align.bias"] = (c,)
     if shape_align:
-        s["shape_align.align.weight"] = (128, 128, 3, 3)
-        s["shape_align.align.bias"] = (128,)
-        s["shape_align.proj.weight"] = (128, 256, 1, 1)
-    _head(s, "bbox_z3d", 128, num_anchors, 1)
+        s["shape_align.align.weight"] = (c, c, 3, 3)
+        s["shape_align.align.bias"] = (c,)
+        s["shape_align.proj.weight"] = (c, 2 * c, 1, 1)
+    _head(s, "bbox_z3d", c, num_anchors, 1)
     if attention == "ANAB":
-        s["bbox_z3d_gl.0.value_conv.weight"] = (128, 128, 1, 1)
-        s["bbox_z3d_gl.0.spatial_conv.weight"] = (4, 128, 1, 1)
-        s["bbox_z3d_gl.0.key_conv.weight"] = (168, 128, 1, 1)
-        s["bbox_z3d_gl.0.query_conv.weight"] = (168, 128, 1, 1)
-        _bn(s, "bbox_z3d_gl.1", 128)
+        s["bbox_z3d_gl.0.value_conv.weight"] = (c, c, 1, 1)
+        s["bbox_z3d_gl.0.spatial_conv.weight"] = (4, c, 1, 1)
+        s["bbox_z3d_gl.0.key_conv.weight"] = (168, c, 1, 1)
+        s["bbox_z3d_gl.0.query_conv.weight"] = (168, c, 1, 1)
+        _bn(s, "bbox_z3d_gl.1", c)
     for h in HEADS_TAIL2:
-        _head(s, h, 128, num_anchors, 1)
+        _head(s, h, c, num_anchors, 1)
     return s
 
 
@@ -153,16 +180,33 @@ def _bilinear_up(shape):
     return w
 
 
+# DLA-102 only: the residual roots add every tree's x2 once more and the Bottleneck's last 1x1 sums over half the channels, so
+# with the DLA-34 recipe the backbone maps grow level by level.  These gains on the backbone's root convs and the Bottleneck
+# output convs keep max |level5| and max |feats0| at the DLA-34 network's magnitude (tests/test_dla102_host.py checks it).
+DLA102_ROOT_GAIN = 0.2
+DLA102_CONV3_GAIN = 0.2
+
+
+def _dla102_gain(name):
+    if ".root.conv." in name:
+        return DLA102_ROOT_GAIN
+    if name.endswith(".conv3.weight"):
+        return DLA102_CONV3_GAIN
+    return 1.0
+
+
 def config_flags(name):
     """The flag keywords of param_spec / synth_state_dict / synth_conf for a shipped configuration
     ("base", "anab", "anab_fullalign")."""
     return dict(CONFIG_FLAGS[name])
 
 
-def synth_state_dict(seed=0, num_anchors=36, num_classes=4, shape_align=True, center_align=True, attention="ANAB"):
+def synth_state_dict(seed=0, num_anchors=36, num_classes=4, shape_align=True, center_align=True, attention="ANAB",
+                     back_bone="dla34"):
     """Every tensor is drawn from its own stream keyed by its name: a configuration without some sub-modules gets the same
     values for the keys it shares with the fullalign dict."""
-    spec = param_spec(num_anchors, num_classes, shape_align, center_align, attention)
+    spec = param_spec(num_anchors, num_classes, shape_align, center_align, attention, back_bone)
+    deep = back_bone == "dla102"
     sd = OrderedDict()
     for name, shape in spec.items():
         g = _rng(seed, name)
@@ -208,17 +252,19 @@ def synth_state_dict(seed=0, num_anchors=36, num_classes=4, shape_align=True, ce
                 v = g.normal(0.0, 0.8 * math.sqrt(2.0 / fan_in), shape)
                 if name.startswith("bbox_") and name.endswith(".6.weight"):
                     v = v * BOX_OUT_GAIN                      # regression deltas ~N(0, 0.3): realistic align offsets
+                if deep and name.startswith("base.base.level"):
+                    v = v * _dla102_gain(name)
         dt = torch.int64 if leaf == "num_batches_tracked" else torch.float32
         sd[name] = torch.from_numpy(np.asarray(v)).to(dt).reshape(shape)
     return sd
 
 
 def synth_conf(crop_size=(384, 1280), seed=0, batch_size=1, device="cuda:0", shape_align=True, center_align=True,
-               attention="ANAB"):
+               attention="ANAB", back_bone="dla34"):
     """Stand-in for the pickled training conf: 2-D anchors from the reference recipe
     (lib/rpn_util.py:39-52,167-183), seeded 3-D anchor columns and bbox_means/stds."""
     rng = np.random.Generator(np.random.PCG64([seed, 0xC0F]))
-    conf = Config()
+    conf = Config(back_bone=back_bone)
     conf.attention, conf.center_align, conf.shape_align = attention, center_align, shape_align
     conf.crop_size = list(crop_size)
     conf.batch_size = batch_size
