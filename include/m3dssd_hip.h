@@ -14,6 +14,12 @@
  *                                 stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
  *                                 model/DCNv2/src/dcn_v2_cuda.h:9-17, dcn_v2_cuda.c:10-102,
  *                                 kernel model/DCNv2/src/cuda/dcn_v2_im2col_cuda.cu:118-180
+ *   m3d_dcn_v2_backward ........ void dcn_v2_cuda_backward(THCudaTensor *input, *weight, *bias, *ones, *offset, *mask,
+ *                                 *columns, *grad_input, *grad_weight, *grad_bias, *grad_offset, *grad_mask,
+ *                                 *grad_output, kernel_h, ..., deformable_group)
+ *                                 model/DCNv2/src/dcn_v2_cuda.h:18-29, dcn_v2_cuda.c:104-241, kernels
+ *                                 model/DCNv2/src/cuda/dcn_v2_im2col_cuda.cu:49-116,182-312
+ *   m3d_dcn_v2_backward_workspace_bytes .. the `ones` / `columns` scratch tensors of that call (dcn_v2_func.py:41-48)
  *   _nms / m3d_nms_sorted_dev .. void _nms(int* keep_out, int* num_out, const float* boxes_host,
  *                                 int boxes_num, int boxes_dim, float nms_overlap_thresh, int device_id)
  *                                 lib/nms/gpu_nms.hpp:1-2, lib/nms/nms_kernel.cu:91-144 (kernel :34-78)
@@ -61,12 +67,15 @@ enum {
 const char *m3d_last_error(void);
 /* Library/ABI version.  Policy: the number moves whenever a caller built against the previous header could misbehave --
  * a signature or struct layout changes, the CONTRACT of an argument changes (a workspace size rule, a row limit, a
- * precondition), or entry points are added that the Python binding resolves at load time.  A binding checks it once
- * after dlopen and refuses a library of another version (m3dssd_amd/_hip.py).
+ * precondition), or existing entry points are removed or replaced.  Purely additive entry points do NOT move it: an old
+ * binding never calls them, and a new binding on a library that lacks them fails at load, because the Python binding resolves
+ * every declared name when it opens the library (m3dssd_amd/_hip.py: lib()).  A binding checks the number once after dlopen
+ * and refuses a library of another version.
  *   4 -> 5 (round 6): m3d_conv_bf16_desc.dcn_ws sized by m3d_conv_bf16_dcn_ws_bytes(N, Ho, Wo) (was ">= 1024 bytes"),
  *                     m3d_nms_sorted_dev / m3d_topk_decode accept up to 16 384 rows per image (was 4 096), 15 entry
  *                     points added in round 5 (anab_attend_*, head_mlp2 / tail2 / qkvs bf16, tree_entry, frontend2, ...),
- *                     the round-4 experimental forms (bf16_wino2, bf16_frontend, bf16_head_mlp) left the product library. */
+ *                     the round-4 experimental forms (bf16_wino2, bf16_frontend, bf16_head_mlp) left the product library.
+ *   added under 5: m3d_dcn_v2_backward, m3d_dcn_v2_backward_workspace_bytes (additive; nothing existing changed). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -421,6 +430,29 @@ int m3d_dcn_v2_forward(const float *input, const float *weight, const float *bia
                        int channels_out, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h,
                        int pad_w, int dilation_h, int dilation_w, int deformable_group, void *workspace,
                        long long workspace_bytes, m3d_stream_t stream);
+
+/* Drop-in for dcn_v2_cuda_backward (csrc/dcn_backward.hip): NCHW contiguous fp32 device tensors, the reference's argument
+ * meaning with `ones` / `columns` replaced by the caller's workspace of m3d_dcn_v2_backward_workspace_bytes() bytes (-1 for an
+ * invalid group count; the size does not depend on which gradients are asked for).  Given grad_output [N, Co, Ho, Wo] it
+ * produces grad_input [N, C, H, W], grad_offset [N, G*2*kh*kw, Ho, Wo], grad_mask [N, G*kh*kw, Ho, Wo], grad_weight
+ * [Co, C, kh, kw] and grad_bias [Co]: the analytic derivative of m3d_dcn_v2_forward as it is defined (a sample contributes iff
+ * h_im > -1, w_im > -1, h_im < H, w_im < W, a corner iff it lies inside the image, hl = floor(h_im); a NaN / inf coordinate is
+ * outside and has zero gradients).  Two differences from the reference:
+ *   - every non-NULL gradient is OVERWRITTEN (the reference accumulates into grad_weight / grad_bias and adds into a
+ *     grad_input its caller has zeroed, dcn_v2_func.py:44-48);
+ *   - any of the five gradient pointers may be NULL = not wanted (autograd's needs_input_grad); the work only it needs is skipped.
+ * grad_offset, grad_mask, grad_weight and grad_bias are bitwise reproducible from run to run; grad_input is accumulated with
+ * float atomics, as in the reference (dcn_v2_im2col_cuda.cu:234), and may differ in its last bits between runs.
+ * Same restrictions and errors as the forward (stride_h == stride_w etc.; M3D_E_ARG / M3D_E_WORKSPACE with both sizes). */
+long long m3d_dcn_v2_backward_workspace_bytes(int batch, int channels, int height, int width, int channels_out,
+                                              int kernel_h, int kernel_w, int stride, int pad, int dilation,
+                                              int deformable_group);
+int m3d_dcn_v2_backward(const float *input, const float *weight, const float *offset, const float *mask,
+                        const float *grad_output,
+                        float *grad_input, float *grad_offset, float *grad_mask, float *grad_weight, float *grad_bias,
+                        int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
+                        int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
+                        int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
 
 /* Weight packing: [Cout, Cin, kh, kw] (torch layout) -> [Cout_pad, kh*kw*Cin_pad] (tap-major, zero pad). */
 int m3d_pack_conv_weight(const float *w, float *packed, int Cout, int Cout_pad, int Cin, int Cin_pad, int kh,

@@ -12,7 +12,8 @@ from . import ops
 class DCNv2Function:
     """Callable with the reference's legacy instance-style convention:
     ``DCNv2Function(stride, padding, dilation, deformable_groups)(input, offset, mask, weight, bias)``.
-    Inference only (the backward of the reference, dcn_v2_func.py:40-62, is out of scope)."""
+    With grad mode on and any of the five tensors requiring grad (the reference's rule, dcn_v2_func.py:25) the call goes through
+    the differentiable ``ops.dcn_v2`` (backward of the reference: dcn_v2_func.py:40-62); otherwise it is the plain forward."""
 
     def __init__(self, stride, padding, dilation=1, deformable_groups=1):
         self.stride, self.padding, self.dilation, self.deformable_groups = stride, padding, dilation, deformable_groups
@@ -23,8 +24,8 @@ class DCNv2Function:
     def forward(self, input, offset, mask, weight, bias):
         if not input.is_cuda:
             raise NotImplementedError
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (input, offset, mask)):
-            raise NotImplementedError("m3dssd_amd implements the DCNv2 forward only (inference path)")
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (input, offset, mask, weight, bias)):
+            return ops.dcn_v2(input, offset, mask, weight, bias, self.stride, self.padding, self.dilation, self.deformable_groups)
         with torch.no_grad():
             return ops.dcn_v2_forward(input, offset, mask, weight, bias, self.stride, self.padding, self.dilation,
                                       self.deformable_groups)
@@ -69,5 +70,13 @@ class DCN(DCNv2):
             self.conv_offset_mask.bias.zero_()
 
     def forward(self, input):
+        if input.is_cuda and torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # differentiable form, the reference's composition (dcn_v2.py:64-70): the offset / mask convolution through torch
+            out = self.conv_offset_mask(input)
+            o1, o2, mask = torch.chunk(out, 3, dim=1)
+            offset = torch.cat((o1, o2), dim=1)
+            mask = torch.sigmoid(mask)
+            return ops.dcn_v2(input.contiguous(), offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                              self.deformable_groups)
         from .standalone import dcn_layer_forward
         return dcn_layer_forward(self, input)

@@ -138,6 +138,9 @@ class DeformConv(nn.Module):
         self.conv = DCN(chi, cho, kernel_size=3, stride=1, padding=1, dilation=1, deformable_groups=1)
 
     def forward(self, x):
+        if self.training and torch.is_grad_enabled() and x.is_cuda:
+            # training form, model/pose_dla_dcn.py:482-485: differentiable DCN, torch BatchNorm with batch statistics
+            return self.actf(self.conv(x))
         from .standalone import deform_conv_forward
         return deform_conv_forward(self, x)
 

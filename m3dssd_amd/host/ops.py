@@ -54,6 +54,71 @@ def dcn_v2_forward(inp, offset, mask, weight, bias, stride, padding, dilation=1,
     return out
 
 
+def dcn_v2_backward(inp, offset, mask, weight, grad_output, stride, padding, dilation=1, deformable_groups=1,
+                    needs=(True, True, True, True, True)):
+    """DCNv2Function.backward (model/DCNv2/dcn_v2_func.py:40-62) on the HIP library: returns (grad_input, grad_offset, grad_mask,
+    grad_weight, grad_bias); an entry of ``needs`` that is False gives None and skips the work only that gradient needs.
+    Every returned gradient is freshly written (nothing is accumulated into)."""
+    _require_cuda(inp, offset, mask, weight, grad_output)
+    if not inp.is_contiguous():
+        raise RuntimeError("input tensor has to be contiguous")
+    if not weight.is_contiguous():
+        raise RuntimeError("weight tensor has to be contiguous")
+    if inp.dtype != torch.float32:
+        raise RuntimeError("dcn_v2_backward: float32 only")
+    L = _hip.lib()
+    n, c, h, w = inp.shape
+    co, ck, kh, kw = weight.shape
+    if ck != c:
+        raise RuntimeError("Input shape and kernel channels wont match: (%d vs %d)." % (c, ck))
+    if deformable_groups < 1 or c % deformable_groups:
+        raise RuntimeError("dcn_v2_backward: deformable_groups (%d) must divide the input channels (%d)" % (deformable_groups, c))
+    ho = (h + 2 * padding - (dilation * (kh - 1) + 1)) // stride + 1
+    wo = (w + 2 * padding - (dilation * (kw - 1) + 1)) // stride + 1
+    if tuple(offset.shape) != (n, deformable_groups * 2 * kh * kw, ho, wo) or \
+            tuple(mask.shape) != (n, deformable_groups * kh * kw, ho, wo):
+        raise RuntimeError("dcn_v2_backward: offset/mask shape does not match the output size")
+    if tuple(grad_output.shape) != (n, co, ho, wo):
+        raise RuntimeError("dcn_v2_backward: grad_output shape does not match the output size")
+    offset, mask, weight = offset.contiguous().float(), mask.contiguous().float(), weight.float()
+    grad_output = grad_output.contiguous().float()
+    shapes = (inp.shape, offset.shape, mask.shape, weight.shape, (co,))
+    grads = [torch.empty(tuple(s), device=inp.device, dtype=torch.float32) if need else None for s, need in zip(shapes, needs)]
+    nbytes = L.m3d_dcn_v2_backward_workspace_bytes(n, c, h, w, co, kh, kw, stride, padding, dilation, deformable_groups)
+    if nbytes < 0:
+        raise RuntimeError("dcn_v2_backward: bad shape")
+    ws = torch.empty(nbytes + 256, device=inp.device, dtype=torch.uint8)
+    base = (ws.data_ptr() + 255) // 256 * 256
+    ptrs = [g.data_ptr() if g is not None else None for g in grads]
+    with torch.cuda.device(inp.device):
+        _hip.check(L.m3d_dcn_v2_backward(inp.data_ptr(), weight.data_ptr(), offset.data_ptr(), mask.data_ptr(),
+                                         grad_output.data_ptr(), *ptrs, n, c, h, w, co, kh, kw, stride, stride, padding, padding,
+                                         dilation, dilation, deformable_groups, base, nbytes, _stream()))
+    return tuple(grads)
+
+
+class _DCNv2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, inp, offset, mask, weight, bias, stride, padding, dilation, deformable_groups):
+        ctx.conf = (stride, padding, dilation, deformable_groups)
+        ctx.save_for_backward(inp, offset, mask, weight)
+        return dcn_v2_forward(inp, offset, mask, weight, bias, stride, padding, dilation, deformable_groups)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        inp, offset, mask, weight = ctx.saved_tensors
+        grads = dcn_v2_backward(inp, offset, mask, weight, grad_output, *ctx.conf, needs=tuple(ctx.needs_input_grad[:5]))
+        return grads + (None, None, None, None)
+
+
+def dcn_v2(inp, offset, mask, weight, bias, stride, padding, dilation=1, deformable_groups=1):
+    """The DCNv2 operator, differentiable in its five tensor arguments: m3d_dcn_v2_forward (the bits of ``dcn_v2_forward``) with
+    m3d_dcn_v2_backward behind it."""
+    _require_cuda(inp, offset, mask, weight, bias)
+    return _DCNv2.apply(inp, offset, mask, weight, bias, stride, padding, dilation, deformable_groups)
+
+
 def nms_sorted(boxes_sorted, thresh):
     """Device NMS on score-sorted boxes [B, n, >=4] (or [n, >=4]) -> (keep [B, n] int32, num [B] int32)."""
     _require_cuda(boxes_sorted)
