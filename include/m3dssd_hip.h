@@ -20,6 +20,8 @@
  *                                 model/DCNv2/src/dcn_v2_cuda.h:18-29, dcn_v2_cuda.c:104-241, kernels
  *                                 model/DCNv2/src/cuda/dcn_v2_im2col_cuda.cu:49-116,182-312
  *   m3d_dcn_v2_backward_workspace_bytes .. the `ones` / `columns` scratch tensors of that call (dcn_v2_func.py:41-48)
+ *   m3d_rpn_targets / m3d_rpn_loss .. RPN_3D_loss.forward, lib/loss/rpn_3d.py:54-657, with compute_targets,
+ *                                 lib/rpn_util.py:430-532 (host numpy in the reference) and the backward autograd derives
  *   _nms / m3d_nms_sorted_dev .. void _nms(int* keep_out, int* num_out, const float* boxes_host,
  *                                 int boxes_num, int boxes_dim, float nms_overlap_thresh, int device_id)
  *                                 lib/nms/gpu_nms.hpp:1-2, lib/nms/nms_kernel.cu:91-144 (kernel :34-78)
@@ -75,7 +77,8 @@ const char *m3d_last_error(void);
  *                     m3d_nms_sorted_dev / m3d_topk_decode accept up to 16 384 rows per image (was 4 096), 15 entry
  *                     points added in round 5 (anab_attend_*, head_mlp2 / tail2 / qkvs bf16, tree_entry, frontend2, ...),
  *                     the round-4 experimental forms (bf16_wino2, bf16_frontend, bf16_head_mlp) left the product library.
- *   added under 5: m3d_dcn_v2_backward, m3d_dcn_v2_backward_workspace_bytes (additive; nothing existing changed). */
+ *   added under 5: m3d_dcn_v2_backward, m3d_dcn_v2_backward_workspace_bytes (additive; nothing existing changed);
+ *                  m3d_rpn_targets, m3d_rpn_loss, m3d_rpn_loss_workspace_bytes (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -453,6 +456,75 @@ int m3d_dcn_v2_backward(const float *input, const float *weight, const float *of
                         int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
                         int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
                         int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * RPN_3D_loss on the device (csrc/rpn_loss.hip): target assignment, hard-negative sampling, fused loss + gradients.
+ * Row r of an image is anchor (a, h, w), r = (a*H + h)*W + w, R = A*H*W rows (locate_anchors' order); cls / prob are
+ * [B, R, C], bbox_2d [B, R, 4], bbox_3d [B, R, 7], contiguous float32 device tensors.
+ *   anchors   device, float64 [A, 9]: x1 y1 x2 y2 z w h l ry (conf.anchors widened).
+ *   conf      HOST, float64 [M3D_RPN_CONF_COUNT], indices below.  box_samples may be +inf; fg_fraction NaN = None (only with
+ *             box_samples = inf, as in the reference).
+ *   gt_table  device, float64 [B, Gmax + 1, M3D_RPN_GT_COLS] -- the one upload of a call.  Row 0 of an image: n_valid, n_ignore.
+ *             Rows 1 .. n_valid: x1 y1 x2 y2 (corners), class label (1 .. C-1), then bbox_3d[0:7] = cx cy z w h l ry.  The next
+ *             n_ignore rows: x1 y1 x2 y2 of the ignore regions.  n_valid + n_ignore <= Gmax <= M3D_RPN_MAX_GT; a larger Gmax is
+ *             M3D_E_ARG (nothing is truncated).  An image with n_valid = 0 contributes nothing (label 0 everywhere).
+ * m3d_rpn_targets writes, per row: labels (int16: class for fg, 0 for bg, 3000 for ignored), gt_index (int16: the valid gt a fg
+ * row regresses to, -1 otherwise), targets (float32 [B, R, 11]: the normalised 2-D (4) and 3-D (7) transforms; (0 - mean) / std
+ * where the row is not fg), scores (float32: prob[label], the key of the sampling), and leaves the per-image counts in the
+ * workspace.  m3d_rpn_loss must get the SAME workspace, untouched, and the same labels / targets / scores; it writes sampled
+ * (uint8: 0 no, 1 fg, 2 bg), the gradients of `loss` with respect to cls, bbox_2d and bbox_3d (zero for unsampled rows), the
+ * float32 loss and the float64 stat block (indices below).  Among equal scores the lower row is sampled first.  A sampled fg
+ * whose decoded box misses its target gives loss = +inf like the reference and a ZERO IoU-term gradient for that row (the
+ * reference's is NaN).  Everything is bitwise reproducible from run to run; nothing is copied to the host.
+ * ------------------------------------------------------------------------------------------ */
+#define M3D_RPN_MAX_GT 128
+#define M3D_RPN_GT_COLS 12
+enum {
+    M3D_RPN_CONF_MEANS = 0,        /* 11 */
+    M3D_RPN_CONF_STDS = 11,        /* 11 */
+    M3D_RPN_CONF_FG_THRESH = 22,
+    M3D_RPN_CONF_IGN_THRESH = 23,
+    M3D_RPN_CONF_BG_LO = 24,
+    M3D_RPN_CONF_BG_HI = 25,
+    M3D_RPN_CONF_BEST_THRESH = 26,
+    M3D_RPN_CONF_BOX_SAMPLES = 27,
+    M3D_RPN_CONF_FG_FRACTION = 28,
+    M3D_RPN_CONF_FOCAL = 29,
+    M3D_RPN_CONF_LAMBDA_CLS = 30,
+    M3D_RPN_CONF_LAMBDA_IOU = 31,
+    M3D_RPN_CONF_LAMBDA_2D = 32,
+    M3D_RPN_CONF_LAMBDA_3D = 33,
+    M3D_RPN_CONF_STRIDE = 34,
+    M3D_RPN_CONF_COUNT = 35
+};
+enum {
+    M3D_RPN_STAT_LOSS = 0,
+    M3D_RPN_STAT_CLS = 1,
+    M3D_RPN_STAT_BBOX_2D = 2,
+    M3D_RPN_STAT_BBOX_3D = 3,
+    M3D_RPN_STAT_IOU_LOSS = 4,
+    M3D_RPN_STAT_Z = 5,
+    M3D_RPN_STAT_RY = 6,
+    M3D_RPN_STAT_IOU_ACC = 7,
+    M3D_RPN_STAT_ACC_FG = 8,
+    M3D_RPN_STAT_ACC_BG = 9,
+    M3D_RPN_STAT_N_FG = 10,       /* fg / bg rows of the batch (all, not only the sampled) */
+    M3D_RPN_STAT_N_BG = 11,
+    M3D_RPN_STAT_FG_NUM = 12,     /* sampled fg / bg rows of the batch */
+    M3D_RPN_STAT_BG_NUM = 13,
+    M3D_RPN_STAT_N_ACTIVE = 14,   /* rows in the mean of the classification loss */
+    M3D_RPN_STAT_FG_WEIGHT = 15,
+    M3D_RPN_STAT_COUNT = 16
+};
+long long m3d_rpn_loss_workspace_bytes(int B, long long R);
+int m3d_rpn_targets(const double *anchors, int A, int H, int W, const double *conf, int n_conf, const double *gt_table, int B,
+                    int Gmax, const float *cls, const float *prob, int C, short *labels, short *gt_index, float *targets,
+                    float *scores, void *workspace, long long workspace_bytes, m3d_stream_t stream);
+int m3d_rpn_loss(const double *anchors, int A, int H, int W, const double *conf, int n_conf, const double *gt_table, int B,
+                 int Gmax, const float *cls, const float *bbox_2d, const float *bbox_3d, int C, const short *labels,
+                 const float *targets, const float *scores, unsigned char *sampled, float *grad_cls, float *grad_bbox_2d,
+                 float *grad_bbox_3d, float *loss, double *stats, void *workspace, long long workspace_bytes,
+                 m3d_stream_t stream);
 
 /* Weight packing: [Cout, Cin, kh, kw] (torch layout) -> [Cout_pad, kh*kw*Cin_pad] (tap-major, zero pad). */
 int m3d_pack_conv_weight(const float *w, float *packed, int Cout, int Cout_pad, int Cin, int Cin_pad, int kh,

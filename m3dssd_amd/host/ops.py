@@ -119,6 +119,19 @@ def dcn_v2(inp, offset, mask, weight, bias, stride, padding, dilation=1, deforma
     return _DCNv2.apply(inp, offset, mask, weight, bias, stride, padding, dilation, deformable_groups)
 
 
+def rpn_targets(cls, prob, anchors, conf_vec, gt_table, feat_size):
+    """compute_targets (lib/rpn_util.py:430-532) for a whole batch on the device: m3d_rpn_targets.  ``anchors`` float64 device
+    [A, 9], ``conf_vec`` from ``host.loss.pack_conf``, ``gt_table`` from ``host.loss.pack_gts``; see host/loss.py."""
+    from . import loss
+    return loss.rpn_targets(cls, prob, anchors, conf_vec, gt_table, feat_size)
+
+
+def rpn_loss(cls, prob, bbox_2d, bbox_3d, anchors, conf_vec, gt_table, feat_size, return_details=False):
+    """The RPN_3D_loss computation below the module: m3d_rpn_targets + m3d_rpn_loss, differentiable in cls, bbox_2d, bbox_3d."""
+    from . import loss
+    return loss.rpn_loss(cls, prob, bbox_2d, bbox_3d, anchors, conf_vec, gt_table, feat_size, return_details)
+
+
 def nms_sorted(boxes_sorted, thresh):
     """Device NMS on score-sorted boxes [B, n, >=4] (or [n, >=4]) -> (keep [B, n] int32, num [B] int32)."""
     _require_cuda(boxes_sorted)
