@@ -78,7 +78,8 @@ const char *m3d_last_error(void);
  *                     points added in round 5 (anab_attend_*, head_mlp2 / tail2 / qkvs bf16, tree_entry, frontend2, ...),
  *                     the round-4 experimental forms (bf16_wino2, bf16_frontend, bf16_head_mlp) left the product library.
  *   added under 5: m3d_dcn_v2_backward, m3d_dcn_v2_backward_workspace_bytes (additive; nothing existing changed);
- *                  m3d_rpn_targets, m3d_rpn_loss, m3d_rpn_loss_workspace_bytes (additive). */
+ *                  m3d_rpn_targets, m3d_rpn_loss, m3d_rpn_loss_workspace_bytes (additive);
+ *                  m3d_topk_decode_planar_mw, m3d_topk_decode_mw_workspace_bytes (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -672,6 +673,18 @@ int m3d_topk_decode_planar(const unsigned int *score_bits, const float *cls_plan
                            const float *anchors, const float *means, const float *stds, const float *scale, float *aboxes,
                            int *rows_out, void *workspace, long long workspace_bytes, int B, int A, int HW, int k,
                            m3d_stream_t stream);
+/* m3d_topk_decode_planar for few images on a large chip: the pass over all R keys is spread over `wgs_per_image` workgroups
+ * per image (histogram of the top 11 score bits into a global histogram, then every workgroup appends its slice's keys above /
+ * inside the threshold bin to global lists), and one finishing workgroup per image walks the lower digits, sorts and decodes.
+ * Four launches whatever the data (graph-capturable), integer atomics only, nothing carried over between calls.  Same contract
+ * and limits, output identical bit for bit.  wgs_per_image: 0 = the library's choice, else 1 .. 256 (M3D_E_ARG outside);
+ * slices are whole 16-byte groups of keys, so trailing workgroups may be idle.  workspace:
+ * m3d_topk_decode_mw_workspace_bytes(B, R = A * HW, k)  (-1 for a non-positive argument). */
+long long m3d_topk_decode_mw_workspace_bytes(int B, int R, int k);
+int m3d_topk_decode_planar_mw(const unsigned int *score_bits, const float *cls_planar, const float *box_planar, const float *rois,
+                              const float *anchors, const float *means, const float *stds, const float *scale, float *aboxes,
+                              int *rows_out, void *workspace, long long workspace_bytes, int B, int A, int HW, int k,
+                              int wgs_per_image, m3d_stream_t stream);
 /* Decode `n_rows` selected rows per image -> aboxes [B][n_rows][14]
  * (x1,y1,x2,y2,score,cls,x3d,y3d,z3d,w3d,h3d,l3d,ry3d,anchor). */
 int m3d_decode_rows(const long long *rows /*[B][n_rows] row ids*/, const float *prob, const float *bbox_2d,

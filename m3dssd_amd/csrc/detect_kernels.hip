@@ -9,6 +9,11 @@
 //    deterministic), rows above the threshold bin are selected, rows inside it become the candidates of the next digit
 //    (ping-pong buffers in the workspace; typically a few hundred rows); the walk ends as soon as the candidates left are
 //    exactly the rows still needed.  No float atomics, no data-dependent launch count: graph-capturable.
+//  * topk_mw_*: the same selection for ONE frame, where one workgroup per image leaves the chip idle: the level-0 pass over all R
+//    keys is spread over `wgs` workgroups per image (zero -> per-slice LDS histogram added into a global one -> every workgroup
+//    finds the threshold bin itself and appends its slice's keys to a global selected / candidate list), and the finishing
+//    launch is topk_decode_kernel<true>: the lower digits, the sort and the decode of the single-workgroup kernel, unchanged.
+//    The 64-bit keys are unique and the finish sorts them, so the output does not depend on the order of the appends.
 //  * select_post_kernel: keep lists of the NMS -> [B][post + 1][14] blocks (zero padded; row `post` carries the count), the
 //    wire format of the multi-GPU all-gather.
 #include <atomic>
@@ -132,6 +137,10 @@ struct TopkArgs {
     const float *scale;               // [B] or null: test-time scale factor of each image (lib/rpn_util.py:1504-1506)
     int R, k;
     int A, HW;                        // planar form (A > 0): prob = cls planar [B][4A][HW], b2 = box planar [B][11][A*HW], b3 unused
+    // multi-workgroup form (topk_mw_*): what the level-0 launches leave for the finishing one, behind `cand` in the workspace
+    unsigned long long *mw_sel;       // [B][k] keys above the threshold bin (fewer than k by the definition of the bin)
+    unsigned *mw_hist;                // [B][2048] histogram of the top 11 score bits
+    unsigned *mw_cnt;                 // [B][2] keys in mw_sel, keys in cand[b][0]
 };
 
 // Exclusive prefix sum of one value per thread over the 1024-thread workgroup (16 waves): wave shuffles + one LDS hop.
@@ -152,6 +161,8 @@ __device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned *wave_t
     return base + inc - v;
 }
 
+// MW: level 0 was done by topk_mw_hist_kernel / topk_mw_scatter_kernel (selected keys in a.mw_sel, candidates in cand[img][0])
+template <bool MW>
 __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
 {
     __shared__ unsigned hist[2048];
@@ -160,7 +171,7 @@ __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
     __shared__ unsigned s_bin, s_above, s_nsel, s_ncand;
     const int img = blockIdx.x, tid = threadIdx.x;
     const int R = a.R, k = a.k;
-    const unsigned int *sc = a.score_bits + (size_t)img * R;
+    [[maybe_unused]] const unsigned int *sc = a.score_bits + (size_t)img * R;
     unsigned long long *candA = a.cand + (size_t)img * 2 * R, *candB = candA + R;
 
     // threshold bin of a 2048-bin histogram: the highest bin b with  count(digit > b) < need <= count(digit >= b)
@@ -178,46 +189,57 @@ __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
     for (int i = tid; i < 2048; i += TOPK_NT) hist[i] = 0;
     __syncthreads();
     // ---- level 0: top 11 bits of the score over all R rows -----------------------------------------------------------
-    const int R4 = R >> 2;
-    const u32x4 *sc4 = reinterpret_cast<const u32x4 *>(sc);    // R*4 bytes per image: 16-byte aligned when R % 4 == 0
-    const bool vec = (R & 3) == 0;
-    if (vec) {
-        for (int i = tid; i < R4; i += TOPK_NT) {
-            const u32x4 v = sc4[i];
-            atomicAdd(&hist[v[0] >> 21], 1u);
-            atomicAdd(&hist[v[1] >> 21], 1u);
-            atomicAdd(&hist[v[2] >> 21], 1u);
-            atomicAdd(&hist[v[3] >> 21], 1u);
-        }
-    } else {
-        for (int i = tid; i < R; i += TOPK_NT) atomicAdd(&hist[sc[i] >> 21], 1u);
-    }
-    __syncthreads();
-    find_bin(need);
-    {
-        const unsigned bin = s_bin;
-        auto put = [&](unsigned s, int row) {
-            const unsigned d = s >> 21;
-            if (d >= bin) {
-                const unsigned long long key = ((unsigned long long)s << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)row);
-                if (d > bin) sel[atomicAdd(&s_nsel, 1u)] = key;
-                else candA[atomicAdd(&s_ncand, 1u)] = key;
-            }
-        };
+    unsigned ncand;
+    if constexpr (!MW) {
+        const int R4 = R >> 2;
+        const u32x4 *sc4 = reinterpret_cast<const u32x4 *>(sc);    // R*4 bytes per image: 16-byte aligned when R % 4 == 0
+        const bool vec = (R & 3) == 0;
         if (vec) {
             for (int i = tid; i < R4; i += TOPK_NT) {
                 const u32x4 v = sc4[i];
-                put(v[0], 4 * i); put(v[1], 4 * i + 1); put(v[2], 4 * i + 2); put(v[3], 4 * i + 3);
+                atomicAdd(&hist[v[0] >> 21], 1u);
+                atomicAdd(&hist[v[1] >> 21], 1u);
+                atomicAdd(&hist[v[2] >> 21], 1u);
+                atomicAdd(&hist[v[3] >> 21], 1u);
             }
         } else {
-            for (int i = tid; i < R; i += TOPK_NT) put(sc[i], i);
+            for (int i = tid; i < R; i += TOPK_NT) atomicAdd(&hist[sc[i] >> 21], 1u);
         }
+        __syncthreads();
+        find_bin(need);
+        {
+            const unsigned bin = s_bin;
+            auto put = [&](unsigned s, int row) {
+                const unsigned d = s >> 21;
+                if (d >= bin) {
+                    const unsigned long long key = ((unsigned long long)s << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)row);
+                    if (d > bin) sel[atomicAdd(&s_nsel, 1u)] = key;
+                    else candA[atomicAdd(&s_ncand, 1u)] = key;
+                }
+            };
+            if (vec) {
+                for (int i = tid; i < R4; i += TOPK_NT) {
+                    const u32x4 v = sc4[i];
+                    put(v[0], 4 * i); put(v[1], 4 * i + 1); put(v[2], 4 * i + 2); put(v[3], 4 * i + 3);
+                }
+            } else {
+                for (int i = tid; i < R; i += TOPK_NT) put(sc[i], i);
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+        need -= s_above;
+        ncand = s_ncand;
+        __syncthreads();                                           // everyone has read the counters before they are reset
+    } else {
+        const unsigned nsel = min(a.mw_cnt[2 * img], (unsigned)k);
+        const unsigned long long *gsel = a.mw_sel + (size_t)img * k;
+        for (unsigned i = tid; i < nsel; i += TOPK_NT) sel[i] = gsel[i];
+        if (tid == 0) s_nsel = nsel;
+        need -= nsel;                                          // = count(digit > threshold bin)
+        ncand = min(a.mw_cnt[2 * img + 1], (unsigned)R);
+        __syncthreads();
     }
-    __threadfence_block();
-    __syncthreads();
-    need -= s_above;
-    unsigned ncand = s_ncand;
-    __syncthreads();                                           // everyone has read the counters before they are reset
     // ---- lower digits over the candidate list (global ping-pong; the workgroup is its only reader / writer) ---------
     // key bits 52..42, 41..32, then the row part: bits 31..22 are all ones for R < 2^22, so 21..11 and 10..0
     const int shifts[4] = {42, 32, 11, 0};
@@ -287,6 +309,7 @@ __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
     }
 }
 
+template <bool MW>
 static int topk_launch(const TopkArgs &a, int B, hipStream_t stream)
 {
     int P = 1;
@@ -295,12 +318,12 @@ static int topk_launch(const TopkArgs &a, int B, hipStream_t stream)
     if (lds > 32768) {
         // The raised dynamic-LDS limit is a PER-DEVICE attribute of the kernel: a process that drives several GPUs (nn.DataParallel
         // replica engines, one engine per device) needs it on each of them -- set it on the current device, once per device ordinal.
-        static std::atomic<int> state[64];                             // 0 unknown, 1 raised, 2 refused
+        static std::atomic<int> state[64];                             // 0 unknown, 1 raised, 2 refused (per kernel form)
         int dev = 0;
         M3D_HIP(hipGetDevice(&dev));
         int st = (dev >= 0 && dev < 64) ? state[dev].load(std::memory_order_acquire) : 0;
         if (st == 0) {
-            const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_decode_kernel),
+            const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_decode_kernel<MW>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
                                                 TOPK_MAXK * (int)sizeof(unsigned long long)) == hipSuccess;
             if (!ok) (void)hipGetLastError();
@@ -309,7 +332,7 @@ static int topk_launch(const TopkArgs &a, int B, hipStream_t stream)
         }
         M3D_REQUIRE(st == 1, "topk_decode: device %d cannot reserve %d bytes of LDS for k = %d", dev, lds, a.k);
     }
-    hipLaunchKernelGGL(topk_decode_kernel, dim3(B), dim3(TOPK_NT), lds, stream, a);
+    hipLaunchKernelGGL(topk_decode_kernel<MW>, dim3(B), dim3(TOPK_NT), lds, stream, a);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
 }
@@ -344,8 +367,8 @@ extern "C" int m3d_topk_decode_scaled(const unsigned int *score_bits, const floa
     TopkArgs a;
     a.score_bits = score_bits; a.prob = prob; a.b2 = bbox_2d; a.b3 = bbox_3d; a.rois = rois; a.anchors = anchors;
     a.means = means; a.stds = stds; a.aboxes = aboxes; a.rows_out = rows_out; a.cand = (unsigned long long *)workspace;
-    a.R = R; a.k = k; a.scale = scale; a.A = 0; a.HW = 0;
-    return topk_launch(a, B, (hipStream_t)stream);
+    a.R = R; a.k = k; a.scale = scale; a.A = 0; a.HW = 0; a.mw_sel = nullptr; a.mw_hist = nullptr; a.mw_cnt = nullptr;
+    return topk_launch<false>(a, B, (hipStream_t)stream);
 }
 
 extern "C" int m3d_topk_decode_planar(const unsigned int *score_bits, const float *cls_planar, const float *box_planar,
@@ -365,8 +388,196 @@ extern "C" int m3d_topk_decode_planar(const unsigned int *score_bits, const floa
     TopkArgs a;
     a.score_bits = score_bits; a.prob = cls_planar; a.b2 = box_planar; a.b3 = nullptr; a.rois = rois; a.anchors = anchors;
     a.means = means; a.stds = stds; a.aboxes = aboxes; a.rows_out = rows_out; a.cand = (unsigned long long *)workspace;
+    a.R = R; a.k = k; a.scale = scale; a.A = A; a.HW = HW; a.mw_sel = nullptr; a.mw_hist = nullptr; a.mw_cnt = nullptr;
+    return topk_launch<false>(a, B, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Multi-workgroup level 0 (one frame on a 256-CU chip: one workgroup per image reads all R keys twice from a single CU).
+// Image b's keys are cut into `wgs` slices of whole 16-byte groups (single keys when R % 4 != 0); slices past the end are empty.
+//   zero    : global histogram and the two list counters of every image (nothing carries over from an earlier call)
+//   hist    : per-slice LDS histogram of the top 11 score bits, non-zero bins added into the image's global histogram
+//   scatter : every workgroup finds the threshold bin from the global histogram, counts its slice's keys above / inside the
+//             bin, reserves room in the global lists with ONE atomicAdd per list, and writes the keys there
+//   finish  : topk_decode_kernel<true>
+// Integer atomics only.  The launch list is fixed: graph-capturable.
+#define TOPK_MW_MAX_WGS 256               // per image: one slice per CU
+// library's choice for wgs_per_image = 0: one slice per four CUs, 1 080 16-byte groups per slice at R = 276 480.  To be replaced by the
+// best of the sweep of tools/latency_frame.py's kernel leg (B = 1, R = 276 480, k = 3000; profiles/latency_frame.jsonl): NOT MEASURED yet.
+#define TOPK_MW_DEFAULT_WGS 64
+
+struct TopkSlice { int lo, hi; bool vec; };
+
+__device__ __forceinline__ TopkSlice topk_mw_slice(int R, int wg, int wgs)
+{
+    TopkSlice s;
+    s.vec = (R & 3) == 0;
+    const int n = s.vec ? (R >> 2) : R;                    // units: 16-byte groups of four keys, or single keys
+    const int per = (n + wgs - 1) / wgs;
+    s.lo = min(n, wg * per);
+    s.hi = min(n, s.lo + per);
+    return s;
+}
+
+__global__ __launch_bounds__(TOPK_NT) void topk_mw_zero_kernel(TopkArgs a)
+{
+    const int img = blockIdx.x;
+    for (int i = threadIdx.x; i < 2048; i += TOPK_NT) a.mw_hist[(size_t)img * 2048 + i] = 0;
+    if (threadIdx.x < 2) a.mw_cnt[2 * img + threadIdx.x] = 0;
+}
+
+__global__ __launch_bounds__(TOPK_NT) void topk_mw_hist_kernel(TopkArgs a)
+{
+    __shared__ unsigned hist[2048];
+    const int img = blockIdx.y, tid = threadIdx.x;
+    const TopkSlice sl = topk_mw_slice(a.R, blockIdx.x, gridDim.x);
+    if (sl.lo >= sl.hi) return;                            // (uniform over the workgroup)
+    const unsigned int *sc = a.score_bits + (size_t)img * a.R;
+    for (int i = tid; i < 2048; i += TOPK_NT) hist[i] = 0;
+    __syncthreads();
+    if (sl.vec) {
+        const u32x4 *sc4 = reinterpret_cast<const u32x4 *>(sc);
+        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) {
+            const u32x4 v = sc4[i];
+            atomicAdd(&hist[v[0] >> 21], 1u);
+            atomicAdd(&hist[v[1] >> 21], 1u);
+            atomicAdd(&hist[v[2] >> 21], 1u);
+            atomicAdd(&hist[v[3] >> 21], 1u);
+        }
+    } else {
+        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) atomicAdd(&hist[sc[i] >> 21], 1u);
+    }
+    __syncthreads();
+    unsigned *gh = a.mw_hist + (size_t)img * 2048;
+    for (int i = tid; i < 2048; i += TOPK_NT) {
+        const unsigned h = hist[i];
+        if (h) atomicAdd(&gh[i], h);
+    }
+}
+
+__global__ __launch_bounds__(TOPK_NT) void topk_mw_scatter_kernel(TopkArgs a)
+{
+    __shared__ unsigned hist[2048];
+    __shared__ unsigned wave_tot[16];
+    __shared__ unsigned s_bin, s_csel, s_ccand, s_bsel, s_bcand, s_isel, s_icand;
+    const int img = blockIdx.y, tid = threadIdx.x;
+    const int R = a.R, k = a.k;
+    const TopkSlice sl = topk_mw_slice(R, blockIdx.x, gridDim.x);
+    if (sl.lo >= sl.hi) return;
+    const unsigned int *sc = a.score_bits + (size_t)img * R;
+    const u32x4 *sc4 = reinterpret_cast<const u32x4 *>(sc);
+    const unsigned *gh = a.mw_hist + (size_t)img * 2048;
+    for (int i = tid; i < 2048; i += TOPK_NT) hist[i] = gh[i];
+    if (tid == 0) { s_csel = 0; s_ccand = 0; s_isel = 0; s_icand = 0; }
+    __syncthreads();
+    {   // threshold bin: the highest bin b with  count(digit > b) < k <= count(digit >= b)  (as topk_decode_kernel finds it)
+        const unsigned need = (unsigned)k;
+        const int j0 = 2047 - 2 * tid, j1 = j0 - 1;
+        const unsigned h0 = hist[j0], h1 = hist[j1];
+        const unsigned ex = block_excl_scan(h0 + h1, wave_tot, tid);
+        if (ex < need && need <= ex + h0) s_bin = (unsigned)j0;
+        else if (ex + h0 < need && need <= ex + h0 + h1) s_bin = (unsigned)j1;
+        __syncthreads();
+    }
+    const unsigned bin = s_bin;
+    // how many keys of the slice go to either list
+    unsigned csel = 0, ccand = 0;
+    auto count = [&](unsigned s) {
+        const unsigned d = s >> 21;
+        csel += d > bin;
+        ccand += d == bin;
+    };
+    if (sl.vec) {
+        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) {
+            const u32x4 v = sc4[i];
+            count(v[0]); count(v[1]); count(v[2]); count(v[3]);
+        }
+    } else {
+        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) count(sc[i]);
+    }
+    if (csel) atomicAdd(&s_csel, csel);
+    if (ccand) atomicAdd(&s_ccand, ccand);
+    __syncthreads();
+    if (s_csel == 0 && s_ccand == 0) return;               // (uniform)
+    if (tid == 0) {
+        s_bsel = s_csel ? atomicAdd(&a.mw_cnt[2 * img], s_csel) : 0;
+        s_bcand = s_ccand ? atomicAdd(&a.mw_cnt[2 * img + 1], s_ccand) : 0;
+    }
+    __syncthreads();
+    const unsigned bsel = s_bsel, bcand = s_bcand;
+    unsigned long long *gsel = a.mw_sel + (size_t)img * k;
+    unsigned long long *cand = a.cand + (size_t)img * 2 * R;
+    auto put = [&](unsigned s, int row) {
+        const unsigned d = s >> 21;
+        if (d >= bin) {
+            const unsigned long long key = ((unsigned long long)s << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)row);
+            if (d > bin) {
+                const unsigned at = bsel + atomicAdd(&s_isel, 1u);
+                if (at < (unsigned)k) gsel[at] = key;      // (count(digit > bin) < k: the bound never binds)
+            } else {
+                const unsigned at = bcand + atomicAdd(&s_icand, 1u);
+                if (at < (unsigned)R) cand[at] = key;
+            }
+        }
+    };
+    if (sl.vec) {
+        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) {
+            const u32x4 v = sc4[i];
+            put(v[0], 4 * i); put(v[1], 4 * i + 1); put(v[2], 4 * i + 2); put(v[3], 4 * i + 3);
+        }
+    } else {
+        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) put(sc[i], i);
+    }
+}
+
+static long long topk_mw_align(long long v) { return (v + 15) & ~15LL; }
+
+extern "C" long long m3d_topk_decode_mw_workspace_bytes(int B, int R, int k)
+{
+    if (B < 1 || R < 1 || k < 1) return -1;
+    // cand [B][2][R] keys (the layout of m3d_topk_decode_workspace_bytes), selected keys [B][k], histogram [B][2048], counters [B][2]
+    return m3d_topk_decode_workspace_bytes(B, R) + (long long)B * k * (long long)sizeof(unsigned long long)
+           + (long long)B * 2048 * (long long)sizeof(unsigned) + topk_mw_align((long long)B * 2 * (long long)sizeof(unsigned));
+}
+
+extern "C" int m3d_topk_decode_planar_mw(const unsigned int *score_bits, const float *cls_planar, const float *box_planar,
+                                         const float *rois, const float *anchors, const float *means, const float *stds,
+                                         const float *scale, float *aboxes, int *rows_out, void *workspace,
+                                         long long workspace_bytes, int B, int A, int HW, int k, int wgs_per_image,
+                                         m3d_stream_t stream)
+{
+    M3D_REQUIRE(score_bits && cls_planar && box_planar && rois && anchors && means && stds && aboxes && workspace,
+                "topk_decode_planar_mw: null pointer");
+    M3D_REQUIRE(B >= 1 && A >= 1 && HW >= 1 && (long long)A * HW < (1 << 22), "topk_decode_planar_mw: A * HW must be in [1, 2^22)");
+    const int R = A * HW;
+    M3D_REQUIRE(k >= 1 && k <= R && k <= TOPK_MAXK, "topk_decode_planar_mw: k (%d) must be in [1, min(R, %d)]", k, TOPK_MAXK);
+    M3D_REQUIRE(wgs_per_image >= 0 && wgs_per_image <= TOPK_MW_MAX_WGS,
+                "topk_decode_planar_mw: wgs_per_image (%d) must be in [0, %d] (0 = library's choice)", wgs_per_image, TOPK_MW_MAX_WGS);
+    if (workspace_bytes < m3d_topk_decode_mw_workspace_bytes(B, R, k)) {
+        m3d_set_error("topk_decode_planar_mw: workspace of %lld bytes, %lld needed", workspace_bytes,
+                      m3d_topk_decode_mw_workspace_bytes(B, R, k));
+        return M3D_E_WORKSPACE;
+    }
+    int wgs = wgs_per_image;
+    if (wgs == 0) {                                        // no more slices than there are workgroup-sized pieces of the image
+        const int units = (R & 3) ? R : (R >> 2);
+        wgs = max(1, min(TOPK_MW_DEFAULT_WGS, cdiv(units, TOPK_NT)));
+    }
+    TopkArgs a;
+    a.score_bits = score_bits; a.prob = cls_planar; a.b2 = box_planar; a.b3 = nullptr; a.rois = rois; a.anchors = anchors;
+    a.means = means; a.stds = stds; a.aboxes = aboxes; a.rows_out = rows_out; a.cand = (unsigned long long *)workspace;
     a.R = R; a.k = k; a.scale = scale; a.A = A; a.HW = HW;
-    return topk_launch(a, B, (hipStream_t)stream);
+    a.mw_sel = a.cand + (size_t)B * 2 * R;
+    a.mw_hist = reinterpret_cast<unsigned *>(a.mw_sel + (size_t)B * k);
+    a.mw_cnt = a.mw_hist + (size_t)B * 2048;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(topk_mw_zero_kernel, dim3(B), dim3(TOPK_NT), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(topk_mw_hist_kernel, dim3(wgs, B), dim3(TOPK_NT), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(topk_mw_scatter_kernel, dim3(wgs, B), dim3(TOPK_NT), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    return topk_launch<true>(a, B, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

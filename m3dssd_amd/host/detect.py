@@ -114,6 +114,34 @@ def detect_from_planar(eng, plan, rois, conf, scale=None):
     return aboxes, keep, num
 
 
+def detect_from_planar_mw(eng, plan, rois, conf, scale=None, wgs=None):
+    """detect_from_planar with the multi-workgroup top-k (``m3d_topk_decode_planar_mw``): the form for one frame (or a few), where
+    one workgroup per image leaves the chip idle behind the forward.  Same rows, same bits (tests/test_gpu_frame_detector.py).
+    wgs: workgroups per image for the pass over all rows; None = the library's choice."""
+    L = _hip.lib()
+    cls_pl, box_pl, bits = plan.named["cls_planar"], plan.named["box_planar"], plan.named["score_bits"]
+    dev = bits.device
+    B, R = bits.shape[0], bits.shape[1]
+    A = eng.A
+    HW = R // A
+    n_pre = min(int(conf.nms_topN_pre), R)
+    P = eng.P
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        aboxes = torch.empty(B, n_pre, 14, device=dev, dtype=torch.float32)
+        keep = torch.empty(B, n_pre, device=dev, dtype=torch.int32)
+        num = torch.empty(B, device=dev, dtype=torch.int32)
+        tk_bytes = L.m3d_topk_decode_mw_workspace_bytes(B, R, n_pre)
+        ws = torch.empty(max(tk_bytes, L.m3d_nms_workspace_bytes(B, n_pre)), device=dev, dtype=torch.uint8)
+        _hip.check(L.m3d_topk_decode_planar_mw(bits.data_ptr(), cls_pl.data_ptr(), box_pl.data_ptr(), rois.data_ptr(),
+                                               P["anchors"].data_ptr(), P["means"].data_ptr(), P["stds"].data_ptr(),
+                                               None if scale is None else scale.data_ptr(), aboxes.data_ptr(), None, ws.data_ptr(),
+                                               tk_bytes, B, A, HW, n_pre, 0 if wgs is None else int(wgs), st))
+        _hip.check(L.m3d_nms_sorted_dev(aboxes.data_ptr(), B, n_pre, 14, float(conf.nms_thres), ws.data_ptr(),
+                                        keep.data_ptr(), num.data_ptr(), st))
+    return aboxes, keep, num
+
+
 def score_keys_planar(eng, plan):
     """The launch that replaces bundle_outputs when only the detection stage follows: sort keys from the planar class logits."""
     bits = plan.named["score_bits"]

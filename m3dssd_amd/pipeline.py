@@ -1,4 +1,4 @@
-"""Throughput mode: a software-pipelined detector.
+"""Throughput mode: a software-pipelined detector (``PipelinedDetector``); single-frame mode: ``FrameDetector`` (at the end).
 
 The post-forward stage (64-bit-key top-k, decode, NMS, row selection -- lib/rpn_util.py:1442-1555 in the reference)
 is latency-bound and leaves the chip mostly idle for ~0.35 ms per batch.  ``PipelinedDetector`` overlaps it with
@@ -38,7 +38,8 @@ import numpy as np
 import torch
 
 from . import _hip
-from .host.detect import detect_from_outputs, detect_from_planar, score_keys_planar, select_block, unwrap
+from .host.detect import (detect_from_outputs, detect_from_planar, detect_from_planar_mw, score_keys_planar, select_block,
+                          unwrap)
 from .host.refine import p2_arrays
 
 
@@ -309,3 +310,141 @@ class PipelinedDetector:
         self._pending = False
         res = (self._tblock if as_block else self._tblock[:, :-1], self._tcounts)
         return res + (self._trefined[:, :-1],) if self.refine else res
+
+
+# FrameDetector(topk_wgs=None): the multi-workgroup top-k up to this batch size, the single-workgroup kernel (one workgroup per
+# image) above it.  The rule for moving it is a measurement: the kernel leg of tools/latency_frame.py (profiles/latency_frame.jsonl)
+# has to show the multi-workgroup kernel's p50 below the single-workgroup one by more than the spread of the latter against itself.
+# NOT MEASURED yet ("Single frame"), so the default stays the single-workgroup kernel at every batch size.
+FRAME_MW_MAX_BATCH = 0
+
+
+class FrameDetector:
+    """Single-frame mode: ``detect(x)`` returns the detections of THIS x.
+
+    One captured hipGraph per instance holds the whole planar-form forward of the plan, the key pass (where the plan does not write
+    the sort keys itself), top-k + decode from the planar staging, NMS, row selection and -- ``refine=True`` -- the 3-D refinement
+    of ``test_kitti_3d`` (``m3d_refine_3d_ex``).  Nothing is deferred and there is no side stream: the only branches are the ones
+    ``run_plan`` emits under capture.  Results are those of ``detect_batch(net, x, conf, scale=...)`` (+ ``refine_detections``),
+    bit for bit (tests/test_gpu_frame_detector.py); a caller with a stream of batches who can take the result one batch late gets
+    more frames per second from ``PipelinedDetector``.
+
+    ``u8_frame=(h, w)``: x is uint8 BGR [B, h, w, 3] (device tensor or pinned host memory), copied on the current stream into the
+    device buffer the stem reads (padding, normalisation and BGR->RGB happen in its loads).
+    ``topk_wgs``: None = the library's choice (FRAME_MW_MAX_BATCH), 1 = the single-workgroup ``m3d_topk_decode_planar``, any other
+    positive value = workgroups per image of ``m3d_topk_decode_planar_mw``."""
+
+    def __init__(self, net, conf, height, width, batch=1, refine=False, score_thresh=0.75, step_r_init=0.3 * math.pi, r_lim=0.01,
+                 u8_frame=None, topk_wgs=None):
+        net = unwrap(net)
+        self.net, self.conf = net, conf
+        dev = next(net.parameters()).device
+        if dev.type != "cuda":
+            raise NotImplementedError("FrameDetector needs the module on a ROCm device")
+        if topk_wgs is not None and int(topk_wgs) < 1:
+            raise ValueError("topk_wgs must be None or a positive number of workgroups per image, got %r" % (topk_wgs,))
+        self.dev = dev
+        self.batch = int(batch)
+        self.refine = bool(refine)
+        self.u8_frame = None if u8_frame is None else (int(u8_frame[0]), int(u8_frame[1]))
+        if topk_wgs is None:
+            self.topk_wgs = 0 if self.batch <= FRAME_MW_MAX_BATCH else 1       # 0: m3d_topk_decode_planar_mw picks the count
+        else:
+            self.topk_wgs = int(topk_wgs)
+        self._rargs = (float(score_thresh), 1 if bool(getattr(conf, "hill_climbing", True)) else 0, float(step_r_init), float(r_lim))
+        self.eng = net.engine()
+        self.plan = self.eng.plan_for(self.batch, height, width)
+        if self.u8_frame is None:
+            self.input = torch.zeros(self.batch, 3, height, width, device=dev, dtype=torch.float32)
+        else:
+            fh, fw = self.u8_frame
+            if fh > height or fw > width:
+                raise RuntimeError("u8_frame %dx%d does not fit the padded size %dx%d" % (fh, fw, height, width))
+            self.input = torch.zeros(self.batch, fh, fw, 3, device=dev, dtype=torch.uint8)
+        assert self.plan.ops[-1][0] == "bundle_outputs"
+        self.n_fwd = len(self.plan.ops) - 1                 # planar form: everything in front of the output bundling
+        self._rois = net.rois.to(dev)
+        B = self.batch
+        self._scale = torch.ones(B, device=dev, dtype=torch.float32) if self.refine else None
+        if self.refine:
+            self._p2 = torch.zeros(B, 16, device=dev, dtype=torch.float64)
+            self._p2_inv = torch.zeros(B, 16, device=dev, dtype=torch.float64)
+            self._p2[:, 0::5] = 1.0
+            self._p2_inv[:, 0::5] = 1.0
+            self._clip = torch.zeros(B, 2, device=dev, dtype=torch.float32)
+        self._build()
+
+    def _run(self):
+        """Forward, keys, detection (and refinement) of what ``self.input`` holds, on the current stream."""
+        n = self.plan.named
+        if self.u8_frame is None:
+            n["input_ptr"][0] = self.input.data_ptr()
+            self.eng.run_plan(self.plan, 0, self.n_fwd)
+        else:
+            # the stem launch reads (pointer, h, w) of the uint8 frames when it is ISSUED: capture bakes them into the graph
+            n["input_u8"][:] = [self.input.data_ptr(), self.u8_frame[0], self.u8_frame[1]]
+            try:
+                self.eng.run_plan(self.plan, 0, self.n_fwd)
+            finally:
+                n["input_u8"][0] = 0
+        if not n.get("keys_by_select"):                     # else anchor_select wrote them on the way (engine: SELECT_KEYS)
+            score_keys_planar(self.eng, self.plan)
+        if self.topk_wgs == 1:
+            rows = detect_from_planar(self.eng, self.plan, self._rois, self.conf, self._scale)
+        else:
+            rows = detect_from_planar_mw(self.eng, self.plan, self._rois, self.conf, self._scale, self.topk_wgs or None)
+        block, counts = select_block(*rows, self.conf)
+        if not self.refine:
+            return block, counts, None
+        B, K1, _ = block.shape                              # K1 = kept rows + the count row (past counts[b]: refined to zeros)
+        out = torch.empty(B, K1, 16, device=self.dev, dtype=torch.float64)
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        _hip.check(_hip.lib().m3d_refine_3d_ex(block.data_ptr(), counts.data_ptr(), B, K1, self._p2.data_ptr(),
+                                               self._p2_inv.data_ptr(), None, self._clip.data_ptr(),
+                                               *self._rargs, out.data_ptr(), st))
+        return block, counts, out
+
+    def _build(self):
+        cap = torch.cuda.Stream(self.dev)
+        cap.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(cap), torch.no_grad():
+            self._run()                                     # warm-up outside capture: plan buffers, allocator pools, kernel attributes
+            torch.cuda.synchronize(self.dev)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=cap):
+                self._block, self._counts, self._refined = self._run()
+        torch.cuda.current_stream(self.dev).wait_stream(cap)
+
+    def _upload_meta(self, m):
+        B = self.batch
+        p2, p2_inv = p2_arrays(m["p2"], B)
+        self._p2.copy_(torch.from_numpy(p2.reshape(B, 16)))
+        self._p2_inv.copy_(torch.from_numpy(p2_inv.reshape(B, 16)))
+        scale = m.get("scale")
+        self._scale.copy_(torch.from_numpy(np.ones(B, np.float32) if scale is None else np.asarray(scale, np.float32).reshape(B)))
+        clip = m.get("clip_wh")
+        self._clip.copy_(torch.from_numpy(np.zeros((B, 2), np.float32) if clip is None
+                                          else np.asarray(clip, np.float32).reshape(B, 2)))
+
+    def detect(self, x, meta=None, as_block=False):
+        """Detections of x: (dets [B, nms_topN_post, 14], counts [B] int32), with refine=True also the refined rows
+        [B, nms_topN_post, 16] (float64).  Device tensors, queued on the current stream; the host is not synchronised.  The tensors
+        belong to the graph and are overwritten by the next detect(): clone what has to outlive it.
+        x: float32 [B, 3, height, width], or with u8_frame uint8 BGR [B, h, w, 3] on the device or in pinned host memory.
+        refine=True: meta = {"p2": [B, 4, 4] (or [4, 4]), "scale": [B] or None, "clip_wh": [B, 2] or None} of THIS x.
+        as_block: return the [B, nms_topN_post + 1, 14] gather block (m3dssd_amd.dist.gather_block) instead of dets."""
+        want = torch.uint8 if self.u8_frame is not None else torch.float32
+        if not torch.is_tensor(x) or x.dtype != want or tuple(x.shape) != tuple(self.input.shape):
+            raise RuntimeError("FrameDetector.detect: %s frames of shape %s expected, got %s %s"
+                               % (str(want).replace("torch.", ""), tuple(self.input.shape), getattr(x, "dtype", type(x).__name__),
+                                  tuple(getattr(x, "shape", ()))))
+        if self.u8_frame is not None and not (x.is_cuda or x.is_pinned()):
+            raise RuntimeError("FrameDetector.detect: the uint8 frames must be in pinned host memory (tensor.pin_memory()) or on the device")
+        if self.refine:
+            if meta is None:
+                raise RuntimeError("FrameDetector(refine=True).detect needs the frame's meta (p2, scale, clip_wh)")
+            self._upload_meta(meta)
+        self.input.copy_(x, non_blocking=True)
+        self.graph.replay()
+        res = (self._block if as_block else self._block[:, :-1], self._counts)
+        return res + (self._refined[:, :-1],) if self.refine else res
