@@ -161,6 +161,55 @@ __device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned *wave_t
     return base + inc - v;
 }
 
+// the 64-bit total order: descending score, ascending row among equal scores
+__device__ __forceinline__ unsigned long long topk_key(unsigned s, int row)
+{
+    return ((unsigned long long)s << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)row);
+}
+
+// A slice of one image's keys, in units of 16-byte groups of four keys (vec: R % 4 == 0, the image's R * 4 bytes are then 16-byte
+// aligned) or of single keys.  Image b's keys are cut into `wgs` such slices; slices past the end are empty.
+struct TopkSlice { int lo, hi; bool vec; };
+
+__device__ __forceinline__ TopkSlice topk_slice(int R, int wg, int wgs)
+{
+    TopkSlice s;
+    s.vec = (R & 3) == 0;
+    const int n = s.vec ? (R >> 2) : R;
+    const int per = (n + wgs - 1) / wgs;
+    s.lo = min(n, wg * per);
+    s.hi = min(n, s.lo + per);
+    return s;
+}
+
+// f(score bits, row) for every key of the slice, strided over the workgroup: the only place that knows about the 16-byte loads
+template <typename F>
+__device__ __forceinline__ void topk_for_keys(const unsigned int *sc, TopkSlice sl, int tid, F f)
+{
+    if (sl.vec) {
+        const u32x4 *sc4 = reinterpret_cast<const u32x4 *>(sc);
+        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) {
+            const u32x4 v = sc4[i];
+            f(v[0], 4 * i); f(v[1], 4 * i + 1); f(v[2], 4 * i + 2); f(v[3], 4 * i + 3);
+        }
+    } else {
+        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) f(sc[i], i);
+    }
+}
+
+// threshold bin of a 2048-bin histogram in LDS: the highest bin b with  count(digit > b) < need <= count(digit >= b)
+// -> *s_bin = b, *s_above = count(digit > b)  (both in LDS, valid for every thread on return)
+__device__ __forceinline__ void topk_find_bin(const unsigned *hist, unsigned need, unsigned *wave_tot, int tid, unsigned *s_bin,
+                                              unsigned *s_above)
+{
+    const int j0 = 2047 - 2 * tid, j1 = j0 - 1;                // two bins per thread, walking down from the top bin
+    const unsigned h0 = hist[j0], h1 = hist[j1];
+    const unsigned ex = block_excl_scan(h0 + h1, wave_tot, tid);
+    if (ex < need && need <= ex + h0) { *s_bin = (unsigned)j0; *s_above = ex; }
+    else if (ex + h0 < need && need <= ex + h0 + h1) { *s_bin = (unsigned)j1; *s_above = ex + h0; }
+    __syncthreads();
+}
+
 // MW: level 0 was done by topk_mw_hist_kernel / topk_mw_scatter_kernel (selected keys in a.mw_sel, candidates in cand[img][0])
 template <bool MW>
 __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
@@ -174,16 +223,6 @@ __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
     [[maybe_unused]] const unsigned int *sc = a.score_bits + (size_t)img * R;
     unsigned long long *candA = a.cand + (size_t)img * 2 * R, *candB = candA + R;
 
-    // threshold bin of a 2048-bin histogram: the highest bin b with  count(digit > b) < need <= count(digit >= b)
-    auto find_bin = [&](unsigned need) {
-        const int j0 = 2047 - 2 * tid, j1 = j0 - 1;            // two bins per thread, walking down from the top bin
-        const unsigned h0 = hist[j0], h1 = hist[j1];
-        const unsigned ex = block_excl_scan(h0 + h1, wave_tot, tid);
-        if (ex < need && need <= ex + h0) { s_bin = (unsigned)j0; s_above = ex; }
-        else if (ex + h0 < need && need <= ex + h0 + h1) { s_bin = (unsigned)j1; s_above = ex + h0; }
-        __syncthreads();
-    };
-
     unsigned need = (unsigned)k;
     if (tid == 0) { s_nsel = 0; s_ncand = 0; }
     for (int i = tid; i < 2048; i += TOPK_NT) hist[i] = 0;
@@ -191,41 +230,19 @@ __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
     // ---- level 0: top 11 bits of the score over all R rows -----------------------------------------------------------
     unsigned ncand;
     if constexpr (!MW) {
-        const int R4 = R >> 2;
-        const u32x4 *sc4 = reinterpret_cast<const u32x4 *>(sc);    // R*4 bytes per image: 16-byte aligned when R % 4 == 0
-        const bool vec = (R & 3) == 0;
-        if (vec) {
-            for (int i = tid; i < R4; i += TOPK_NT) {
-                const u32x4 v = sc4[i];
-                atomicAdd(&hist[v[0] >> 21], 1u);
-                atomicAdd(&hist[v[1] >> 21], 1u);
-                atomicAdd(&hist[v[2] >> 21], 1u);
-                atomicAdd(&hist[v[3] >> 21], 1u);
-            }
-        } else {
-            for (int i = tid; i < R; i += TOPK_NT) atomicAdd(&hist[sc[i] >> 21], 1u);
-        }
+        const TopkSlice all = topk_slice(R, 0, 1);                 // the whole image
+        topk_for_keys(sc, all, tid, [&](unsigned s, int) { atomicAdd(&hist[s >> 21], 1u); });
         __syncthreads();
-        find_bin(need);
-        {
-            const unsigned bin = s_bin;
-            auto put = [&](unsigned s, int row) {
-                const unsigned d = s >> 21;
-                if (d >= bin) {
-                    const unsigned long long key = ((unsigned long long)s << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)row);
-                    if (d > bin) sel[atomicAdd(&s_nsel, 1u)] = key;
-                    else candA[atomicAdd(&s_ncand, 1u)] = key;
-                }
-            };
-            if (vec) {
-                for (int i = tid; i < R4; i += TOPK_NT) {
-                    const u32x4 v = sc4[i];
-                    put(v[0], 4 * i); put(v[1], 4 * i + 1); put(v[2], 4 * i + 2); put(v[3], 4 * i + 3);
-                }
-            } else {
-                for (int i = tid; i < R; i += TOPK_NT) put(sc[i], i);
+        topk_find_bin(hist, need, wave_tot, tid, &s_bin, &s_above);
+        const unsigned bin = s_bin;
+        topk_for_keys(sc, all, tid, [&](unsigned s, int row) {
+            const unsigned d = s >> 21;
+            if (d >= bin) {
+                const unsigned long long key = topk_key(s, row);
+                if (d > bin) sel[atomicAdd(&s_nsel, 1u)] = key;
+                else candA[atomicAdd(&s_ncand, 1u)] = key;
             }
-        }
+        });
         __threadfence_block();
         __syncthreads();
         need -= s_above;
@@ -252,7 +269,7 @@ __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
         __syncthreads();
         for (unsigned i = tid; i < ncand; i += TOPK_NT) atomicAdd(&hist[(unsigned)(candA[i] >> sh) & mk], 1u);
         __syncthreads();
-        find_bin(need);
+        topk_find_bin(hist, need, wave_tot, tid, &s_bin, &s_above);
         const unsigned bin = s_bin;
         for (unsigned i = tid; i < ncand; i += TOPK_NT) {
             const unsigned long long key = candA[i];
@@ -342,6 +359,50 @@ extern "C" long long m3d_topk_decode_workspace_bytes(int B, int R)
     return (long long)B * 2 * R * (long long)sizeof(unsigned long long);
 }
 
+static long long topk_mw_align(long long v) { return (v + 15) & ~15LL; }
+
+extern "C" long long m3d_topk_decode_mw_workspace_bytes(int B, int R, int k)
+{
+    if (B < 1 || R < 1 || k < 1) return -1;
+    // cand [B][2][R] keys (the layout of m3d_topk_decode_workspace_bytes), selected keys [B][k], histogram [B][2048], counters [B][2]
+    return m3d_topk_decode_workspace_bytes(B, R) + (long long)B * k * (long long)sizeof(unsigned long long)
+           + (long long)B * 2048 * (long long)sizeof(unsigned) + topk_mw_align((long long)B * 2 * (long long)sizeof(unsigned));
+}
+
+// The argument checks, the workspace check and the TopkArgs of every m3d_topk_decode* entry point (`name`: the one in the messages).
+//   bundled (planar = false): prob / b2 / b3 = prob, bbox_2d, bbox_3d [B][R][*], n0 = R, n1 unused
+//   planar:                   prob / b2 = cls planar, box planar, b3 unused, (n0, n1) = (A, HW)
+//   mw: the workspace rule and the mw_* pointers of the multi-workgroup form
+static int topk_args(TopkArgs &a, bool planar, bool mw, const char *name, const unsigned int *score_bits, const float *prob,
+                     const float *b2, const float *b3, const float *rois, const float *anchors, const float *means,
+                     const float *stds, const float *scale, float *aboxes, int *rows_out, void *workspace, long long workspace_bytes,
+                     int B, int n0, int n1, int k)
+{
+    a = TopkArgs{};
+    M3D_REQUIRE(score_bits && prob && b2 && (planar || b3) && rois && anchors && means && stds && aboxes && workspace,
+                "%s: null pointer", name);
+    if (!planar) n1 = 1;
+    M3D_REQUIRE(B >= 1 && n0 >= 1 && n1 >= 1 && (long long)n0 * n1 < (1 << 22), "%s: %s (%lld) must be in [1, 2^22)", name,
+                planar ? "A * HW" : "R", (long long)n0 * n1);
+    const int R = n0 * n1;
+    M3D_REQUIRE(k >= 1 && k <= R && k <= TOPK_MAXK, "%s: k (%d) must be in [1, min(R, %d)]", name, k, TOPK_MAXK);
+    const long long need = mw ? m3d_topk_decode_mw_workspace_bytes(B, R, k) : m3d_topk_decode_workspace_bytes(B, R);
+    if (workspace_bytes < need) {
+        m3d_set_error("%s: workspace of %lld bytes, %lld needed", name, workspace_bytes, need);
+        return M3D_E_WORKSPACE;
+    }
+    a.score_bits = score_bits; a.prob = prob; a.b2 = b2; a.b3 = b3; a.rois = rois; a.anchors = anchors;
+    a.means = means; a.stds = stds; a.aboxes = aboxes; a.rows_out = rows_out; a.cand = (unsigned long long *)workspace;
+    a.scale = scale; a.R = R; a.k = k;
+    if (planar) { a.A = n0; a.HW = n1; }
+    if (mw) {
+        a.mw_sel = a.cand + (size_t)B * 2 * R;
+        a.mw_hist = reinterpret_cast<unsigned *>(a.mw_sel + (size_t)B * k);
+        a.mw_cnt = a.mw_hist + (size_t)B * 2048;
+    }
+    return M3D_OK;
+}
+
 extern "C" int m3d_topk_decode(const unsigned int *score_bits, const float *prob, const float *bbox_2d, const float *bbox_3d,
                                const float *rois, const float *anchors, const float *means, const float *stds, float *aboxes,
                                int *rows_out, void *workspace, long long workspace_bytes, int B, int R, int k,
@@ -356,19 +417,10 @@ extern "C" int m3d_topk_decode_scaled(const unsigned int *score_bits, const floa
                                       const float *scale, float *aboxes, int *rows_out, void *workspace, long long workspace_bytes,
                                       int B, int R, int k, m3d_stream_t stream)
 {
-    M3D_REQUIRE(score_bits && prob && bbox_2d && bbox_3d && rois && anchors && means && stds && aboxes && workspace,
-                "topk_decode: null pointer");
-    M3D_REQUIRE(B >= 1 && R >= 1 && R < (1 << 22), "topk_decode: R (%d) must be in [1, 2^22)", R);
-    M3D_REQUIRE(k >= 1 && k <= R && k <= TOPK_MAXK, "topk_decode: k (%d) must be in [1, min(R, %d)]", k, TOPK_MAXK);
-    if (workspace_bytes < m3d_topk_decode_workspace_bytes(B, R)) {
-        m3d_set_error("topk_decode: workspace of %lld bytes, %lld needed", workspace_bytes, m3d_topk_decode_workspace_bytes(B, R));
-        return M3D_E_WORKSPACE;
-    }
     TopkArgs a;
-    a.score_bits = score_bits; a.prob = prob; a.b2 = bbox_2d; a.b3 = bbox_3d; a.rois = rois; a.anchors = anchors;
-    a.means = means; a.stds = stds; a.aboxes = aboxes; a.rows_out = rows_out; a.cand = (unsigned long long *)workspace;
-    a.R = R; a.k = k; a.scale = scale; a.A = 0; a.HW = 0; a.mw_sel = nullptr; a.mw_hist = nullptr; a.mw_cnt = nullptr;
-    return topk_launch<false>(a, B, (hipStream_t)stream);
+    const int rc = topk_args(a, false, false, "topk_decode", score_bits, prob, bbox_2d, bbox_3d, rois, anchors, means, stds, scale,
+                             aboxes, rows_out, workspace, workspace_bytes, B, R, 0, k);
+    return rc != M3D_OK ? rc : topk_launch<false>(a, B, (hipStream_t)stream);
 }
 
 extern "C" int m3d_topk_decode_planar(const unsigned int *score_bits, const float *cls_planar, const float *box_planar,
@@ -376,25 +428,15 @@ extern "C" int m3d_topk_decode_planar(const unsigned int *score_bits, const floa
                                       const float *scale, float *aboxes, int *rows_out, void *workspace, long long workspace_bytes,
                                       int B, int A, int HW, int k, m3d_stream_t stream)
 {
-    M3D_REQUIRE(score_bits && cls_planar && box_planar && rois && anchors && means && stds && aboxes && workspace,
-                "topk_decode_planar: null pointer");
-    M3D_REQUIRE(B >= 1 && A >= 1 && HW >= 1 && (long long)A * HW < (1 << 22), "topk_decode_planar: A * HW must be in [1, 2^22)");
-    const int R = A * HW;
-    M3D_REQUIRE(k >= 1 && k <= R && k <= TOPK_MAXK, "topk_decode_planar: k (%d) must be in [1, min(R, %d)]", k, TOPK_MAXK);
-    if (workspace_bytes < m3d_topk_decode_workspace_bytes(B, R)) {
-        m3d_set_error("topk_decode_planar: workspace of %lld bytes, %lld needed", workspace_bytes, m3d_topk_decode_workspace_bytes(B, R));
-        return M3D_E_WORKSPACE;
-    }
     TopkArgs a;
-    a.score_bits = score_bits; a.prob = cls_planar; a.b2 = box_planar; a.b3 = nullptr; a.rois = rois; a.anchors = anchors;
-    a.means = means; a.stds = stds; a.aboxes = aboxes; a.rows_out = rows_out; a.cand = (unsigned long long *)workspace;
-    a.R = R; a.k = k; a.scale = scale; a.A = A; a.HW = HW; a.mw_sel = nullptr; a.mw_hist = nullptr; a.mw_cnt = nullptr;
-    return topk_launch<false>(a, B, (hipStream_t)stream);
+    const int rc = topk_args(a, true, false, "topk_decode_planar", score_bits, cls_planar, box_planar, nullptr, rois, anchors, means,
+                             stds, scale, aboxes, rows_out, workspace, workspace_bytes, B, A, HW, k);
+    return rc != M3D_OK ? rc : topk_launch<false>(a, B, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Multi-workgroup level 0 (one frame on a 256-CU chip: one workgroup per image reads all R keys twice from a single CU).
-// Image b's keys are cut into `wgs` slices of whole 16-byte groups (single keys when R % 4 != 0); slices past the end are empty.
+// Image b's keys are cut into `wgs` slices (topk_slice).
 //   zero    : global histogram and the two list counters of every image (nothing carries over from an earlier call)
 //   hist    : per-slice LDS histogram of the top 11 score bits, non-zero bins added into the image's global histogram
 //   scatter : every workgroup finds the threshold bin from the global histogram, counts its slice's keys above / inside the
@@ -405,19 +447,6 @@ extern "C" int m3d_topk_decode_planar(const unsigned int *score_bits, const floa
 // library's choice for wgs_per_image = 0: one slice per four CUs, 1 080 16-byte groups per slice at R = 276 480.  To be replaced by the
 // best of the sweep of tools/latency_frame.py's kernel leg (B = 1, R = 276 480, k = 3000; profiles/latency_frame.jsonl): NOT MEASURED yet.
 #define TOPK_MW_DEFAULT_WGS 64
-
-struct TopkSlice { int lo, hi; bool vec; };
-
-__device__ __forceinline__ TopkSlice topk_mw_slice(int R, int wg, int wgs)
-{
-    TopkSlice s;
-    s.vec = (R & 3) == 0;
-    const int n = s.vec ? (R >> 2) : R;                    // units: 16-byte groups of four keys, or single keys
-    const int per = (n + wgs - 1) / wgs;
-    s.lo = min(n, wg * per);
-    s.hi = min(n, s.lo + per);
-    return s;
-}
 
 __global__ __launch_bounds__(TOPK_NT) void topk_mw_zero_kernel(TopkArgs a)
 {
@@ -430,23 +459,12 @@ __global__ __launch_bounds__(TOPK_NT) void topk_mw_hist_kernel(TopkArgs a)
 {
     __shared__ unsigned hist[2048];
     const int img = blockIdx.y, tid = threadIdx.x;
-    const TopkSlice sl = topk_mw_slice(a.R, blockIdx.x, gridDim.x);
+    const TopkSlice sl = topk_slice(a.R, blockIdx.x, gridDim.x);
     if (sl.lo >= sl.hi) return;                            // (uniform over the workgroup)
     const unsigned int *sc = a.score_bits + (size_t)img * a.R;
     for (int i = tid; i < 2048; i += TOPK_NT) hist[i] = 0;
     __syncthreads();
-    if (sl.vec) {
-        const u32x4 *sc4 = reinterpret_cast<const u32x4 *>(sc);
-        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) {
-            const u32x4 v = sc4[i];
-            atomicAdd(&hist[v[0] >> 21], 1u);
-            atomicAdd(&hist[v[1] >> 21], 1u);
-            atomicAdd(&hist[v[2] >> 21], 1u);
-            atomicAdd(&hist[v[3] >> 21], 1u);
-        }
-    } else {
-        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) atomicAdd(&hist[sc[i] >> 21], 1u);
-    }
+    topk_for_keys(sc, sl, tid, [&](unsigned s, int) { atomicAdd(&hist[s >> 21], 1u); });
     __syncthreads();
     unsigned *gh = a.mw_hist + (size_t)img * 2048;
     for (int i = tid; i < 2048; i += TOPK_NT) {
@@ -459,42 +477,25 @@ __global__ __launch_bounds__(TOPK_NT) void topk_mw_scatter_kernel(TopkArgs a)
 {
     __shared__ unsigned hist[2048];
     __shared__ unsigned wave_tot[16];
-    __shared__ unsigned s_bin, s_csel, s_ccand, s_bsel, s_bcand, s_isel, s_icand;
+    __shared__ unsigned s_bin, s_above, s_csel, s_ccand, s_bsel, s_bcand, s_isel, s_icand;
     const int img = blockIdx.y, tid = threadIdx.x;
     const int R = a.R, k = a.k;
-    const TopkSlice sl = topk_mw_slice(R, blockIdx.x, gridDim.x);
+    const TopkSlice sl = topk_slice(R, blockIdx.x, gridDim.x);
     if (sl.lo >= sl.hi) return;
     const unsigned int *sc = a.score_bits + (size_t)img * R;
-    const u32x4 *sc4 = reinterpret_cast<const u32x4 *>(sc);
     const unsigned *gh = a.mw_hist + (size_t)img * 2048;
     for (int i = tid; i < 2048; i += TOPK_NT) hist[i] = gh[i];
     if (tid == 0) { s_csel = 0; s_ccand = 0; s_isel = 0; s_icand = 0; }
     __syncthreads();
-    {   // threshold bin: the highest bin b with  count(digit > b) < k <= count(digit >= b)  (as topk_decode_kernel finds it)
-        const unsigned need = (unsigned)k;
-        const int j0 = 2047 - 2 * tid, j1 = j0 - 1;
-        const unsigned h0 = hist[j0], h1 = hist[j1];
-        const unsigned ex = block_excl_scan(h0 + h1, wave_tot, tid);
-        if (ex < need && need <= ex + h0) s_bin = (unsigned)j0;
-        else if (ex + h0 < need && need <= ex + h0 + h1) s_bin = (unsigned)j1;
-        __syncthreads();
-    }
+    topk_find_bin(hist, (unsigned)k, wave_tot, tid, &s_bin, &s_above);      // (the finishing launch counts the keys above the bin itself)
     const unsigned bin = s_bin;
     // how many keys of the slice go to either list
     unsigned csel = 0, ccand = 0;
-    auto count = [&](unsigned s) {
+    topk_for_keys(sc, sl, tid, [&](unsigned s, int) {
         const unsigned d = s >> 21;
         csel += d > bin;
         ccand += d == bin;
-    };
-    if (sl.vec) {
-        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) {
-            const u32x4 v = sc4[i];
-            count(v[0]); count(v[1]); count(v[2]); count(v[3]);
-        }
-    } else {
-        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) count(sc[i]);
-    }
+    });
     if (csel) atomicAdd(&s_csel, csel);
     if (ccand) atomicAdd(&s_ccand, ccand);
     __syncthreads();
@@ -507,10 +508,10 @@ __global__ __launch_bounds__(TOPK_NT) void topk_mw_scatter_kernel(TopkArgs a)
     const unsigned bsel = s_bsel, bcand = s_bcand;
     unsigned long long *gsel = a.mw_sel + (size_t)img * k;
     unsigned long long *cand = a.cand + (size_t)img * 2 * R;
-    auto put = [&](unsigned s, int row) {
+    topk_for_keys(sc, sl, tid, [&](unsigned s, int row) {
         const unsigned d = s >> 21;
         if (d >= bin) {
-            const unsigned long long key = ((unsigned long long)s << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)row);
+            const unsigned long long key = topk_key(s, row);
             if (d > bin) {
                 const unsigned at = bsel + atomicAdd(&s_isel, 1u);
                 if (at < (unsigned)k) gsel[at] = key;      // (count(digit > bin) < k: the bound never binds)
@@ -519,25 +520,7 @@ __global__ __launch_bounds__(TOPK_NT) void topk_mw_scatter_kernel(TopkArgs a)
                 if (at < (unsigned)R) cand[at] = key;
             }
         }
-    };
-    if (sl.vec) {
-        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) {
-            const u32x4 v = sc4[i];
-            put(v[0], 4 * i); put(v[1], 4 * i + 1); put(v[2], 4 * i + 2); put(v[3], 4 * i + 3);
-        }
-    } else {
-        for (int i = sl.lo + tid; i < sl.hi; i += TOPK_NT) put(sc[i], i);
-    }
-}
-
-static long long topk_mw_align(long long v) { return (v + 15) & ~15LL; }
-
-extern "C" long long m3d_topk_decode_mw_workspace_bytes(int B, int R, int k)
-{
-    if (B < 1 || R < 1 || k < 1) return -1;
-    // cand [B][2][R] keys (the layout of m3d_topk_decode_workspace_bytes), selected keys [B][k], histogram [B][2048], counters [B][2]
-    return m3d_topk_decode_workspace_bytes(B, R) + (long long)B * k * (long long)sizeof(unsigned long long)
-           + (long long)B * 2048 * (long long)sizeof(unsigned) + topk_mw_align((long long)B * 2 * (long long)sizeof(unsigned));
+    });
 }
 
 extern "C" int m3d_topk_decode_planar_mw(const unsigned int *score_bits, const float *cls_planar, const float *box_planar,
@@ -546,30 +529,17 @@ extern "C" int m3d_topk_decode_planar_mw(const unsigned int *score_bits, const f
                                          long long workspace_bytes, int B, int A, int HW, int k, int wgs_per_image,
                                          m3d_stream_t stream)
 {
-    M3D_REQUIRE(score_bits && cls_planar && box_planar && rois && anchors && means && stds && aboxes && workspace,
-                "topk_decode_planar_mw: null pointer");
-    M3D_REQUIRE(B >= 1 && A >= 1 && HW >= 1 && (long long)A * HW < (1 << 22), "topk_decode_planar_mw: A * HW must be in [1, 2^22)");
-    const int R = A * HW;
-    M3D_REQUIRE(k >= 1 && k <= R && k <= TOPK_MAXK, "topk_decode_planar_mw: k (%d) must be in [1, min(R, %d)]", k, TOPK_MAXK);
     M3D_REQUIRE(wgs_per_image >= 0 && wgs_per_image <= TOPK_MW_MAX_WGS,
                 "topk_decode_planar_mw: wgs_per_image (%d) must be in [0, %d] (0 = library's choice)", wgs_per_image, TOPK_MW_MAX_WGS);
-    if (workspace_bytes < m3d_topk_decode_mw_workspace_bytes(B, R, k)) {
-        m3d_set_error("topk_decode_planar_mw: workspace of %lld bytes, %lld needed", workspace_bytes,
-                      m3d_topk_decode_mw_workspace_bytes(B, R, k));
-        return M3D_E_WORKSPACE;
-    }
+    TopkArgs a;
+    const int rc = topk_args(a, true, true, "topk_decode_planar_mw", score_bits, cls_planar, box_planar, nullptr, rois, anchors, means,
+                             stds, scale, aboxes, rows_out, workspace, workspace_bytes, B, A, HW, k);
+    if (rc != M3D_OK) return rc;
     int wgs = wgs_per_image;
     if (wgs == 0) {                                        // no more slices than there are workgroup-sized pieces of the image
-        const int units = (R & 3) ? R : (R >> 2);
+        const int units = (a.R & 3) ? a.R : (a.R >> 2);
         wgs = max(1, min(TOPK_MW_DEFAULT_WGS, cdiv(units, TOPK_NT)));
     }
-    TopkArgs a;
-    a.score_bits = score_bits; a.prob = cls_planar; a.b2 = box_planar; a.b3 = nullptr; a.rois = rois; a.anchors = anchors;
-    a.means = means; a.stds = stds; a.aboxes = aboxes; a.rows_out = rows_out; a.cand = (unsigned long long *)workspace;
-    a.R = R; a.k = k; a.scale = scale; a.A = A; a.HW = HW;
-    a.mw_sel = a.cand + (size_t)B * 2 * R;
-    a.mw_hist = reinterpret_cast<unsigned *>(a.mw_sel + (size_t)B * k);
-    a.mw_cnt = a.mw_hist + (size_t)B * 2048;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(topk_mw_zero_kernel, dim3(B), dim3(TOPK_NT), 0, st, a);
     M3D_LAUNCH_CHECK();

@@ -59,87 +59,71 @@ def _scale_tensor(scale, B, dev):
     return torch.from_numpy(arr).to(dev)
 
 
-def detect_from_outputs(eng, plan, prob, bbox_2d, bbox_3d, rois, conf, scale=None):
-    """top-N-pre select + decode -> NMS on the engine's output buffers (current stream of their device).
-    -> (aboxes [B, n_pre, 14] score-sorted, keep [B, n_pre] int32 positions, num_keep [B] int32).
-    scale: per-image test-time scale factors (device float32 [B]) -- the boxes are divided by them BEFORE the NMS like the
-    reference's im_detect_3d does (lib/rpn_util.py:1504-1506)."""
+def _topk_nms(dev, B, n_pre, conf, tk_bytes, topk):
+    """The top-k + decode launch ``topk(aboxes, workspace, stream)`` (workspace rule: ``tk_bytes``), then the NMS, on the current
+    stream of ``dev`` -> (aboxes [B, n_pre, 14] score-sorted, keep [B, n_pre] int32 positions, num_keep [B] int32)."""
     L = _hip.lib()
-    dev = prob.device
-    B, R = prob.shape[0], prob.shape[1]
-    bits = plan.named["score_bits"]
-    n_pre = min(int(conf.nms_topN_pre), R)
-    P = eng.P
     with torch.cuda.device(dev):
         st = _stream(dev)
         aboxes = torch.empty(B, n_pre, 14, device=dev, dtype=torch.float32)
         keep = torch.empty(B, n_pre, device=dev, dtype=torch.int32)
         num = torch.empty(B, device=dev, dtype=torch.int32)
-        tk_bytes = L.m3d_topk_decode_workspace_bytes(B, R)
         ws = torch.empty(max(tk_bytes, L.m3d_nms_workspace_bytes(B, n_pre)), device=dev, dtype=torch.uint8)
-        _hip.check(L.m3d_topk_decode_scaled(bits.data_ptr(), prob.data_ptr(), bbox_2d.data_ptr(), bbox_3d.data_ptr(),
-                                            rois.data_ptr(), P["anchors"].data_ptr(), P["means"].data_ptr(),
-                                            P["stds"].data_ptr(), None if scale is None else scale.data_ptr(), aboxes.data_ptr(),
-                                            None, ws.data_ptr(), tk_bytes, B, R, n_pre, st))
+        _hip.check(topk(aboxes.data_ptr(), ws.data_ptr(), st))
         _hip.check(L.m3d_nms_sorted_dev(aboxes.data_ptr(), B, n_pre, 14, float(conf.nms_thres), ws.data_ptr(),
                                         keep.data_ptr(), num.data_ptr(), st))
     return aboxes, keep, num
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def detect_from_outputs(eng, plan, prob, bbox_2d, bbox_3d, rois, conf, scale=None):
+    """top-N-pre select + decode -> NMS on the engine's output buffers (current stream of their device).
+    -> (aboxes [B, n_pre, 14] score-sorted, keep [B, n_pre] int32 positions, num_keep [B] int32).
+    scale: per-image test-time scale factors (device float32 [B]) -- the boxes are divided by them BEFORE the NMS like the
+    reference's im_detect_3d does (lib/rpn_util.py:1504-1506)."""
+    L, P = _hip.lib(), eng.P
+    B, R = prob.shape[0], prob.shape[1]
+    k = min(int(conf.nms_topN_pre), R)
+    nb = L.m3d_topk_decode_workspace_bytes(B, R)
+    head = (plan.named["score_bits"].data_ptr(), prob.data_ptr(), bbox_2d.data_ptr(), bbox_3d.data_ptr(), rois.data_ptr(),
+            P["anchors"].data_ptr(), P["means"].data_ptr(), P["stds"].data_ptr(), _ptr(scale))
+    return _topk_nms(prob.device, B, k, conf, nb,
+                     lambda aboxes, ws, st: L.m3d_topk_decode_scaled(*head, aboxes, None, ws, nb, B, R, k, st))
+
+
+def _detect_planar(eng, plan, rois, conf, scale, wgs):
+    """wgs: None = ``m3d_topk_decode_planar``; else the workgroups per image of ``m3d_topk_decode_planar_mw`` (0 = its choice)."""
+    L, P = _hip.lib(), eng.P
+    cls_pl, box_pl, bits = plan.named["cls_planar"], plan.named["box_planar"], plan.named["score_bits"]
+    B, R = bits.shape[0], bits.shape[1]
+    A = eng.A
+    k = min(int(conf.nms_topN_pre), R)
+    head = (bits.data_ptr(), cls_pl.data_ptr(), box_pl.data_ptr(), rois.data_ptr(), P["anchors"].data_ptr(), P["means"].data_ptr(),
+            P["stds"].data_ptr(), _ptr(scale))
+    if wgs is None:
+        nb = L.m3d_topk_decode_workspace_bytes(B, R)
+        return _topk_nms(bits.device, B, k, conf, nb,
+                         lambda aboxes, ws, st: L.m3d_topk_decode_planar(*head, aboxes, None, ws, nb, B, A, R // A, k, st))
+    nb = L.m3d_topk_decode_mw_workspace_bytes(B, R, k)
+    return _topk_nms(bits.device, B, k, conf, nb,
+                     lambda aboxes, ws, st: L.m3d_topk_decode_planar_mw(*head, aboxes, None, ws, nb, B, A, R // A, k, wgs, st))
 
 
 def detect_from_planar(eng, plan, rois, conf, scale=None):
     """detect_from_outputs without the bundled tensors: the sort keys come from ``m3d_score_keys_planar`` (run behind the forward
     in place of ``m3d_bundle_outputs``) and the top-N-pre rows are decoded straight from the planar staging the heads write
     (``m3d_topk_decode_planar``).  Same rows, same bits (tests/test_gpu_detect.py); 5.5 MB per image instead of 38."""
-    L = _hip.lib()
-    cls_pl, box_pl, bits = plan.named["cls_planar"], plan.named["box_planar"], plan.named["score_bits"]
-    dev = bits.device
-    B, R = bits.shape[0], bits.shape[1]
-    A = eng.A
-    HW = R // A
-    n_pre = min(int(conf.nms_topN_pre), R)
-    P = eng.P
-    with torch.cuda.device(dev):
-        st = _stream(dev)
-        aboxes = torch.empty(B, n_pre, 14, device=dev, dtype=torch.float32)
-        keep = torch.empty(B, n_pre, device=dev, dtype=torch.int32)
-        num = torch.empty(B, device=dev, dtype=torch.int32)
-        tk_bytes = L.m3d_topk_decode_workspace_bytes(B, R)
-        ws = torch.empty(max(tk_bytes, L.m3d_nms_workspace_bytes(B, n_pre)), device=dev, dtype=torch.uint8)
-        _hip.check(L.m3d_topk_decode_planar(bits.data_ptr(), cls_pl.data_ptr(), box_pl.data_ptr(), rois.data_ptr(),
-                                            P["anchors"].data_ptr(), P["means"].data_ptr(), P["stds"].data_ptr(),
-                                            None if scale is None else scale.data_ptr(), aboxes.data_ptr(), None, ws.data_ptr(),
-                                            tk_bytes, B, A, HW, n_pre, st))
-        _hip.check(L.m3d_nms_sorted_dev(aboxes.data_ptr(), B, n_pre, 14, float(conf.nms_thres), ws.data_ptr(),
-                                        keep.data_ptr(), num.data_ptr(), st))
-    return aboxes, keep, num
+    return _detect_planar(eng, plan, rois, conf, scale, None)
 
 
 def detect_from_planar_mw(eng, plan, rois, conf, scale=None, wgs=None):
     """detect_from_planar with the multi-workgroup top-k (``m3d_topk_decode_planar_mw``): the form for one frame (or a few), where
     one workgroup per image leaves the chip idle behind the forward.  Same rows, same bits (tests/test_gpu_frame_detector.py).
     wgs: workgroups per image for the pass over all rows; None = the library's choice."""
-    L = _hip.lib()
-    cls_pl, box_pl, bits = plan.named["cls_planar"], plan.named["box_planar"], plan.named["score_bits"]
-    dev = bits.device
-    B, R = bits.shape[0], bits.shape[1]
-    A = eng.A
-    HW = R // A
-    n_pre = min(int(conf.nms_topN_pre), R)
-    P = eng.P
-    with torch.cuda.device(dev):
-        st = _stream(dev)
-        aboxes = torch.empty(B, n_pre, 14, device=dev, dtype=torch.float32)
-        keep = torch.empty(B, n_pre, device=dev, dtype=torch.int32)
-        num = torch.empty(B, device=dev, dtype=torch.int32)
-        tk_bytes = L.m3d_topk_decode_mw_workspace_bytes(B, R, n_pre)
-        ws = torch.empty(max(tk_bytes, L.m3d_nms_workspace_bytes(B, n_pre)), device=dev, dtype=torch.uint8)
-        _hip.check(L.m3d_topk_decode_planar_mw(bits.data_ptr(), cls_pl.data_ptr(), box_pl.data_ptr(), rois.data_ptr(),
-                                               P["anchors"].data_ptr(), P["means"].data_ptr(), P["stds"].data_ptr(),
-                                               None if scale is None else scale.data_ptr(), aboxes.data_ptr(), None, ws.data_ptr(),
-                                               tk_bytes, B, A, HW, n_pre, 0 if wgs is None else int(wgs), st))
-        _hip.check(L.m3d_nms_sorted_dev(aboxes.data_ptr(), B, n_pre, 14, float(conf.nms_thres), ws.data_ptr(),
-                                        keep.data_ptr(), num.data_ptr(), st))
-    return aboxes, keep, num
+    return _detect_planar(eng, plan, rois, conf, scale, 0 if wgs is None else int(wgs))
 
 
 def score_keys_planar(eng, plan):

@@ -28,6 +28,47 @@ def p2_arrays(p2, B):
     return np.array(p2, dtype=np.float64, order="C"), np.ascontiguousarray(np.stack([np.linalg.inv(m) for m in p2]))
 
 
+class RefineMeta:
+    """The per-batch device buffers the refinement of a captured graph reads: p2, its inverse, the test-time scale factors and the
+    clip sizes.  Identity / 1 / "not clipped" until ``upload``."""
+
+    def __init__(self, batch, dev):
+        self.batch = int(batch)
+        self.p2 = torch.zeros(batch, 16, device=dev, dtype=torch.float64)
+        self.p2_inv = torch.zeros(batch, 16, device=dev, dtype=torch.float64)
+        self.p2[:, 0::5] = 1.0
+        self.p2_inv[:, 0::5] = 1.0
+        self.scale = torch.ones(batch, device=dev, dtype=torch.float32)
+        self.clip = torch.zeros(batch, 2, device=dev, dtype=torch.float32)
+
+    def upload(self, meta):
+        """meta = {"p2": [B, 4, 4] (or [4, 4]), "scale": [B] or None, "clip_wh": [B, 2] or None} (host) -> the device buffers."""
+        B = self.batch
+        p2, p2_inv = p2_arrays(meta["p2"], B)
+        self.p2.copy_(torch.from_numpy(p2.reshape(B, 16)))
+        self.p2_inv.copy_(torch.from_numpy(p2_inv.reshape(B, 16)))
+        scale = meta.get("scale")
+        self.scale.copy_(torch.from_numpy(np.ones(B, np.float32) if scale is None else np.asarray(scale, np.float32).reshape(B)))
+        clip = meta.get("clip_wh")
+        self.clip.copy_(torch.from_numpy(np.zeros((B, 2), np.float32) if clip is None
+                                         else np.asarray(clip, np.float32).reshape(B, 2)))
+
+
+def refine_rows(block, counts, p2, p2_inv, scale, clip, score_thresh, hill_climbing, step_r_init, r_lim):
+    """The launch of refine_detections on device tensors (current stream of their device): block [B, K, 14] float32, counts [B]
+    int32, p2 / p2_inv [B, 16] float64, scale [B] float32 or None, clip [B, 2] float32 or None -> float64 [B, K, 16]."""
+    B, K, _ = block.shape
+    dev = block.device
+    out = torch.empty(B, K, 16, device=dev, dtype=torch.float64)
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.lib().m3d_refine_3d_ex(block.data_ptr(), counts.data_ptr(), B, K, p2.data_ptr(), p2_inv.data_ptr(),
+                                               None if scale is None else scale.data_ptr(),
+                                               None if clip is None else clip.data_ptr(), float(score_thresh),
+                                               1 if hill_climbing else 0, float(step_r_init), float(r_lim), out.data_ptr(), st))
+    return out
+
+
 def refine_detections(dets, counts, p2, score_thresh=0.75, hill_climbing=True, step_r_init=0.3 * math.pi, r_lim=0.01,
                       scale=None, clip_wh=None):
     """dets [B, K, 14] float32 device rows (detect_batch / im_detect_3d format), counts [B] int32 device, p2 [B, 4, 4] (or
@@ -39,23 +80,13 @@ def refine_detections(dets, counts, p2, score_thresh=0.75, hill_climbing=True, s
         raise NotImplementedError("refine_detections: ROCm device tensors expected")
     if dets.dim() != 3 or dets.shape[2] != 14 or dets.dtype != torch.float32:
         raise RuntimeError("refine_detections: dets must be float32 [B, K, 14]")
-    B, K, _ = dets.shape
+    B = dets.shape[0]
     p2, p2_inv = p2_arrays(p2, B)
     dev = dets.device
-    d_p2 = torch.from_numpy(p2).to(dev)
-    d_pi = torch.from_numpy(p2_inv).to(dev)
     d_sc = None if scale is None else torch.as_tensor(np.asarray(scale, dtype=np.float32).reshape(B)).to(dev)
     d_cl = None if clip_wh is None else torch.as_tensor(np.asarray(clip_wh, dtype=np.float32).reshape(B, 2)).to(dev)
-    dets = dets.contiguous()
-    counts = counts.to(device=dev, dtype=torch.int32).contiguous()
-    out = torch.empty(B, K, 16, device=dev, dtype=torch.float64)
-    with torch.cuda.device(dev):
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _hip.check(_hip.lib().m3d_refine_3d_ex(dets.data_ptr(), counts.data_ptr(), B, K, d_p2.data_ptr(), d_pi.data_ptr(),
-                                               None if d_sc is None else d_sc.data_ptr(),
-                                               None if d_cl is None else d_cl.data_ptr(), float(score_thresh),
-                                               1 if hill_climbing else 0, float(step_r_init), float(r_lim), out.data_ptr(), st))
-    return out
+    return refine_rows(dets.contiguous(), counts.to(device=dev, dtype=torch.int32).contiguous(), torch.from_numpy(p2).to(dev),
+                       torch.from_numpy(p2_inv).to(dev), d_sc, d_cl, score_thresh, hill_climbing, step_r_init, r_lim)
 
 
 def kitti_text(refined_rows, lbls):

@@ -34,41 +34,81 @@ import ctypes
 import math
 import os
 
-import numpy as np
 import torch
 
 from . import _hip
 from .host.detect import (detect_from_outputs, detect_from_planar, detect_from_planar_mw, score_keys_planar, select_block,
                           unwrap)
-from .host.refine import p2_arrays
+from .host.refine import RefineMeta, refine_rows
 
 
-class PipelinedDetector:
-    def __init__(self, net, conf, batch, height, width, refine=False, score_thresh=0.75, step_r_init=0.3 * math.pi, r_lim=0.01,
-                 u8_frame=None, planar=None):
+class _Detector:
+    """What both detectors own: the module, its engine and plan, the input buffers, the refinement's buffers, and the pieces of a
+    captured step -- plan ops with the input pointer set, rows -> selection -> optional refinement, the result tuple."""
+
+    def __init__(self, net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, u8_buffers):
         net = unwrap(net)                               # (a DataParallel / DDP wrapper of the module, as the reference's scripts pass it)
         self.net, self.conf = net, conf
-        self.planar = (os.environ.get("M3D_PIPE_PLANAR", "1") != "0") if planar is None else bool(planar)
-        self.u8_frame = None if u8_frame is None else (int(u8_frame[0]), int(u8_frame[1]))
-        self.refine = bool(refine)
-        self._rargs = (float(score_thresh), 1 if bool(getattr(conf, "hill_climbing", True)) else 0, float(step_r_init), float(r_lim))
         dev = next(net.parameters()).device
         if dev.type != "cuda":
-            raise NotImplementedError("PipelinedDetector needs the module on a ROCm device")
+            raise NotImplementedError("%s needs the module on a ROCm device" % type(self).__name__)
         self.dev = dev
+        self.batch = int(batch)
+        self.refine = bool(refine)
+        self.u8_frame = None if u8_frame is None else (int(u8_frame[0]), int(u8_frame[1]))
+        self._rargs = (float(score_thresh), bool(getattr(conf, "hill_climbing", True)), float(step_r_init), float(r_lim))
         self.eng = net.engine()
-        self.plan = self.eng.plan_for(batch, height, width)
+        self.plan = self.eng.plan_for(self.batch, height, width)
         if self.u8_frame is None:
-            self.input = torch.zeros(batch, 3, height, width, device=dev, dtype=torch.float32)
+            self.input = torch.zeros(self.batch, 3, height, width, device=dev, dtype=torch.float32)
         else:
             fh, fw = self.u8_frame
             if fh > height or fw > width:
                 raise RuntimeError("u8_frame %dx%d does not fit the padded size %dx%d" % (fh, fw, height, width))
-            nbytes = batch * fh * fw * 3
+            nbytes = self.batch * fh * fw * 3
             self._u8_bytes = nbytes
-            self._u8_flat = [torch.zeros(-(-nbytes // 16) * 16, device=dev, dtype=torch.uint8) for _ in range(2)]
-            self.inputs_u8 = [t[:nbytes].view(batch, fh, fw, 3) for t in self._u8_flat]
+            self._u8_flat = [torch.zeros(-(-nbytes // 16) * 16, device=dev, dtype=torch.uint8) for _ in range(u8_buffers)]
+            self.inputs_u8 = [t[:nbytes].view(self.batch, fh, fw, 3) for t in self._u8_flat]
             self.input = self.inputs_u8[0]
+        assert self.plan.ops[-1][0] == "bundle_outputs"
+        self.n_fwd = len(self.plan.ops) - 1                 # planar form: everything in front of the output bundling
+        self._rois = net.rois.to(dev)
+        # refine mode: calibration / scale / image size of the batch whose detections the next replay refines
+        self._meta = RefineMeta(self.batch, dev) if self.refine else None
+
+    def _forward(self, start, end, buf=0):
+        if self.u8_frame is None:
+            self.plan.named["input_ptr"][0] = self.input.data_ptr()
+            self.eng.run_plan(self.plan, start, end)
+            return
+        # the stem launch reads (pointer, h, w) of the uint8 frames when it is ISSUED: capture bakes buffer `buf` into the graph
+        self.plan.named["input_u8"][:] = [self.inputs_u8[buf].data_ptr(), self.u8_frame[0], self.u8_frame[1]]
+        try:
+            self.eng.run_plan(self.plan, start, end)
+        finally:
+            self.plan.named["input_u8"][0] = 0
+
+    def _select(self, rows):
+        """(aboxes, keep, num) of a detect_from_* -> (block, counts, refined rows or None)."""
+        block, counts = select_block(*rows, self.conf)
+        if not self.refine:
+            return block, counts, None
+        # the block's rows are the kept rows + the count row (past counts[b]: refined to zeros); the scale factors were applied
+        # inside the decode, before the NMS (lib/rpn_util.py:1504-1506), not here
+        m = self._meta
+        return block, counts, refine_rows(block, counts, m.p2, m.p2_inv, None, m.clip, *self._rargs)
+
+    def _result(self, block, counts, refined, as_block):
+        res = (block if as_block else block[:, :-1], counts)
+        return res + (refined[:, :-1],) if self.refine else res
+
+
+class PipelinedDetector(_Detector):
+    def __init__(self, net, conf, batch, height, width, refine=False, score_thresh=0.75, step_r_init=0.3 * math.pi, r_lim=0.01,
+                 u8_frame=None, planar=None):
+        super().__init__(net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, 2)
+        self.planar = (os.environ.get("M3D_PIPE_PLANAR", "1") != "0") if planar is None else bool(planar)
+        if self.u8_frame is not None:
             # slot i: address of the pinned-host frames that the graph reading buffer i uploads into buffer i ^ 1 (0 = nothing)
             self._slots = torch.zeros(2, dtype=torch.int64).pin_memory()
             self._done = [torch.cuda.Event(), torch.cuda.Event()]      # the last replay of graph i finished (main stream)
@@ -78,8 +118,6 @@ class PipelinedDetector:
             self._primed = False                                       # buffer _cur holds the head of the queue
             self._inflight = [None, None]                              # frames a replay of graph i is uploading (kept alive)
             self._prime_ev = None                                      # behind feed()'s own copy of a batch nothing in flight uploads
-        self.n_fwd = len(self.plan.ops) - 1
-        assert self.plan.ops[-1][0] == "bundle_outputs"
         n = self.plan.named
         # planar form: the side branch must be done before the first launch that overwrites the planar staging
         # bundled form: detect(k-1) reads prob / bbox_* / score_bits; bundle_outputs (the last op) writes the first three, but with
@@ -94,18 +132,8 @@ class PipelinedDetector:
         fork = os.environ.get("M3D_PIPE_FORK")
         self.n_fork = min(int(fork) if fork is not None else int(n.get("pipe_fork_op", 0)), self.n_join)
         self._outs = (n["prob"], n["bbox_2d"], n["bbox_3d"])
-        self._rois = net.rois.to(dev)
         self._pending = False
-        if self.refine:
-            # calibration / scale / image size of the batch whose detections the NEXT replay refines; `_meta_next` (host) holds
-            # those of the batch submitted last
-            self._p2 = torch.zeros(batch, 16, device=dev, dtype=torch.float64)
-            self._p2_inv = torch.zeros(batch, 16, device=dev, dtype=torch.float64)
-            self._p2[:, 0::5] = 1.0
-            self._p2_inv[:, 0::5] = 1.0
-            self._scale = torch.ones(batch, device=dev, dtype=torch.float32)
-            self._clip = torch.zeros(batch, 2, device=dev, dtype=torch.float32)
-            self._meta_next = None
+        self._meta_next = None                          # (refine mode, host) the meta of the batch submitted last
         self._build()
 
     def _check_no_write_beside_detect(self):
@@ -122,35 +150,12 @@ class PipelinedDetector:
 
     def _detect(self):
         prob, b2, b3 = self._outs
-        # refine mode carries the frames' test-time scale factors: the boxes are divided by them inside the decode, before the NMS
-        # (lib/rpn_util.py:1504-1506), not in the refinement behind it
-        scale = self._scale if self.refine else None
+        scale = self._meta.scale if self.refine else None
         if self.planar:
             rows = detect_from_planar(self.eng, self.plan, self._rois, self.conf, scale)
         else:
             rows = detect_from_outputs(self.eng, self.plan, prob, b2, b3, self._rois, self.conf, scale)
-        block, counts = select_block(*rows, self.conf)
-        if not self.refine:
-            return block, counts, None
-        B, K1, _ = block.shape                          # K1 = kept rows + the count row (past counts[b]: refined to zeros)
-        out = torch.empty(B, K1, 16, device=self.dev, dtype=torch.float64)
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        _hip.check(_hip.lib().m3d_refine_3d_ex(block.data_ptr(), counts.data_ptr(), B, K1, self._p2.data_ptr(),
-                                               self._p2_inv.data_ptr(), None, self._clip.data_ptr(),
-                                               *self._rargs, out.data_ptr(), st))
-        return block, counts, out
-
-    def _forward(self, start, end, buf=0):
-        if self.u8_frame is None:
-            self.plan.named["input_ptr"][0] = self.input.data_ptr()
-            self.eng.run_plan(self.plan, start, end)
-            return
-        # the stem launch reads (pointer, h, w) of the uint8 frames when it is ISSUED: capture bakes buffer `buf` into the graph
-        self.plan.named["input_u8"][:] = [self.inputs_u8[buf].data_ptr(), self.u8_frame[0], self.u8_frame[1]]
-        try:
-            self.eng.run_plan(self.plan, start, end)
-        finally:
-            self.plan.named["input_u8"][0] = 0
+        return self._select(rows)
 
     def _finish(self, buf=0):
         """The launches behind the join: the rest of the forward, then the key-only pass (planar) or the output bundling."""
@@ -200,18 +205,8 @@ class PipelinedDetector:
 
     def _upload_meta(self):
         """Calibration of the batch submitted LAST -> the device buffers the refinement of the next replay reads."""
-        m = self._meta_next
-        if m is None:
-            return
-        B = self.input.shape[0]
-        p2, p2_inv = p2_arrays(m["p2"], B)
-        self._p2.copy_(torch.from_numpy(p2.reshape(B, 16)))
-        self._p2_inv.copy_(torch.from_numpy(p2_inv.reshape(B, 16)))
-        scale = m.get("scale")
-        self._scale.copy_(torch.from_numpy(np.ones(B, np.float32) if scale is None else np.asarray(scale, np.float32).reshape(B)))
-        clip = m.get("clip_wh")
-        self._clip.copy_(torch.from_numpy(np.zeros((B, 2), np.float32) if clip is None
-                                          else np.asarray(clip, np.float32).reshape(B, 2)))
+        if self._meta_next is not None:
+            self._meta.upload(self._meta_next)
 
     # ---- fed-input form ---------------------------------------------------------------------------------------------------------
     def feed(self, frames):
@@ -296,8 +291,7 @@ class PipelinedDetector:
         self._pending = True
         if not had:
             return None
-        res = (self._block if as_block else self._block[:, :-1], self._counts)
-        return res + (self._refined[:, :-1],) if self.refine else res
+        return self._result(self._block, self._counts, self._refined, as_block)
 
     def flush(self, as_block=False):
         """Detections of the last submitted batch."""
@@ -308,8 +302,7 @@ class PipelinedDetector:
             self._meta_next = None
         self.tail.replay()
         self._pending = False
-        res = (self._tblock if as_block else self._tblock[:, :-1], self._tcounts)
-        return res + (self._trefined[:, :-1],) if self.refine else res
+        return self._result(self._tblock, self._tcounts, self._trefined, as_block)
 
 
 # FrameDetector(topk_wgs=None): the multi-workgroup top-k up to this batch size, the single-workgroup kernel (one workgroup per
@@ -319,7 +312,7 @@ class PipelinedDetector:
 FRAME_MW_MAX_BATCH = 0
 
 
-class FrameDetector:
+class FrameDetector(_Detector):
     """Single-frame mode: ``detect(x)`` returns the detections of THIS x.
 
     One captured hipGraph per instance holds the whole planar-form forward of the plan, the key pass (where the plan does not write
@@ -336,73 +329,26 @@ class FrameDetector:
 
     def __init__(self, net, conf, height, width, batch=1, refine=False, score_thresh=0.75, step_r_init=0.3 * math.pi, r_lim=0.01,
                  u8_frame=None, topk_wgs=None):
-        net = unwrap(net)
-        self.net, self.conf = net, conf
-        dev = next(net.parameters()).device
-        if dev.type != "cuda":
-            raise NotImplementedError("FrameDetector needs the module on a ROCm device")
         if topk_wgs is not None and int(topk_wgs) < 1:
             raise ValueError("topk_wgs must be None or a positive number of workgroups per image, got %r" % (topk_wgs,))
-        self.dev = dev
-        self.batch = int(batch)
-        self.refine = bool(refine)
-        self.u8_frame = None if u8_frame is None else (int(u8_frame[0]), int(u8_frame[1]))
+        super().__init__(net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, 1)
         if topk_wgs is None:
             self.topk_wgs = 0 if self.batch <= FRAME_MW_MAX_BATCH else 1       # 0: m3d_topk_decode_planar_mw picks the count
         else:
             self.topk_wgs = int(topk_wgs)
-        self._rargs = (float(score_thresh), 1 if bool(getattr(conf, "hill_climbing", True)) else 0, float(step_r_init), float(r_lim))
-        self.eng = net.engine()
-        self.plan = self.eng.plan_for(self.batch, height, width)
-        if self.u8_frame is None:
-            self.input = torch.zeros(self.batch, 3, height, width, device=dev, dtype=torch.float32)
-        else:
-            fh, fw = self.u8_frame
-            if fh > height or fw > width:
-                raise RuntimeError("u8_frame %dx%d does not fit the padded size %dx%d" % (fh, fw, height, width))
-            self.input = torch.zeros(self.batch, fh, fw, 3, device=dev, dtype=torch.uint8)
-        assert self.plan.ops[-1][0] == "bundle_outputs"
-        self.n_fwd = len(self.plan.ops) - 1                 # planar form: everything in front of the output bundling
-        self._rois = net.rois.to(dev)
-        B = self.batch
-        self._scale = torch.ones(B, device=dev, dtype=torch.float32) if self.refine else None
-        if self.refine:
-            self._p2 = torch.zeros(B, 16, device=dev, dtype=torch.float64)
-            self._p2_inv = torch.zeros(B, 16, device=dev, dtype=torch.float64)
-            self._p2[:, 0::5] = 1.0
-            self._p2_inv[:, 0::5] = 1.0
-            self._clip = torch.zeros(B, 2, device=dev, dtype=torch.float32)
         self._build()
 
     def _run(self):
         """Forward, keys, detection (and refinement) of what ``self.input`` holds, on the current stream."""
-        n = self.plan.named
-        if self.u8_frame is None:
-            n["input_ptr"][0] = self.input.data_ptr()
-            self.eng.run_plan(self.plan, 0, self.n_fwd)
-        else:
-            # the stem launch reads (pointer, h, w) of the uint8 frames when it is ISSUED: capture bakes them into the graph
-            n["input_u8"][:] = [self.input.data_ptr(), self.u8_frame[0], self.u8_frame[1]]
-            try:
-                self.eng.run_plan(self.plan, 0, self.n_fwd)
-            finally:
-                n["input_u8"][0] = 0
-        if not n.get("keys_by_select"):                     # else anchor_select wrote them on the way (engine: SELECT_KEYS)
+        self._forward(0, self.n_fwd)
+        if not self.plan.named.get("keys_by_select"):       # else anchor_select wrote them on the way (engine: SELECT_KEYS)
             score_keys_planar(self.eng, self.plan)
+        scale = self._meta.scale if self.refine else None
         if self.topk_wgs == 1:
-            rows = detect_from_planar(self.eng, self.plan, self._rois, self.conf, self._scale)
+            rows = detect_from_planar(self.eng, self.plan, self._rois, self.conf, scale)
         else:
-            rows = detect_from_planar_mw(self.eng, self.plan, self._rois, self.conf, self._scale, self.topk_wgs or None)
-        block, counts = select_block(*rows, self.conf)
-        if not self.refine:
-            return block, counts, None
-        B, K1, _ = block.shape                              # K1 = kept rows + the count row (past counts[b]: refined to zeros)
-        out = torch.empty(B, K1, 16, device=self.dev, dtype=torch.float64)
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        _hip.check(_hip.lib().m3d_refine_3d_ex(block.data_ptr(), counts.data_ptr(), B, K1, self._p2.data_ptr(),
-                                               self._p2_inv.data_ptr(), None, self._clip.data_ptr(),
-                                               *self._rargs, out.data_ptr(), st))
-        return block, counts, out
+            rows = detect_from_planar_mw(self.eng, self.plan, self._rois, self.conf, scale, self.topk_wgs or None)
+        return self._select(rows)
 
     def _build(self):
         cap = torch.cuda.Stream(self.dev)
@@ -414,17 +360,6 @@ class FrameDetector:
             with torch.cuda.graph(self.graph, stream=cap):
                 self._block, self._counts, self._refined = self._run()
         torch.cuda.current_stream(self.dev).wait_stream(cap)
-
-    def _upload_meta(self, m):
-        B = self.batch
-        p2, p2_inv = p2_arrays(m["p2"], B)
-        self._p2.copy_(torch.from_numpy(p2.reshape(B, 16)))
-        self._p2_inv.copy_(torch.from_numpy(p2_inv.reshape(B, 16)))
-        scale = m.get("scale")
-        self._scale.copy_(torch.from_numpy(np.ones(B, np.float32) if scale is None else np.asarray(scale, np.float32).reshape(B)))
-        clip = m.get("clip_wh")
-        self._clip.copy_(torch.from_numpy(np.zeros((B, 2), np.float32) if clip is None
-                                          else np.asarray(clip, np.float32).reshape(B, 2)))
 
     def detect(self, x, meta=None, as_block=False):
         """Detections of x: (dets [B, nms_topN_post, 14], counts [B] int32), with refine=True also the refined rows
@@ -443,8 +378,7 @@ class FrameDetector:
         if self.refine:
             if meta is None:
                 raise RuntimeError("FrameDetector(refine=True).detect needs the frame's meta (p2, scale, clip_wh)")
-            self._upload_meta(meta)
+            self._meta.upload(meta)
         self.input.copy_(x, non_blocking=True)
         self.graph.replay()
-        res = (self._block if as_block else self._block[:, :-1], self._counts)
-        return res + (self._refined[:, :-1],) if self.refine else res
+        return self._result(self._block, self._counts, self._refined, as_block)
