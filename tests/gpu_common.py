@@ -190,6 +190,96 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ------------------------------------------------------------------------------------ bf16 conv descriptor (tests/test_gpu_bf16.py, tests/test_gpu_exact.py)
+def _nhwc16(x, cs=None):
+    """[N,C,H,W] fp32 -> bf16 NHWC device tensor with pixel stride cs (extra channels filled with a sentinel)."""
+    n, c, h, w = x.shape
+    cs = c if cs is None else cs
+    t = torch.full((n, h, w, cs), 768.0, dtype=torch.bfloat16)
+    t[..., :c] = x.permute(0, 2, 3, 1).to(torch.bfloat16)
+    return t.contiguous().to(_dev())
+
+
+def _run_conv(x, wt, bias=None, bn=None, stride=1, pad=0, act=0, res=None, res_mode=0, sigmoid_from=-1, out_mode=0, om=None,
+              in_cs=None, variant=None, patch=False, wide=False, alias_res_out=False, affine=None):
+    """Through the C ABI.  Returns [N, Cout, Ho, Wo] fp32 (bf16 outputs widened).  alias_res_out: res = out (in-place residual);
+    returns the call's status code and error text instead.  affine = (scale, shift): the epilogue's per-channel fp32 scale / shift
+    given directly (instead of folding bias / bn)."""
+    from m3dssd_amd import _hip
+    from m3dssd_amd.engine_bf16 import pack_conv_bf16
+    L = _hip.lib()
+    dev = _dev()
+    n, c, h, w = x.shape
+    co, _, kh, kw = wt.shape
+    ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    xin = _nhwc16(x, in_cs)
+    wp, kpad = pack_conv_bf16(wt, None, None, dev)
+    d = _hip.ConvBf16Desc()
+    d.inp, d.in_cs, d.N, d.H, d.W, d.Cin = xin.data_ptr(), xin.shape[3], n, h, w, c
+    d.wgt, d.Cout, d.Cout_pad, d.Kpad = wp.data_ptr(), co, wp.shape[0], kpad
+    d.kh, d.kw, d.stride, d.pad, d.Ho, d.Wo = kh, kw, stride, pad, ho, wo
+    keep = [xin, wp]
+    scale = torch.ones(co)
+    shift = torch.zeros(co) if bias is None else bias.clone()
+    if bn is not None:
+        g, b, m, v = bn
+        s = g / torch.sqrt(v + 1e-5)
+        shift = (shift - m) * s + b
+        scale = s
+    if affine is not None:
+        assert bias is None and bn is None
+        scale, shift = affine[0].float(), affine[1].float()
+    if bias is not None or bn is not None or affine is not None:
+        sc, sh = scale.to(dev).contiguous(), shift.to(dev).contiguous()
+        d.scale, d.shift = sc.data_ptr(), sh.data_ptr()
+        keep += [sc, sh]
+    if res is not None:
+        r = _nhwc16(res)
+        d.res, d.res_cs, d.res_mode = r.data_ptr(), r.shape[3], res_mode
+        keep.append(r)
+    d.act, d.sigmoid_from, d.groups = act, sigmoid_from, 1
+    if wide:                # 128 x 128 wave-tile kernel: the same weights in fragment order (engine_bf16.PackedBf16.wave3x3)
+        cop = wp.shape[0]
+        wv = wp[:, :9 * c].reshape(cop // 128, 4, 32, 9, c // 32, 2, 2, 8).permute(0, 4, 3, 5, 1, 6, 2, 7).contiguous()
+        d.wgt_wave = wv.data_ptr()
+        keep.append(wv)
+    if om is not None:
+        o = om.to(dev).contiguous()
+        d.dcn_offmask, d.dcn_om_cs = o.data_ptr(), o.shape[-1]
+        keep.append(o)
+        if patch:           # LDS-patch DCNv2 kernel: fp16 weight copy + the device scratch of the |offset| bound
+            nws = max(256, _hip.lib().m3d_conv_bf16_dcn_ws_bytes(n, ho, wo) // 4)
+            w16, ws = wp.float().to(torch.float16).contiguous(), torch.full((nws,), 7, device=dev, dtype=torch.int32)
+            d.wgt_f16, d.dcn_ws, d.dcn_ws_bytes = w16.data_ptr(), ws.data_ptr(), 4 * nws
+            keep += [w16, ws]
+    if out_mode == 0:
+        ocs = (co + 7) // 8 * 8 + 8
+        out = torch.full((n, ho, wo, ocs), 512.0, device=dev, dtype=torch.bfloat16)
+        d.out, d.out_cs = out.data_ptr(), ocs
+    elif out_mode == 1:
+        ocs = (co + 3) // 4 * 4 + 4
+        out = torch.full((n, ho, wo, ocs), 512.0, device=dev, dtype=torch.float32)
+        d.out, d.out_cs = out.data_ptr(), ocs
+    else:
+        out = torch.full((n, co + 1, ho * wo), 512.0, device=dev, dtype=torch.float32)
+        d.out, d.out_img_stride = out.data_ptr(), (co + 1) * ho * wo
+    d.out_mode = out_mode
+    if alias_res_out:
+        d.res, d.res_cs, d.res_mode = d.out, d.out_cs, 0
+        rc = L.m3d_conv_bf16_forward(ctypes.byref(d), _stream())
+        torch.cuda.synchronize()
+        return rc, L.m3d_last_error().decode()
+    if variant is not None:
+        assert L.m3d_conv_bf16_variant(ctypes.byref(d)) == variant
+    _hip.check(L.m3d_conv_bf16_forward(ctypes.byref(d), _stream()))
+    torch.cuda.synchronize()
+    if out_mode == 2:
+        assert (out[:, co] == 512.0).all()                     # the channel past Cout is untouched
+        return out[:, :co].view(n, co, ho, wo).cpu()
+    assert (out[..., co:].float() == 512.0).all()              # nothing is written past Cout
+    return out[..., :co].float().permute(0, 3, 1, 2).contiguous().cpu()
+
+
 # ------------------------------------------------------------------------------------ top-k select + decode
 def _topk_inputs(R, A, seed, scores):
     g = torch.Generator().manual_seed(seed)
@@ -407,4 +497,4 @@ def _net_dt(crop, B, dtype="f32"):
     return net.to(_dev()).set_compute_dtype(dtype), conf
 
 
-__all__ = ['CONV_CASES', 'CROP', 'GOLDEN', 'ROOT', 'TOPK_CASES', 'WINO44_CASES', 'WINO_CASES', '_RANK_SCRIPT', '_check_decisions', '_clean_rows', '_dev', '_free_port', '_head_case', '_log', '_net_dev', '_net_dt', '_net_sd', '_parity_log', '_relerr', '_relerr_t', '_run_bench', '_run_both', '_run_ranks', '_single_process_reference', '_soak', '_sortable_bits', '_stream', '_topk_inputs', '_w44_case', 'gpu_nms_empty']
+__all__ = ['CONV_CASES', 'CROP', 'GOLDEN', 'ROOT', 'TOPK_CASES', 'WINO44_CASES', 'WINO_CASES', '_RANK_SCRIPT', '_check_decisions', '_clean_rows', '_dev', '_free_port', '_head_case', '_log', '_net_dev', '_net_dt', '_net_sd', '_nhwc16', '_parity_log', '_relerr', '_relerr_t', '_run_bench', '_run_both', '_run_conv', '_run_ranks', '_single_process_reference', '_soak', '_sortable_bits', '_stream', '_topk_inputs', '_w44_case', 'gpu_nms_empty']
