@@ -79,7 +79,8 @@ const char *m3d_last_error(void);
  *                     the round-4 experimental forms (bf16_wino2, bf16_frontend, bf16_head_mlp) left the product library.
  *   added under 5: m3d_dcn_v2_backward, m3d_dcn_v2_backward_workspace_bytes (additive; nothing existing changed);
  *                  m3d_rpn_targets, m3d_rpn_loss, m3d_rpn_loss_workspace_bytes (additive);
- *                  m3d_topk_decode_planar_mw, m3d_topk_decode_mw_workspace_bytes (additive). */
+ *                  m3d_topk_decode_planar_mw, m3d_topk_decode_mw_workspace_bytes (additive);
+ *                  m3d_conv_wave_forward_wgsplit, m3d_conv_wave_wgsplit_width (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -138,6 +139,17 @@ int m3d_conv_wave_applicable(const m3d_conv_desc *d);
  * epilogue).  Without a workspace the layer is simply not split. */
 int m3d_conv_wave_splitk_plan(const m3d_conv_desc *d, int *splits, long long *ws_bytes);
 int m3d_conv_wave_forward(const m3d_conv_desc *d, m3d_stream_t stream);
+/* The same layer with the K split of m3d_conv_wave_splitk_plan INSIDE the workgroups: the S = 2 / 4 / 8 waves of a workgroup
+ * own one tile, each runs one K slice (the slices of the plan), the partial sums are added in slice order through LDS and the
+ * epilogue is applied in the same launch -- the same bits as the workspace form, no workspace, no second launch.  splitk_ws /
+ * splitk_ws_bytes are ignored (the plan is computed as if a workspace were given); a layer the plan does not split runs
+ * unsplit.  This entry point alone also takes plain convolutions (no dcn_offmask, shared weights) with Cout_pad % 64 == 32:
+ * one 32-channel column tile per wave (the 27 -> 32 channel offset / mask convs); m3d_conv_wave_splitk_plan reports their
+ * split with *ws_bytes = 0 (there is no workspace form of them). */
+int m3d_conv_wave_forward_wgsplit(const m3d_conv_desc *d, m3d_stream_t stream);
+/* What that call launches: *slices = K slices (1 = unsplit; the fill threshold is advisory here as in the forward calls, so a
+ * small layer is split too), *width = waves per workgroup (1 / 2 / 4 / 8, the next width that holds the slices). */
+int m3d_conv_wave_wgsplit_width(const m3d_conv_desc *d, int *slices, int *width);
 
 /* Winograd F(2x2,3x3) variant for 3x3 / stride 1 / pad 1 / even H,W plain convolutions (same descriptor; `wgt`
  * must point to the Winograd-transformed weights U = G g G^T packed in fragment order

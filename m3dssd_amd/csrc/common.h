@@ -168,6 +168,28 @@ static inline int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ float leaky(float v) { return fmaxf(v, v * M3D_LEAKY_SLOPE); }
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
+// ---- the convolution epilogue shared by the wave-granular kernel (csrc/dcn_wave.hip: the unsplit form and the in-workgroup
+// K split) and splitk_reduce_kernel (igemm_conv.hip): one definition, so that a layer gives the same bits whichever of them
+// finishes it.  T = float or f32x4 (4 consecutive channels).
+template <typename T>
+__device__ __forceinline__ T conv_epi_affine(T v, T sc, T sh, T rv, bool has_res, int res_mode)
+{
+    if (has_res) return res_mode ? (v + rv) * sc + sh : v * sc + sh + rv;
+    return v * sc + sh;
+}
+// slope: M3D_LEAKY_SLOPE for act == 1, 1.0f for none (max(v, v) = v)
+__device__ __forceinline__ float conv_epi_act(float v, bool sig, float slope) { return sig ? sigmoidf_(v) : fmaxf(v, v * slope); }
+// any_sig: some of the 4 channels c0 .. c0+3 may lie at or past sigmoid_from (the caller's cheap, uniform pre-test)
+__device__ __forceinline__ f32x4 conv_epi_act4(f32x4 v, int c0, int sigmoid_from, bool any_sig, float slope)
+{
+    if (any_sig) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = conv_epi_act(v[e], c0 + e >= sigmoid_from, slope);
+        return v;
+    }
+    return __builtin_elementwise_max(v, v * slope);
+}
+
 // ---- class softmax + row score shared by bundle_outputs / score_keys_planar (rpn_kernels.hip) and the planar decode
 // (detect_kernels.hip): one definition, so the probabilities a row is SORTED by and the ones it is DECODED with are the same bits
 // whichever kernel computes them (M3d_inference_align.py:229-232: softmax over the 4 class logits of an anchor row).

@@ -50,27 +50,37 @@ static long long *g_conv_trace = nullptr;
 extern "C" void m3d_conv_wave_set_trace(void *buf) { g_conv_trace = (long long *)buf; }
 static int g_conv_variant = 0;
 extern "C" void m3d_conv_wave_set_variant(int v) { g_conv_variant = v; }
-#define TRACE_INIT() long long *trp = a.trace ? a.trace + (size_t)blockIdx.x * 128 : nullptr; int tri = 0
+#define TRACE_INIT() long long *trp = (a.trace && threadIdx.x < 64) ? a.trace + (size_t)blockIdx.x * 128 : nullptr; int tri = 0
 #define TRACE() do { if (trp && lane == 0 && tri < 128) trp[tri++] = __builtin_readcyclecounter(); } while (0)
 #else
 #define TRACE_INIT()
 #define TRACE()
 #endif
 
-// NT = column tiles of 32 output channels per wave: 4 (128 channels) or, for 64-channel layers, 2
+// NT = column tiles of 32 output channels per wave: 4 (128 channels) or, for 64-channel layers, 2; 1 (plain kernel, through
+// m3d_conv_wave_forward_wgsplit only) for the 27 -> 32 channel offset / mask convs of the DCNv2 layers on the small maps
 // NCQ / WPE: experiment knobs (diagnostic library only, m3d_conv_wave_experiment): corners gathered per (pixel, tap) and the
 // register bound in waves per SIMD.  The product instantiates the defaults.
-template <bool DEFORM, int NT, int NCQ = 4, int WPE = (DEFORM ? 2 : 3)>      // register bound: 3 waves per SIMD for the plain kernel, 2 for the deformable one (as its K loop needs)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_wave_kernel(const ConvWaveArgs a)
+//
+// S > 1: the K split INSIDE the workgroup (m3d_conv_wave_forward_wgsplit).  The workgroup is S waves that own ONE 32-pixel x
+// (32*NT)-channel tile; wave s runs the K steps [s*ss_per, (s+1)*ss_per) -- the slices conv_wave_plan gives the global split --
+// with its own 4 KB A tile, and the deformable sampling state is built once per workgroup (the nine taps divided among the
+// waves, one shared tapst).  After the K loop the S x 4 KB of A tiles hold one 32 x 32 column tile of partial sums per wave:
+// per column tile the waves share its rows, add the S partials in slice order 0..S-1 (the order of splitk_reduce_kernel),
+// apply the epilogue and store 16 bytes per lane.  No workspace, no second launch; workgroup barriers only.
+template <bool DEFORM, int NT, int NCQ = 4, int WPE = (DEFORM ? 2 : 3), int S = 1>      // register bound: 3 waves per SIMD for the plain kernel, 2 for the deformable one (as its K loop needs)
+__global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_wave_kernel(const ConvWaveArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float tileA[32 * 32];     // [pixel][8 slots of 4 channels], swizzled
+    __shared__ __attribute__((aligned(16))) float tileS[S * 32 * 32];     // per wave: [pixel][8 slots of 4 channels], swizzled
     // [tap][pixel][4 corner offsets (as bits), 4 weights]: DEFORM keeps the sampling state of all (<= 9) taps here, built once in
     // the prologue, because its K loop runs CHUNK-major (32 input channels outer, taps inner): the input lines a wave gathers for
     // one channel chunk are re-used by the 9 taps x 4 corners within 9 steps and the chunk's share of the in-flight pixels
     // (8192 px x 128 B per XCD) fits the 4 MB L2 -- tap-major, every (tap, chunk) visit found its lines evicted: 178 MB of fabric
     // traffic per full-size launch against 84 MB algorithmic (PMC, profiles/r03r, r04a)
     __shared__ __attribute__((aligned(16))) float tapst[(DEFORM ? 9 : 1) * 32 * 8];
-    const int lane = threadIdx.x, l31 = lane & 31, h = lane >> 5;
+    const int lane = threadIdx.x & 63, l31 = lane & 31, h = lane >> 5;
+    const int wv = S > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0;      // this wave's K slice
+    float *const tileA = tileS + wv * 1024;
     const int gp = lane >> 3, gc = lane & 7;                         // gather map: pixel-in-group, chunk
     TRACE_INIT();
     TRACE();
@@ -80,15 +90,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, loc = bid >> 3;
         blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
     }
-    int split = 0;
-    if (a.splits > 1) {
+    int split = wv;
+    if (S == 1 && a.splits > 1) {              // the global split: slices are grid planes
         split = blk / a.base_waves;
         blk -= split * a.base_waves;
     }
     const int bm = blk / a.tiles_n, bn = blk - bm * a.tiles_n;
     const int m0 = bm * 32;
     const int KK = a.kh * a.kw, C32 = a.Cin / 32;
-    const int ss0 = split * a.ss_per, ss1 = min(KK * C32, ss0 + a.ss_per);        // this wave's steps
+    // this wave's steps; S > 1: a plan of 3 / 5 / 6 / 7 slices runs on the next width, its surplus waves have no steps (they
+    // prefetch step 0, add nothing and are left out of the sum)
+    const bool idle = S > 1 && wv >= a.splits;
+    const int ss0 = idle ? 0 : split * a.ss_per, ss1 = idle ? 0 : min(KK * C32, ss0 + a.ss_per);
 
     const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.in, a.in_bytes);
     // per-image weights (the ANAB logits / P.V GEMMs): the 32 pixels of a wave belong to one image (HoWo % 32 == 0)
@@ -135,21 +148,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     float bw[DEFORM ? 4 : 1][4];
     // DEFORM prologue: sampling state of every tap (offsets / mask of all taps fetched in one go: 27 loads in flight per lane)
     if constexpr (DEFORM) {
-        float raws[9][3];
+        // S > 1: wave wv builds taps wv, wv + S, ... for the whole workgroup
+        constexpr int TPW = (9 + S - 1) / S;
+        float raws[TPW][3];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int tp = min(t, KK - 1);
-            raws[t][0] = o_om[2 * tp];
-            raws[t][1] = o_om[2 * tp + 1];
-            raws[t][2] = o_om[2 * KK + tp];
+        for (int i = 0; i < TPW; ++i) {
+            const int tp = min(wv + i * S, KK - 1);
+            raws[i][0] = o_om[2 * tp];
+            raws[i][1] = o_om[2 * tp + 1];
+            raws[i][2] = o_om[2 * KK + tp];
         }
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
+        for (int i = 0; i < TPW; ++i) {
+            const int t = wv + i * S;
             if (t < KK) {                          // wave-uniform
                 const int ti = t / a.kw, tj = t - ti * a.kw;
-                const float mk = raws[t][2];
-                const float h_im = (float)(o_hi0 + ti * a.dil) + raws[t][0];
-                const float w_im = (float)(o_wi0 + tj * a.dil) + raws[t][1];
+                const float mk = raws[i][2];
+                const float h_im = (float)(o_hi0 + ti * a.dil) + raws[i][0];
+                const float w_im = (float)(o_wi0 + tj * a.dil) + raws[i][1];
                 float wq[4];
                 int oq[4], drop[4];
                 dcn_corners(h_im, w_im, a.H, a.W, o_inv, wq, oq, drop);      // no SGPR lane masks in here: see common.h
@@ -166,6 +182,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
             }
         }
         // single wave: the LDS writes above are ordered before the reads below by the wave's own lgkmcnt
+        if constexpr (S > 1) __syncthreads();
     }
     auto setup_tap = [&](int tap) {
         if constexpr (DEFORM) {
@@ -296,6 +313,92 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     const __amdgpu_buffer_rsrc_t rres = make_rsrc(a.res ? a.res : a.out, a.res ? a.res_bytes : 0u);
     const int n0 = bn * 32 * NT;
     const int mb = m0 + 4 * h;
+    if constexpr (S > 1) {
+        // ---- in-workgroup reduction: thread tid owns 4 consecutive channels (c4) of pixel tid >> 3 of the column tile (S = 2:
+        // two pixels, S = 8: the first four waves) ----
+        constexpr int Q = S == 2 ? 2 : 1;
+        const int tid = threadIdx.x;
+        const bool worker = S < 8 || wv < 4;                          // wave-uniform
+        const float slope = a.act == 1 ? M3D_LEAKY_SLOPE : 1.f;
+        const int c4 = lane & 7;
+        int px[Q];
+        unsigned oq[Q], rq[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            px[q] = ((tid + q * 64 * S) >> 3) & 31;
+            const int m = m0 + px[q];
+            const bool ok = worker && m < a.M;
+            oq[q] = ok ? (unsigned)m * (unsigned)a.out_cs * 4u : M3D_BUF_OOB;
+            rq[q] = ok ? (unsigned)m * (unsigned)a.res_cs * 4u : M3D_BUF_OOB;
+        }
+        f32x4 scv[NT], shv[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int c = n0 + nt * 32 + 4 * c4;
+            scv[nt] = f32x4{1.f, 1.f, 1.f, 1.f};
+            shv[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (a.vec_out && c + 3 < a.Cout) {
+                if (a.scale) scv[nt] = *reinterpret_cast<const f32x4 *>(a.scale + c);
+                if (a.shift) shv[nt] = *reinterpret_cast<const f32x4 *>(a.shift + c);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (c + e < a.Cout) {
+                        if (a.scale) scv[nt][e] = a.scale[c + e];
+                        if (a.shift) shv[nt][e] = a.shift[c + e];
+                    }
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int c = n0 + nt * 32 + 4 * c4;
+            const bool full = a.vec_out && c + 3 < a.Cout;      // 16-byte accesses; else the 4-byte form, channel by channel
+            f32x4 rv[Q];
+            if (a.res) {
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    if (full) {
+                        rv[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rres, rq[q] + (unsigned)c * 4u, 0, 0));
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            rv[q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                rres, c + e < a.Cout ? rq[q] + (unsigned)(c + e) * 4u : M3D_BUF_OOB, 0, 0));
+                    }
+                }
+            }
+            if (nt) __syncthreads();            // the previous column tile has been read by everyone
+            // accumulator element r of lane (channel l31, half h) is pixel (r & 3) + 8 * (r >> 2) + 4 * h of the tile
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tileA[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + l31] = acc[nt][r];
+            __syncthreads();
+            if (worker) {
+                const bool tile_sig = a.sigmoid_from >= 0 && n0 + nt * 32 + 31 >= a.sigmoid_from;      // wave-uniform
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    const float *p = &tileS[px[q] * 32 + 4 * c4];
+                    f32x4 v = *reinterpret_cast<const f32x4 *>(p);
+#pragma unroll
+                    for (int s = 1; s < S; ++s)      // slice order
+                        if (s < a.splits) v = v + *reinterpret_cast<const f32x4 *>(p + s * 1024);
+                    v = conv_epi_affine(v, scv[nt], shv[nt], a.res ? rv[q] : v, a.res != nullptr, a.res_mode);
+                    v = conv_epi_act4(v, c, a.sigmoid_from, tile_sig, slope);
+                    if (full) {
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, oq[q] + (unsigned)c * 4u, 0, 0);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float pe = v[e];       // (bit-casting the vector element expression directly stores element 0)
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pe), rout,
+                                                                  c + e < a.Cout ? oq[q] + (unsigned)(c + e) * 4u : M3D_BUF_OOB, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+        TRACE();
+        return;
+    }
     if (a.splits > 1) {                        // raw partial sums; the reduce launch owns the epilogue
         const __amdgpu_buffer_rsrc_t rws = make_rsrc(a.ws, a.ws_bytes);
         const unsigned sbase = (unsigned)split * (unsigned)a.M;
@@ -371,21 +474,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 f32x4 v = *reinterpret_cast<const f32x4 *>(&tileA[(pr + 8 * q) * 32 + 4 * c4]);   // the wave's own writes: in order
-                if (a.res) v = a.res_mode ? (v + rv[q]) * scv[nt] + shv[nt] : v * scv[nt] + shv[nt] + rv[q];
-                else v = v * scv[nt] + shv[nt];
-                if (tile_sig) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = c + e >= a.sigmoid_from ? sigmoidf_(v[e]) : fmaxf(v[e], v[e] * slope);
-                } else {
-                    v = __builtin_elementwise_max(v, v * slope);
-                }
+                v = conv_epi_affine(v, scv[nt], shv[nt], a.res ? rv[q] : v, a.res != nullptr, a.res_mode);     // (common.h)
+                v = conv_epi_act4(v, c, a.sigmoid_from, tile_sig, slope);
                 if (c + 3 < a.Cout) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, oq[q] + (unsigned)c * 4u, 0, 0);
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[e]), rout,
+                    for (int e = 0; e < 4; ++e) {
+                        const float pe = v[e];       // (bit-casting the vector element expression directly stores element 0)
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pe), rout,
                                                               c + e < a.Cout ? oq[q] + (unsigned)(c + e) * 4u : M3D_BUF_OOB, 0, 0);
+                    }
                 }
             }
         }
@@ -411,11 +510,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = mb + (r & 3) + 8 * (r >> 2);
-            float v = acc[nt][r];
-            if (a.res) v = a.res_mode ? (v + rv[r]) * sc + sh : v * sc + sh + rv[r];
-            else v = v * sc + sh;
-            if (a.sigmoid_from >= 0 && co >= a.sigmoid_from) v = sigmoidf_(v);
-            else if (a.act == 1) v = fmaxf(v, v * M3D_LEAKY_SLOPE);
+            float v = conv_epi_affine(acc[nt][r], sc, sh, a.res ? rv[r] : 0.f, a.res != nullptr, a.res_mode);
+            v = conv_epi_act(v, a.sigmoid_from >= 0 && co >= a.sigmoid_from, a.act == 1 ? M3D_LEAKY_SLOPE : 1.f);
             const unsigned oo = (cok && m < a.M) ? ((unsigned)m * (unsigned)a.out_cs + (unsigned)co) * 4u : M3D_BUF_OOB;
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rout, oo, 0, 0);
         }
@@ -427,14 +523,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 // with enforce_min, still too few waves.  Measured (profiles/): below one wave per SIMD the LDS-tiled kernel wins and the
 // deformable gather wants two waves per SIMD, so thin layers are split along K until ~1800 waves exist (at least 4 steps of
 // 32 channels per split).  Tuning knobs (experiments only): M3D_CONV_WAVE_MIN / M3D_DCN_WAVE_MIN / M3D_CONV_WAVE_SPLITK=0.
-static int conv_wave_plan(const m3d_conv_desc *d, bool enforce_min, int *splits, int *ss_per)
+static int conv_wave_plan(const m3d_conv_desc *d, bool enforce_min, int *splits, int *ss_per, bool allow32 = false)
 {
     *splits = 1;
     *ss_per = d->kh * d->kw * (d->Cin / 32);
     if (d->out_nchw) return 0;
     if (d->dcn_offmask && d->kh * d->kw > 9) return 0;        // the sampling state of every tap lives in LDS (9 KB per wave)
-    if (d->Cin % 32 != 0 || d->Cout_pad % 64 != 0) return 0;
-    const int cw = d->Cout_pad % 128 == 0 ? 128 : 64;      // channels per wave
+    if (d->Cin % 32 != 0 || d->Cout_pad % 32 != 0) return 0;
+    // an odd multiple of 32 channels: the one-column-tile form, plain convolutions with shared weights, in-workgroup split only
+    if (d->Cout_pad % 64 != 0 && (!allow32 || d->dcn_offmask || d->wgt_img_stride)) return 0;
+    const int cw = d->Cout_pad % 128 == 0 ? 128 : (d->Cout_pad % 64 == 0 ? 64 : 32);      // channels per wave
     if (d->wgt_img_stride && (d->Ho * d->Wo) % 32 != 0) return 0;
     const long long M = (long long)d->N * d->Ho * d->Wo;
     const long long base = ((M + 31) / 32) * (d->Cout_pad / cw);
@@ -473,19 +571,36 @@ extern "C" int m3d_conv_wave_splitk_plan(const m3d_conv_desc *d, int *splits, lo
     static float dummy;
     t.splitk_ws = &dummy;
     int p;
-    const int waves = conv_wave_plan(&t, true, splits, &p);
+    const int waves = conv_wave_plan(&t, true, splits, &p, true);
     if (waves == 0) *splits = 1;
-    *ws_bytes = *splits > 1 ? (long long)*splits * d->N * d->Ho * d->Wo * d->Cout_pad * 4 : 0;
+    // Cout_pad % 64 == 32: the plan holds for m3d_conv_wave_forward_wgsplit alone, there is no workspace form
+    *ws_bytes = (*splits > 1 && d->Cout_pad % 64 == 0) ? (long long)*splits * d->N * d->Ho * d->Wo * d->Cout_pad * 4 : 0;
     return M3D_OK;
 }
 
-extern "C" int m3d_conv_wave_forward(const m3d_conv_desc *d, m3d_stream_t stream_)
+template <bool DEFORM, int NT>
+static void launch_wgsplit(const ConvWaveArgs &a, int S, int wgs, hipStream_t stream)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    M3D_REQUIRE(d && d->in && d->wgt && d->out, "conv_wave: null pointer");
+    constexpr int WPE = DEFORM ? 2 : 3;
+    switch (S) {
+    case 2: hipLaunchKernelGGL((conv_wave_kernel<DEFORM, NT, 4, WPE, 2>), dim3(wgs), dim3(128), 0, stream, a); break;
+    case 4: hipLaunchKernelGGL((conv_wave_kernel<DEFORM, NT, 4, WPE, 4>), dim3(wgs), dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL((conv_wave_kernel<DEFORM, NT, 4, WPE, 8>), dim3(wgs), dim3(512), 0, stream, a); break;
+    }
+}
+
+// wgsplit: the K split of the plan runs inside the workgroups (no workspace: the plan is computed as if one were given)
+static int conv_wave_run(const m3d_conv_desc *d_, hipStream_t stream, bool wgsplit)
+{
+    M3D_REQUIRE(d_ && d_->in && d_->wgt && d_->out, "conv_wave: null pointer");
+    m3d_conv_desc dd = *d_;
+    static float dummy;
+    if (wgsplit) { dd.splitk_ws = &dummy; dd.splitk_ws_bytes = 0; }
+    const m3d_conv_desc *d = &dd;
     int splits = 1, ss_per = 0;
-    const int waves = conv_wave_plan(d, false, &splits, &ss_per);       // the fill heuristic is advisory here
-    M3D_REQUIRE(waves > 0, "conv_wave: needs Cin %% 32 == 0, Cout_pad %% 64 == 0, NHWC output, Ho*Wo %% 32 == 0 with per-image weights");
+    const int waves = conv_wave_plan(d, false, &splits, &ss_per, wgsplit);       // the fill heuristic is advisory here
+    M3D_REQUIRE(waves > 0, "conv_wave: needs Cin %% 32 == 0, Cout_pad %% 64 == 0 (%% 32: plain, shared weights, wgsplit entry), NHWC output, "
+                           "Ho*Wo %% 32 == 0 with per-image weights");
     const int ho = (d->H + 2 * d->pad - (d->dil * (d->kh - 1) + 1)) / d->stride + 1;
     const int wo = (d->W + 2 * d->pad - (d->dil * (d->kw - 1) + 1)) / d->stride + 1;
     M3D_REQUIRE(ho == d->Ho && wo == d->Wo, "conv_wave: Ho/Wo mismatch");
@@ -503,7 +618,7 @@ extern "C" int m3d_conv_wave_forward(const m3d_conv_desc *d, m3d_stream_t stream
     a.in_cs = d->in_cs; a.out_cs = d->out_cs; a.res_cs = d->res_cs; a.om_cs = d->dcn_om_cs;
     a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.HoWo = d->Ho * d->Wo; a.Cout = d->Cout;
     a.kh = d->kh; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-    const int cw = d->Cout_pad % 128 == 0 ? 128 : 64;
+    const int cw = d->Cout_pad % 128 == 0 ? 128 : (d->Cout_pad % 64 == 0 ? 64 : 32);
     a.M = (int)M; a.KG = d->kh * d->kw * d->Cin / 8; a.tiles_n = d->Cout_pad / cw;
     a.act = d->act; a.res_mode = d->res_mode; a.sigmoid_from = d->sigmoid_from; a.w_img_stride = d->wgt_img_stride;
     static int vec_epi = -1;       // M3D_WAVE_VEC_EPILOGUE=0: 4-byte stores straight from the accumulators (A/B)
@@ -519,6 +634,23 @@ extern "C" int m3d_conv_wave_forward(const m3d_conv_desc *d, m3d_stream_t stream
     a.trace = g_conv_trace;
 #endif
     a.ws = nullptr; a.splits = 1; a.ss_per = ss_per; a.base_waves = waves; a.ws_bytes = 0;
+    if (splits > 1 && wgsplit) {
+        // slice s = wave s of the workgroup; the plan yields 2 <= splits <= 8 slices, 3 / 5 / 6 / 7 run on the next instantiated width
+        const int S = splits <= 2 ? 2 : (splits <= 4 ? 4 : 8);
+        M3D_REQUIRE(splits <= 8, "conv_wave: %d K slices do not fit a workgroup", splits);
+        a.splits = splits; a.base_waves = waves / splits;
+        if (cw == 128) {
+            if (d->dcn_offmask) launch_wgsplit<true, 4>(a, S, a.base_waves, stream);
+            else launch_wgsplit<false, 4>(a, S, a.base_waves, stream);
+        } else if (cw == 64) {
+            if (d->dcn_offmask) launch_wgsplit<true, 2>(a, S, a.base_waves, stream);
+            else launch_wgsplit<false, 2>(a, S, a.base_waves, stream);
+        } else {
+            launch_wgsplit<false, 1>(a, S, a.base_waves, stream);
+        }
+        M3D_LAUNCH_CHECK();
+        return M3D_OK;
+    }
     if (splits > 1) {
         const long long need = (long long)splits * M * d->Cout_pad * 4;
         M3D_REQUIRE(need <= d->splitk_ws_bytes && need < (1ll << 31) && ((uintptr_t)d->splitk_ws & 15) == 0,
@@ -545,6 +677,8 @@ extern "C" int m3d_conv_wave_forward(const m3d_conv_desc *d, m3d_stream_t stream
     if (cw == 128) {
         if (d->dcn_offmask) hipLaunchKernelGGL((conv_wave_kernel<true, 4>), dim3(waves), dim3(64), 0, stream, a);
         else hipLaunchKernelGGL((conv_wave_kernel<false, 4>), dim3(waves), dim3(64), 0, stream, a);
+    } else if (cw == 32) {
+        hipLaunchKernelGGL((conv_wave_kernel<false, 1>), dim3(waves), dim3(64), 0, stream, a);       // (wgsplit entry, unsplit plan)
     } else {
         if (d->dcn_offmask) hipLaunchKernelGGL((conv_wave_kernel<true, 2>), dim3(waves), dim3(64), 0, stream, a);
         else hipLaunchKernelGGL((conv_wave_kernel<false, 2>), dim3(waves), dim3(64), 0, stream, a);
@@ -558,4 +692,31 @@ extern "C" int m3d_conv_wave_forward(const m3d_conv_desc *d, m3d_stream_t stream
         return m3d_launch_splitk_reduce(r, stream);
     }
     return M3D_OK;
+}
+
+extern "C" int m3d_conv_wave_forward(const m3d_conv_desc *d, m3d_stream_t stream)
+{
+    return conv_wave_run(d, (hipStream_t)stream, false);
+}
+
+// What m3d_conv_wave_forward_wgsplit launches for this descriptor: *slices = K slices of the plan (fill threshold advisory, as in
+// the forward call; 1 = unsplit), *width = waves per workgroup (the next of 1 / 2 / 4 / 8)
+extern "C" int m3d_conv_wave_wgsplit_width(const m3d_conv_desc *d, int *slices, int *width)
+{
+    M3D_REQUIRE(d && slices && width, "conv_wave_wgsplit_width: null pointer");
+    m3d_conv_desc t = *d;
+    static float dummy;
+    t.splitk_ws = &dummy;
+    int p;
+    const int waves = conv_wave_plan(&t, false, slices, &p, true);
+    M3D_REQUIRE(waves > 0 && *slices <= 8, "conv_wave_wgsplit_width: the wave kernel does not apply to this descriptor");
+    *width = *slices <= 1 ? 1 : (*slices <= 2 ? 2 : (*slices <= 4 ? 4 : 8));
+    return M3D_OK;
+}
+
+// The same layer with the plan's K split inside the workgroups (conv_wave_kernel<.., S>): splitk_ws is ignored, nothing is
+// allocated, one launch.  A layer the plan does not split runs as m3d_conv_wave_forward runs it without a workspace.
+extern "C" int m3d_conv_wave_forward_wgsplit(const m3d_conv_desc *d, m3d_stream_t stream)
+{
+    return conv_wave_run(d, (hipStream_t)stream, true);
 }

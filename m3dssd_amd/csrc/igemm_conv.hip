@@ -391,6 +391,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SplitkReduceAr
     const float *p = a.ws + (size_t)m * a.Cout_pad + co0;
     f32x4 v = *reinterpret_cast<const f32x4 *>(p);
     for (int s = 1; s < a.splits; ++s) v = v + *reinterpret_cast<const f32x4 *>(p + s * stride);
+    const float slope = a.act == 1 ? M3D_LEAKY_SLOPE : 1.f;
     f32x4 o;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -399,14 +400,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SplitkReduceAr
         if (co < a.Cout) {
             const float sc = a.scale ? a.scale[co] : 1.f;
             const float sh = a.shift ? a.shift[co] : 0.f;
-            if (a.res) {
-                const float rv = a.res[(size_t)m * a.res_cs + co];
-                x = a.res_mode ? (x + rv) * sc + sh : x * sc + sh + rv;
-            } else {
-                x = x * sc + sh;
-            }
-            if (a.sigmoid_from >= 0 && co >= a.sigmoid_from) x = sigmoidf_(x);
-            else if (a.act == 1) x = leaky(x);
+            const float rv = a.res ? a.res[(size_t)m * a.res_cs + co] : 0.f;
+            x = conv_epi_affine(x, sc, sh, rv, a.res != nullptr, a.res_mode);     // (common.h: shared with the wave kernel)
+            x = conv_epi_act(x, a.sigmoid_from >= 0 && co >= a.sigmoid_from, slope);
         }
         o[q] = x;
     }

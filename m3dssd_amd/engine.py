@@ -169,6 +169,12 @@ USE_ANAB_WAVE = os.environ.get("M3D_ANAB_WAVE", "1") != "0"
 USE_ANAB_NESTED = os.environ.get("M3D_ANAB_NESTED", "1") != "0"
 USE_DCN_WAVE = os.environ.get("M3D_DCN_WAVE", "1") != "0"
 USE_CONV_WAVE = os.environ.get("M3D_CONV_WAVE", "1") != "0"
+# thin wave-kernel layers: the K slices are the waves of one workgroup (m3d_conv_wave_forward_wgsplit, no workspace);
+# M3D_CONV_WAVE_WGSPLIT=0 restores the global split (workspace + reduce launch) for A/B runs
+USE_CONV_WAVE_WGSPLIT = os.environ.get("M3D_CONV_WAVE_WGSPLIT", "1") != "0"
+# the 27 -> 32 channel offset / mask convs of the 24x80 maps (plans of up to 4 slices) on the one-column-tile form of the same
+# kernel (0: split-K igemm).  The 12x40 one (8 slices) stays on the igemm: 29.7 us there against ~27 us for igemm + reduce.
+USE_OFFMASK_WAVE = os.environ.get("M3D_OFFMASK_WAVE", "1") != "0"
 USE_WINO = os.environ.get("M3D_WINO", "1") != "0"
 USE_WINO44 = os.environ.get("M3D_WINO44", "1") != "0"
 # F(4x4,3x3) workgroups (16 tiles x 128 or 64 channels, one per CU, 256 CUs): 128-channel workgroups need >= 200 of them; the
@@ -494,11 +500,18 @@ class Engine:
             return
         if (pc is not None and wgt_ptr is None and planar is None and (USE_DCN_WAVE if om is not None else USE_CONV_WAVE)
                 and x.cs % 32 == 0 and x.ptr % 128 == 0 and pc.cin_pad == x.c):
-            # wave-granular kernel, no workgroup barriers (csrc/dcn_wave.hip); thin layers are split along K across waves
+            # wave-granular kernel (csrc/dcn_wave.hip); thin layers are split along K across the waves of a workgroup
             wsplits, wbytes = ctypes.c_int(), ctypes.c_longlong()
             _hip.check(L.m3d_conv_wave_splitk_plan(ref, ctypes.byref(wsplits), ctypes.byref(wbytes)))
+            if wsplits.value > 1 and USE_CONV_WAVE_WGSPLIT and (d.Cout_pad % 64 == 0 or (USE_OFFMASK_WAVE and wsplits.value <= 4)):
+                # (a plan that splits has already passed the fill threshold WITH its split)
+                frag = pc.frag()
+                d.wgt = frag.data_ptr()
+                kind = "conv_wave<%s>" % ",".join((["deform"] if om is not None else []) + ["wgsplit%d" % wsplits.value])
+                plan.ops.append((name, kind, flops_true, lambda st: _hip.check(L.m3d_conv_wave_forward_wgsplit(ref, st)), d))
+                return
             ws = None
-            if wsplits.value > 1:
+            if wsplits.value > 1 and wbytes.value > 0:
                 ws = torch.empty(wbytes.value // 4, device=self.device, dtype=torch.float32)
                 d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), wbytes.value
             if L.m3d_conv_wave_applicable(ref) > 0:
