@@ -387,9 +387,10 @@ int m3d_frontend2_bf16_forward(const void *img, int is_u8, int img_h, int img_w,
  * P.V GEMM sequence (m3d_conv_bf16_forward with per-image weights, m3d_softmax_rows_bf16).  q bf16 [B*HW][q_cs] (channels
  * [Ck, Ck_pad) zero), khat bf16 [B][keys_pad][Ck_pad], vhatT bf16 [B][Cv][keys_pad] (rows >= keys ignored), res bf16 [B*HW][res_cs]
  * or NULL, scale / shift fp32 [Cv] or NULL, out bf16 [B*HW][out_cs].  Built for Ck_pad = 192, Cv = 128; HW % 128 == 0.
- * PRECONDITION (not checked): the padding -- khat rows [keys, keys_pad) and vhatT columns [keys, keys_pad) -- must hold FINITE
- * values (zeros; m3d_anab_pool_nested* leave what the caller allocated, the engine allocates with zeros): the padded keys get
- * probability 0, and 0 * (Inf | NaN) in the P.V product would be NaN. */
+ * The padding -- khat rows [keys, keys_pad) and vhatT columns [keys, keys_pad) -- is ignored whatever it holds (NaN included): the
+ * padded keys get probability 0 and their value columns are replaced by zeros when the last key tile is staged.  (The three-launch
+ * form still multiplies the padding: m3d_anab_pool_nested* leave what the caller allocated, the engine allocates with zeros.)
+ * The columns [Ck, Ck_pad) of the valid khat rows are operand (there is no Ck argument): finite, normally zero. */
 int m3d_anab_attend_bf16(const void *q, int q_cs, const void *khat, const void *vhatT, int B, int HW, int Ck_pad, int keys,
                          int keys_pad, int Cv, const void *res, int res_cs, const float *scale, const float *shift, int act,
                          void *out, int out_cs, m3d_stream_t stream);
@@ -639,7 +640,7 @@ int m3d_anab_pool_nested_bf16_ex(const void *kv, int kv_cs, const float *s, int 
  * frag = 0; Ck in {64, 128, 168} with Cv = 128, or Ck = 168 with Cv = 256 (DLA-102: two workgroups per pixel tile, one per
  * half of the value channels), HW % 128 == 0, keys_pad % 32 == 0; res_mode as in m3d_conv_desc (0: + res behind the
  * affine, 1: before it); scale / shift / res may be NULL.
- * PRECONDITION (not checked): khat rows [keys, keys_pad) and vhatT columns [keys, keys_pad) hold finite values (zeros), as for
+ * khat rows [keys, keys_pad), khat columns [Ck, k_cs) and vhatT columns [keys, keys_pad) are ignored whatever they hold, as for
  * m3d_anab_attend_bf16. */
 int m3d_anab_attend_f32(const float *q, int q_cs, const float *khat, int k_cs, const float *vhatT, int B, int HW, int Ck,
                         int keys, int keys_pad, int Cv, const float *res, int res_cs, int res_mode, const float *scale,

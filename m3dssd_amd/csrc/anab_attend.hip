@@ -76,7 +76,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             vr[p] = *reinterpret_cast<const f32x4 *>(vimg + (size_t)row * a.keys_pad + AF_KT * t + c * 4);
         }
     };
-    auto stage_store = [&]() __attribute__((always_inline)) {
+    auto stage_store = [&](int t) __attribute__((always_inline)) {      // t: the tile stage_load brought
+        // (wave-uniform) the ragged last tile: the columns of vhat^T past `keys` are not ours: their probability is 0, and
+        // 0 * (NaN | Inf) would be NaN in the P.V product
+        if (AF_KT * t + AF_KT > a.keys) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (AF_KT * t + ((tid + 256 * p) & 7) * 4 + e >= a.keys) vr[p][e] = 0.f;
+        }
         __syncthreads();                                        // every wave is done with the previous tile
 #pragma unroll
         for (int p = 0; p < KPT; ++p) {
@@ -99,7 +108,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float l = 0.f, m = -INFINITY;
     const int T = (a.keys + AF_KT - 1) / AF_KT;
     stage_load(0);
-    stage_store();
+    stage_store(0);
     for (int t = 0; t < T; ++t) {
         if (t + 1 < T) stage_load(t + 1);                       // (wave-uniform) in flight under this tile's MFMAs
         // ---- S tile: rows = the 32 keys of the tile, columns = the wave's pixels ---------------------------------------------------
@@ -147,7 +156,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int jj = 0; jj < 4; ++jj) o[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[jj], e[4 * i + jj], o[j], 0, 0, 0);
             }
         }
-        if (t + 1 < T) stage_store();
+        if (t + 1 < T) stage_store(t + 1);
     }
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;

@@ -82,7 +82,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONLINE ? 2 
             }
         }
     };
-    auto stage_store = [&](bool with_v, const u32x4 (&kr)[3], const u32x4 (&vr)[2]) __attribute__((always_inline)) {
+    auto stage_store = [&](int t, bool with_v, const u32x4 (&kr)[3], u32x4 (&vr)[2]) __attribute__((always_inline)) {   // t: the tile loaded
+        // (wave-uniform) the ragged last tile: the columns of vhat^T past `keys` are not ours: their probability is 0, and
+        // 0 * (NaN | Inf) would be NaN in the P.V product
+        if (with_v && 32 * t + 32 > a.keys) {
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const int k0 = 32 * t + ((tid + 256 * p) & 3) * 8 + 2 * w;
+                    vr[p][w] &= (k0 < a.keys ? 0x0000FFFFu : 0u) | (k0 + 1 < a.keys ? 0xFFFF0000u : 0u);
+                }
+        }
         __syncthreads();                                    // every wave is done with the previous tile
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
@@ -103,7 +114,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONLINE ? 2 
     auto stage = [&](int t, bool with_v) __attribute__((always_inline)) {
         u32x4 kr[3], vr[2];
         stage_load(t, with_v, kr, vr);
-        stage_store(with_v, kr, vr);
+        stage_store(t, with_v, kr, vr);
     };
     // S tile: rows = the 32 keys of tile t, columns = the wave's pixels
     const int ksw = (l31 >> 1) & 7;
@@ -186,7 +197,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONLINE ? 2 
                 }
             }
 #if !(AN_ABL & 1)
-            if (t + 1 < T) stage_store(true, kr, vr);
+            if (t + 1 < T) stage_store(t + 1, true, kr, vr);
 #endif
         }
     } else {

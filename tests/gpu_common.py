@@ -191,20 +191,21 @@ def _stream():
 
 
 # ------------------------------------------------------------------------------------ bf16 conv descriptor (tests/test_gpu_bf16.py, tests/test_gpu_exact.py)
-def _nhwc16(x, cs=None):
-    """[N,C,H,W] fp32 -> bf16 NHWC device tensor with pixel stride cs (extra channels filled with a sentinel)."""
+def _nhwc16(x, cs=None, pad_value=768.0):
+    """[N,C,H,W] fp32 -> bf16 NHWC device tensor with pixel stride cs (extra channels filled with a sentinel: pad_value)."""
     n, c, h, w = x.shape
     cs = c if cs is None else cs
-    t = torch.full((n, h, w, cs), 768.0, dtype=torch.bfloat16)
+    t = torch.full((n, h, w, cs), pad_value, dtype=torch.bfloat16)
     t[..., :c] = x.permute(0, 2, 3, 1).to(torch.bfloat16)
     return t.contiguous().to(_dev())
 
 
 def _run_conv(x, wt, bias=None, bn=None, stride=1, pad=0, act=0, res=None, res_mode=0, sigmoid_from=-1, out_mode=0, om=None,
-              in_cs=None, variant=None, patch=False, wide=False, alias_res_out=False, affine=None):
+              in_cs=None, variant=None, patch=False, wide=False, alias_res_out=False, affine=None, pad_value=768.0, ws_word=7):
     """Through the C ABI.  Returns [N, Cout, Ho, Wo] fp32 (bf16 outputs widened).  alias_res_out: res = out (in-place residual);
     returns the call's status code and error text instead.  affine = (scale, shift): the epilogue's per-channel fp32 scale / shift
-    given directly (instead of folding bias / bn)."""
+    given directly (instead of folding bias / bn).  pad_value: what the input channels between Cin and in_cs hold (the kernel
+    must ignore them); ws_word: what every flag word of the patch kernel's dcn_ws holds on entry."""
     from m3dssd_amd import _hip
     from m3dssd_amd.engine_bf16 import pack_conv_bf16
     L = _hip.lib()
@@ -212,7 +213,7 @@ def _run_conv(x, wt, bias=None, bn=None, stride=1, pad=0, act=0, res=None, res_m
     n, c, h, w = x.shape
     co, _, kh, kw = wt.shape
     ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-    xin = _nhwc16(x, in_cs)
+    xin = _nhwc16(x, in_cs, pad_value)
     wp, kpad = pack_conv_bf16(wt, None, None, dev)
     d = _hip.ConvBf16Desc()
     d.inp, d.in_cs, d.N, d.H, d.W, d.Cin = xin.data_ptr(), xin.shape[3], n, h, w, c
@@ -249,7 +250,7 @@ def _run_conv(x, wt, bias=None, bn=None, stride=1, pad=0, act=0, res=None, res_m
         keep.append(o)
         if patch:           # LDS-patch DCNv2 kernel: fp16 weight copy + the device scratch of the |offset| bound
             nws = max(256, _hip.lib().m3d_conv_bf16_dcn_ws_bytes(n, ho, wo) // 4)
-            w16, ws = wp.float().to(torch.float16).contiguous(), torch.full((nws,), 7, device=dev, dtype=torch.int32)
+            w16, ws = wp.float().to(torch.float16).contiguous(), torch.full((nws,), ws_word, device=dev, dtype=torch.int32)
             d.wgt_f16, d.dcn_ws, d.dcn_ws_bytes = w16.data_ptr(), ws.data_ptr(), 4 * nws
             keep += [w16, ws]
     if out_mode == 0:
