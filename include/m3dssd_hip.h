@@ -80,7 +80,8 @@ const char *m3d_last_error(void);
  *   added under 5: m3d_dcn_v2_backward, m3d_dcn_v2_backward_workspace_bytes (additive; nothing existing changed);
  *                  m3d_rpn_targets, m3d_rpn_loss, m3d_rpn_loss_workspace_bytes (additive);
  *                  m3d_topk_decode_planar_mw, m3d_topk_decode_mw_workspace_bytes (additive);
- *                  m3d_conv_wave_forward_wgsplit, m3d_conv_wave_wgsplit_width (additive). */
+ *                  m3d_conv_wave_forward_wgsplit, m3d_conv_wave_wgsplit_width (additive);
+ *                  m3d_need_rows, m3d_need_rows_workspace_bytes, m3d_head_mlp_forward_rows, m3d_align_offsets_gated (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -428,6 +429,13 @@ int m3d_head_mlp_forward(const m3d_mlp_desc *d, m3d_stream_t stream);
 /* n (<= 16) independent heads of the same depth, M, Cin and Cout_pad in ONE launch (grid.y = head): the regression heads
  * that read the same aligned feature map (M3d_inference_align.py:139-176) have no mutual dependency. */
 int m3d_head_mlp_forward_batched(const m3d_mlp_desc *d, int n, m3d_stream_t stream);
+/* Row-list form of the batched launch (three-layer heads with Cout_pad = 64): head i with bit i of sparse_head_mask set is
+ * evaluated only at the *n_rows (device) pixels rows[j] = n * HW + pix (what m3d_need_rows writes) -- tile t of the launch takes
+ * rows [64t, 64t + 64) of the list -- and leaves every other element of its output planes as it is; at the listed pixels the
+ * values are bit-equal to the dense launch.  Heads with a clear bit run as in m3d_head_mlp_forward_batched.  Nothing is read
+ * back: the grid is sized for the dense M and the tiles past the list return at once. */
+int m3d_head_mlp_forward_rows(const m3d_mlp_desc *d, int n, const int *rows, const int *n_rows, unsigned int sparse_head_mask,
+                              m3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Drop-in for dcn_v2_cuda_forward: NCHW contiguous fp32 device tensors, exactly the reference
@@ -599,6 +607,12 @@ int m3d_align_offsets(int mode, const int *sel_idx, const float *sel_prob, float
                       const float *bbox_x, const float *bbox_y, const float *anchor_wh, float mean_x,
                       float std_x, float mean_y, float std_y, float *offmask, int om_cs, int B, int A, int HW,
                       int kk, long long box_img_stride, m3d_stream_t stream);
+/* mode 1 where bbox_x / bbox_y hold values only at the pixels with need[b*HW + p] != 0 (m3d_need_rows): the same offsets there,
+ * offset 0 at the other pixels, whose bbox_x / bbox_y are not read (they may hold anything); the mask channel everywhere. */
+int m3d_align_offsets_gated(const int *sel_idx, const float *sel_prob, float thresh, const float *bbox_x, const float *bbox_y,
+                            const float *anchor_wh, float mean_x, float std_x, float mean_y, float std_y,
+                            const unsigned char *need, float *offmask, int om_cs, int B, int A, int HW,
+                            long long box_img_stride, m3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * ANAB (asymmetric non-local block).
@@ -698,6 +712,16 @@ int m3d_topk_decode_planar_mw(const unsigned int *score_bits, const float *cls_p
                               const float *anchors, const float *means, const float *stds, const float *scale, float *aboxes,
                               int *rows_out, void *workspace, long long workspace_bytes, int B, int A, int HW, int k,
                               int wgs_per_image, m3d_stream_t stream);
+/* The pixels whose box-head outputs the top-k decode can read.  score_bits [B][A*HW]: the monotone keys (row = a*HW + pix).
+ *   thresh [B]    the exact k-th largest key of each image (k >= A*HW: the smallest key)
+ *   need [B*HW]   1 where any of the pixel's A keys is >= thresh[b], else 0 (keys equal to the threshold only enlarge the set)
+ *   rows [B*HW]   the needed pixels as b*HW + pix, ascending; entries past *n_rows are not written
+ *   n_rows        their number, on the device
+ * Six launches whatever the data (graph-capturable), integer atomics only, nothing read back, nothing carried over between
+ * calls.  workspace: m3d_need_rows_workspace_bytes(B, HW)  (-1 for a non-positive argument). */
+long long m3d_need_rows_workspace_bytes(int B, int HW);
+int m3d_need_rows(const unsigned int *score_bits, int B, int A, int HW, int k, unsigned int *thresh, unsigned char *need,
+                  int *rows, int *n_rows, void *workspace, long long workspace_bytes, m3d_stream_t stream);
 /* Decode `n_rows` selected rows per image -> aboxes [B][n_rows][14]
  * (x1,y1,x2,y2,score,cls,x3d,y3d,z3d,w3d,h3d,l3d,ry3d,anchor). */
 int m3d_decode_rows(const long long *rows /*[B][n_rows] row ids*/, const float *prob, const float *bbox_2d,

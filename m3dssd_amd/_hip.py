@@ -150,6 +150,7 @@ SIGNATURES = {
     "m3d_softmax_rows_bf16": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
     "m3d_head_mlp_forward": (c_int, [ctypes.POINTER(MlpDesc), P]),
     "m3d_head_mlp_forward_batched": (c_int, [ctypes.POINTER(MlpDesc), c_int, P]),
+    "m3d_head_mlp_forward_rows": (c_int, [ctypes.POINTER(MlpDesc), c_int, P, P, ctypes.c_uint, P]),
     "m3d_wino_conv3x3_forward": (c_int, [ctypes.POINTER(ConvDesc), P]),
     "m3d_wino_conv3x3_forward_ex": (c_int, [ctypes.POINTER(ConvDesc), c_int, P]),
     "m3d_wino_conv3x3_splitk_plan": (c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int), ctypes.POINTER(c_ll)]),
@@ -195,6 +196,7 @@ SIGNATURES = {
     "m3d_anchor_select_keys": (c_int, [P] + [c_int] * 3 + [P, P, P, P]),
     "m3d_fg_top1": (c_int, [P, c_int, c_int, c_int, P, P, P]),
     "m3d_align_offsets": (c_int, [c_int, P, P, c_float, P, P, P, P] + [c_float] * 4 + [P] + [c_int] * 5 + [c_ll, P]),
+    "m3d_align_offsets_gated": (c_int, [P, P, c_float, P, P, P] + [c_float] * 4 + [P, P] + [c_int] * 4 + [c_ll, P]),
     "m3d_anab_pool_partial": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P] + [c_int] * 5 + [P]),
     "m3d_anab_pool_finish": (c_int, [P, P, P] + [c_int] * 4 + [P, c_int, c_int, P, c_int, c_int, P]),
     "m3d_anab_pool_nested_scratch_bytes": (c_ll, [c_int, c_int]),
@@ -211,6 +213,8 @@ SIGNATURES = {
     "m3d_score_keys_planar": (c_int, [P, P, c_int, c_int, c_int, P]),
     "m3d_topk_decode_planar": (c_int, [P] * 11 + [c_ll] + [c_int] * 4 + [P]),
     "m3d_topk_decode_mw_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
+    "m3d_need_rows_workspace_bytes": (c_ll, [c_int, c_int]),
+    "m3d_need_rows": (c_int, [P] + [c_int] * 4 + [P] * 5 + [c_ll, P]),
     "m3d_topk_decode_planar_mw": (c_int, [P] * 11 + [c_ll] + [c_int] * 5 + [P]),
     "m3d_select_post": (c_int, [P] * 3 + [c_int] * 3 + [P, P, P]),
     "m3d_nms_workspace_bytes": (c_ll, [c_int, c_int]),

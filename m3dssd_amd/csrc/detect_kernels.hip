@@ -551,6 +551,190 @@ extern "C" int m3d_topk_decode_planar_mw(const unsigned int *score_bits, const f
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Needed pixels (m3d_need_rows): the detection stage decodes the k highest-scoring rows of an image and nothing else, and row
+// a * HW + pix belongs to pixel pix, so a box head whose output feeds only the decode is needed at the pixels that hold one of
+// those rows.  T_b = the exact k-th largest 32-bit key of image b by a three-digit radix select (11 + 11 + 10 bits; the top 11
+// bits alone put every score in [0.5, 1) into four bins), need[b][pix] = any of the pixel's A keys >= T_b (ties at T_b only
+// enlarge the set), rows = the needed pixels b * HW + pix in ascending order, *n_rows their number.
+//   zero    : the three global histograms of every image
+//   hist<l> : every workgroup finds the bins of the digits above l from the global histograms, then histograms digit l of its
+//             slice's keys that carry that prefix (LDS atomics, non-zero bins added to the global histogram)
+//   mark    : T_b from the three histograms; one workgroup per 256 pixels sets need[] and counts its pixels
+//   compact : the slice's place in the list = the counts of the slices in front of it; ordered scan inside the slice
+// Integer atomics only, fixed grids, every count stays on the device: graph-capturable.
+#define NEED_PX 256                      // pixels per workgroup of the mark / compact launches
+
+struct NeedArgs {
+    const unsigned int *score_bits;   // [B][A*HW]
+    unsigned *hist;                   // [B][3][2048]
+    unsigned *cnt;                    // [B][nsl] needed pixels of every 256-pixel slice
+    unsigned *thresh;                 // [B]
+    unsigned char *need;              // [B][HW]
+    int *rows, *n_rows;
+    int R, A, HW, k, nsl, B;
+};
+
+// the digits above level LV of the k-th largest key: -> prefix (the key bits above digit LV), *need = its rank inside that prefix
+template <int LV>
+__device__ __forceinline__ unsigned need_prefix(const NeedArgs &a, int img, unsigned *hist, unsigned *wave_tot, unsigned *s_bin,
+                                                unsigned *s_above, int tid, unsigned *need)
+{
+    unsigned prefix = 0;
+#pragma unroll
+    for (int l = 0; l < LV; ++l) {
+        const unsigned *gh = a.hist + ((size_t)img * 3 + l) * 2048;
+        for (int i = tid; i < 2048; i += TOPK_NT) hist[i] = gh[i];
+        __syncthreads();
+        topk_find_bin(hist, *need, wave_tot, tid, s_bin, s_above);
+        prefix = (prefix << (l == 2 ? 10 : 11)) | *s_bin;
+        *need -= *s_above;
+    }
+    return prefix;
+}
+
+__global__ __launch_bounds__(TOPK_NT) void need_zero_kernel(NeedArgs a)
+{
+    for (int i = threadIdx.x; i < 3 * 2048; i += TOPK_NT) a.hist[(size_t)blockIdx.x * 3 * 2048 + i] = 0;
+}
+
+template <int LV>
+__global__ __launch_bounds__(TOPK_NT) void need_hist_kernel(NeedArgs a)
+{
+    __shared__ unsigned hist[2048];
+    __shared__ unsigned wave_tot[16];
+    __shared__ unsigned s_bin, s_above;
+    const int img = blockIdx.y, tid = threadIdx.x;
+    const TopkSlice sl = topk_slice(a.R, blockIdx.x, gridDim.x);
+    if (sl.lo >= sl.hi) return;                            // (uniform over the workgroup)
+    unsigned need = (unsigned)a.k;
+    const unsigned prefix = need_prefix<LV>(a, img, hist, wave_tot, &s_bin, &s_above, tid, &need);
+    __syncthreads();
+    for (int i = tid; i < 2048; i += TOPK_NT) hist[i] = 0;
+    __syncthreads();
+    constexpr int sh = LV == 0 ? 21 : LV == 1 ? 10 : 0;
+    constexpr unsigned mk = LV == 2 ? 0x3FFu : 0x7FFu;
+    constexpr int psh = LV == 1 ? 21 : 10;                 // (LV > 0) the bits above this digit
+    topk_for_keys(a.score_bits + (size_t)img * a.R, sl, tid, [&](unsigned s, int) {
+        if (LV == 0 || (s >> psh) == prefix) atomicAdd(&hist[(s >> sh) & mk], 1u);
+    });
+    __syncthreads();
+    unsigned *gh = a.hist + ((size_t)img * 3 + LV) * 2048;
+    for (int i = tid; i < 2048; i += TOPK_NT) {
+        const unsigned h = hist[i];
+        if (h) atomicAdd(&gh[i], h);
+    }
+}
+
+__global__ __launch_bounds__(TOPK_NT) void need_mark_kernel(NeedArgs a)
+{
+    __shared__ unsigned hist[2048];
+    __shared__ unsigned wave_tot[16];
+    __shared__ unsigned s_bin, s_above, s_cnt;
+    __shared__ unsigned s_need[NEED_PX];
+    const int img = blockIdx.y, tid = threadIdx.x;
+    if (tid < NEED_PX) s_need[tid] = 0;
+    if (tid == 0) s_cnt = 0;
+    unsigned need = (unsigned)a.k;
+    const unsigned T = need_prefix<3>(a, img, hist, wave_tot, &s_bin, &s_above, tid, &need);
+    const int pl = tid & (NEED_PX - 1), ag = tid / NEED_PX;            // four threads per pixel, each takes every fourth anchor
+    const int p = blockIdx.x * NEED_PX + pl;
+    if (p < a.HW) {
+        const unsigned int *sc = a.score_bits + (size_t)img * a.R + p;
+        bool f = false;
+        for (int an = ag; an < a.A; an += TOPK_NT / NEED_PX) f |= sc[(size_t)an * a.HW] >= T;
+        if (f) s_need[pl] = 1;
+    }
+    __syncthreads();
+    if (tid < NEED_PX) {                                               // (whole waves)
+        const bool f = p < a.HW && s_need[tid];
+        if (p < a.HW) a.need[(size_t)img * a.HW + p] = f ? 1 : 0;
+        const unsigned c = (unsigned)__popcll(__ballot(f));
+        if ((tid & 63) == 0 && c) atomicAdd(&s_cnt, c);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.cnt[(size_t)img * a.nsl + blockIdx.x] = s_cnt;
+        if (blockIdx.x == 0) a.thresh[img] = T;
+    }
+}
+
+__global__ __launch_bounds__(NEED_PX) void need_compact_kernel(NeedArgs a)
+{
+    __shared__ unsigned wave_tot[16];
+    __shared__ unsigned s_part[NEED_PX / 64][2];
+    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int me = img * a.nsl + blockIdx.x, total = a.B * a.nsl;
+    unsigned before = 0, all = 0;
+    for (int i = tid; i < total; i += NEED_PX) {
+        const unsigned v = a.cnt[i];
+        all += v;
+        if (i < me) before += v;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        before += __shfl_xor(before, d, 64);
+        all += __shfl_xor(all, d, 64);
+    }
+    if (lane == 0) { s_part[wave][0] = before; s_part[wave][1] = all; }
+    __syncthreads();
+    before = 0; all = 0;
+#pragma unroll
+    for (int w = 0; w < NEED_PX / 64; ++w) { before += s_part[w][0]; all += s_part[w][1]; }
+    const int p = blockIdx.x * NEED_PX + tid;
+    const unsigned f = (p < a.HW && a.need[(size_t)img * a.HW + p]) ? 1u : 0u;
+    const unsigned ex = block_excl_scan(f, wave_tot, tid);
+    if (f) a.rows[before + ex] = img * a.HW + p;
+    if (me == 0 && tid == 0) *a.n_rows = (int)all;
+}
+
+extern "C" long long m3d_need_rows_workspace_bytes(int B, int HW)
+{
+    if (B < 1 || HW < 1) return -1;
+    return (long long)B * 3 * 2048 * (long long)sizeof(unsigned) + (long long)B * cdiv(HW, NEED_PX) * (long long)sizeof(unsigned);
+}
+
+extern "C" int m3d_need_rows(const unsigned int *score_bits, int B, int A, int HW, int k, unsigned int *thresh,
+                             unsigned char *need, int *rows, int *n_rows, void *workspace, long long workspace_bytes,
+                             m3d_stream_t stream)
+{
+    M3D_REQUIRE(score_bits && thresh && need && rows && n_rows && workspace, "need_rows: null pointer");
+    M3D_REQUIRE(B >= 1 && A >= 1 && HW >= 1 && (long long)A * HW < (1ll << 31) && (long long)B * HW < (1ll << 31) &&
+                    cdiv(HW, NEED_PX) <= 65535 && B <= 65535,
+                "need_rows: bad B / A / HW (%d, %d, %d)", B, A, HW);
+    M3D_REQUIRE(k >= 1, "need_rows: k (%d) must be positive", k);
+    M3D_REQUIRE(((uintptr_t)score_bits & 15) == 0, "need_rows: score_bits must be 16-byte aligned");
+    const long long nb = m3d_need_rows_workspace_bytes(B, HW);
+    if (workspace_bytes < nb) {
+        m3d_set_error("need_rows: workspace of %lld bytes, %lld needed", workspace_bytes, nb);
+        return M3D_E_WORKSPACE;
+    }
+    NeedArgs a;
+    a.score_bits = score_bits;
+    a.hist = (unsigned *)workspace;
+    a.cnt = a.hist + (size_t)B * 3 * 2048;
+    a.thresh = thresh; a.need = need; a.rows = rows; a.n_rows = n_rows;
+    a.R = A * HW; a.A = A; a.HW = HW; a.B = B;
+    a.k = k < a.R ? k : a.R;                               // k >= A * HW: the threshold is the smallest key, every pixel is needed
+    a.nsl = cdiv(HW, NEED_PX);
+    const int units = (a.R & 3) ? a.R : (a.R >> 2);
+    const int wgs = max(1, min(TOPK_MW_DEFAULT_WGS, cdiv(units, TOPK_NT)));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(need_zero_kernel, dim3(B), dim3(TOPK_NT), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(need_hist_kernel<0>, dim3(wgs, B), dim3(TOPK_NT), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(need_hist_kernel<1>, dim3(wgs, B), dim3(TOPK_NT), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(need_hist_kernel<2>, dim3(wgs, B), dim3(TOPK_NT), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(need_mark_kernel, dim3(a.nsl, B), dim3(TOPK_NT), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(need_compact_kernel, dim3(a.nsl, B), dim3(NEED_PX), 0, st, a);
+    M3D_LAUNCH_CHECK();
+    return M3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Kept rows -> fixed-size blocks.  block [B][post + 1][14]: rows [0, min(num, post)) = aboxes[keep[j]], the rest zero;
 // row `post` = (count, 0, ...).  counts [B] gets the same count as int32.
 __global__ void select_post_kernel(const float *__restrict__ aboxes, const int *__restrict__ keep, const int *__restrict__ num,

@@ -60,17 +60,37 @@ struct MlpBatch {
     MlpArgs head[MLP_MAX_HEADS];                      // blockIdx.y selects the head (same M for all of them)
 };
 
+// Row-list form (m3d_head_mlp_forward_rows): a head whose bit of `sparse` is set runs on the listed pixels only -- tile t is
+// rows[64t .. 64t+64) of the list, gathered at staging, scattered at the planar store; a head whose bit is clear runs densely.
+struct MlpBatchRows : MlpBatch {
+    const int *rows;                                  // global pixel indices (n * HW + pix), *n_rows of them
+    const int *n_rows;                                // on the device
+    unsigned sparse;                                  // bit i: head i takes the list
+};
+
 // CIN: input channels of the staged tile -- 128 (DLA-34, three layers), 256 (two layers, or the three-layer heads of DLA-102, whose
 // first layer reads the 256-channel tile and overwrites it in place like the second does)
-template <bool HAS_L1, int N3, int CIN = HAS_L1 ? 128 : 256>
-__global__ __launch_bounds__(256) void head_mlp_kernel(const MlpBatch batch)
+// ROWS: the row-list form.  The tile's 64 global pixel indices (-1: no such row) sit in LDS behind the activation tile from the
+// staging phase to the output phase; everything between the two is the dense kernel.
+template <bool HAS_L1, int N3, int CIN = HAS_L1 ? 128 : 256, bool ROWS = false>
+__global__ __launch_bounds__(256) void head_mlp_kernel(const std::conditional_t<ROWS, MlpBatchRows, MlpBatch> batch)
 {
     const MlpArgs &a = batch.head[blockIdx.y];
-    extern __shared__ __attribute__((aligned(16))) float act[];   // [64][260]
+    extern __shared__ __attribute__((aligned(16))) float act[];   // [64][260] (+ ROWS: 64 ints)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh4 = (lane >> 5) * 4, hrow = 4 * (lane >> 5);
     const int m0 = blockIdx.x * MLP_BM;
+    [[maybe_unused]] int *tile_rows = reinterpret_cast<int *>(act + MLP_BM * MLP_LDA);
+    [[maybe_unused]] bool listed = false;
+    [[maybe_unused]] int n_list = 0;
+    if constexpr (ROWS) {
+        listed = (batch.sparse >> blockIdx.y) & 1u;
+        if (listed) {
+            n_list = min(*batch.n_rows, a.M);
+            if (m0 >= n_list) return;                         // (uniform) nothing listed for this tile; no load is in flight yet
+        }
+    }
     TRACE_INIT();
     TRACE();
     const int kt1 = HAS_L1 ? a.Cin / MLP_BK : 0, kt2 = MLP_H / MLP_BK, kt3 = MLP_H / MLP_BK;
@@ -127,8 +147,25 @@ __global__ __launch_bounds__(256) void head_mlp_kernel(const MlpBatch batch)
         const unsigned voff = ((unsigned)(m0 + row0) * (unsigned)a.in_cs + (unsigned)c4 * 4u) * 4u;
         const unsigned pstep = (unsigned)(RPP * a.in_cs) * 4u;
         f32x4 v[NP];
+        if constexpr (ROWS) {
+            // the pixel of every staged row: the list entry, or the row itself for a dense head; a row that does not exist reads 0.0f
+            int px[NP];
 #pragma unroll
-        for (int k = 0; k < NP; ++k) v[k] = MLP_ABL(4) ? f32x4{0.f, 0.f, 0.f, 0.f} : buf_load_f32x4(rin, voff, k * pstep);
+            for (int k = 0; k < NP; ++k) {
+                const int r = m0 + row0 + k * RPP;
+                px[k] = listed ? (r < n_list ? batch.rows[r] : -1) : (r < a.M ? r : -1);
+                if ((unsigned)px[k] >= (unsigned)a.M) px[k] = -1;
+            }
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                const unsigned vo = px[k] < 0 ? M3D_BUF_OOB : ((unsigned)px[k] * (unsigned)a.in_cs + (unsigned)c4 * 4u) * 4u;
+                v[k] = buf_load_f32x4(rin, vo, 0);
+                if (c4 == 0) tile_rows[row0 + k * RPP] = px[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NP; ++k) v[k] = MLP_ABL(4) ? f32x4{0.f, 0.f, 0.f, 0.f} : buf_load_f32x4(rin, voff, k * pstep);
+        }
         float *dst = act + row0 * MLP_LDA + c4 * 4;
 #pragma unroll
         for (int k = 0; k < NP; ++k) *reinterpret_cast<f32x4 *>(dst + k * RPP * MLP_LDA) = v[k];
@@ -298,8 +335,12 @@ __global__ __launch_bounds__(256) void head_mlp_kernel(const MlpBatch batch)
         const unsigned hw4 = (unsigned)a.HW * 4u;
 #pragma unroll
         for (int i = 0; i < TMo; ++i) {
-            const int m = m0 + wm + i * 32 + l31;
-            const bool mok = m < a.M;
+            int m = m0 + wm + i * 32 + l31;
+            bool mok = m < a.M;
+            if constexpr (ROWS) {
+                m = tile_rows[wm + i * 32 + l31];
+                mok = m >= 0;
+            }
             const int mm = mok ? m : 0;
             const int n = mm / a.HW, pix = mm - n * a.HW;
             const unsigned pbase = (unsigned)((long long)n * a.out_img_stride + pix + (long long)hrow * a.HW) * 4u;
@@ -318,11 +359,11 @@ __global__ __launch_bounds__(256) void head_mlp_kernel(const MlpBatch batch)
     TRACE();
 }
 
-template <bool HAS_L1, int N3, int CIN = HAS_L1 ? 128 : 256>
-static int launch_mlp(const MlpBatch &b, int n, hipStream_t stream)
+template <bool HAS_L1, int N3, int CIN = HAS_L1 ? 128 : 256, bool ROWS = false>
+static int launch_mlp(const std::conditional_t<ROWS, MlpBatchRows, MlpBatch> &b, int n, hipStream_t stream)
 {
-    constexpr size_t smem = (size_t)(MLP_BM * MLP_LDA) * sizeof(float);
-    auto kern = head_mlp_kernel<HAS_L1, N3, CIN>;
+    constexpr size_t smem = (size_t)(MLP_BM * MLP_LDA) * sizeof(float) + (ROWS ? MLP_BM * sizeof(int) : 0);
+    auto kern = head_mlp_kernel<HAS_L1, N3, CIN, ROWS>;
     static bool attr_set = false;
     if (!attr_set) {
         M3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -358,11 +399,9 @@ static int fill_mlp_args(const m3d_mlp_desc *d, MlpArgs &a)
     return M3D_OK;
 }
 
-extern "C" int m3d_head_mlp_forward_batched(const m3d_mlp_desc *d, int n, m3d_stream_t stream_)
+static int fill_mlp_batch(const m3d_mlp_desc *d, int n, MlpBatch &b)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     M3D_REQUIRE(d && n >= 1 && n <= MLP_MAX_HEADS, "head_mlp: 1..%d heads per launch (got %d)", MLP_MAX_HEADS, n);
-    MlpBatch b;
     for (int i = 0; i < n; ++i) {
         const int rc = fill_mlp_args(d + i, b.head[i]);
         if (rc != M3D_OK) return rc;
@@ -374,6 +413,15 @@ extern "C" int m3d_head_mlp_forward_batched(const m3d_mlp_desc *d, int n, m3d_st
 #ifdef HEAD_TRACE
     b.trace = g_head_trace;
 #endif
+    return M3D_OK;
+}
+
+extern "C" int m3d_head_mlp_forward_batched(const m3d_mlp_desc *d, int n, m3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    MlpBatch b;
+    const int rc = fill_mlp_batch(d, n, b);
+    if (rc != M3D_OK) return rc;
     if (d->w1 && d->Cin == 256) {
         if (d->Cout_pad == 64) return launch_mlp<true, 64, 256>(b, n, stream);
         return launch_mlp<true, 256, 256>(b, n, stream);
@@ -384,6 +432,24 @@ extern "C" int m3d_head_mlp_forward_batched(const m3d_mlp_desc *d, int n, m3d_st
     }
     if (d->Cout_pad == 64) return launch_mlp<false, 64>(b, n, stream);
     return launch_mlp<false, 256>(b, n, stream);
+}
+
+// Row-list form: heads with their bit of sparse_head_mask set are evaluated at the *n_rows listed pixels only (their other
+// output elements are left as they are), the other heads of the launch everywhere.  The grid is sized for the dense M.
+extern "C" int m3d_head_mlp_forward_rows(const m3d_mlp_desc *d, int n, const int *rows, const int *n_rows,
+                                         unsigned int sparse_head_mask, m3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    MlpBatchRows b;
+    const int rc = fill_mlp_batch(d, n, b);
+    if (rc != M3D_OK) return rc;
+    M3D_REQUIRE(rows && n_rows, "head_mlp_rows: null row list");
+    M3D_REQUIRE((sparse_head_mask >> n) == 0, "head_mlp_rows: sparse_head_mask 0x%x names a head past the %d of the launch",
+                sparse_head_mask, n);
+    M3D_REQUIRE(d->w1 && d->Cout_pad == 64, "head_mlp_rows: three-layer heads with Cout_pad = 64 only");
+    b.rows = rows; b.n_rows = n_rows; b.sparse = sparse_head_mask;
+    if (d->Cin == 256) return launch_mlp<true, 64, 256, true>(b, n, stream);
+    return launch_mlp<true, 64, 128, true>(b, n, stream);
 }
 
 extern "C" int m3d_head_mlp_forward(const m3d_mlp_desc *d, m3d_stream_t stream)

@@ -156,11 +156,12 @@ extern "C" int m3d_fg_top1(const float *prob, int B, int A, int HW, int *idx, fl
 //                                                    offmask[p][2kk..3kk) = max fg prob
 // mode 1, center_align (feturealign_mgpu.py:67-89):  offmask[p] = (off_y, off_x, prob) with
 //         off_x = ((bbox_x[idx] * std_x + mean_x) * anchor_w/stride) * hard        (kk = 1)
+//         need (optional, mode 1): pixels with need[p] == 0 get offset 0 and their bbox_x / bbox_y are not read
 __global__ void align_offsets_kernel(int mode, const int *__restrict__ sel_idx, const float *__restrict__ sel_prob,
                                      float thresh, const float *__restrict__ table, const float *__restrict__ bbox_x,
                                      const float *__restrict__ bbox_y, const float *__restrict__ anchor_wh, float mean_x,
                                      float std_x, float mean_y, float std_y, float *__restrict__ om, int om_cs, int A,
-                                     int HW, int kk, long long box_img_stride)
+                                     int HW, int kk, long long box_img_stride, const unsigned char *__restrict__ need)
 {
     const int b = blockIdx.y;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -187,6 +188,12 @@ __global__ void align_offsets_kernel(int mode, const int *__restrict__ sel_idx, 
         for (int k = 0; k < 2 * kk; ++k) o[k] = table[idx * 2 * kk + k] * hard;
         for (int k = 0; k < kk; ++k) o[2 * kk + k] = pr;
     } else {
+        if (need && !need[bp]) {
+            o[0] = 0.f;
+            o[1] = 0.f;
+            o[2] = pr;
+            return;
+        }
         const float bx = bbox_x[(size_t)b * box_img_stride + (size_t)idx * HW + p];
         const float by = bbox_y[(size_t)b * box_img_stride + (size_t)idx * HW + p];
         const float off_x = ((bx * std_x + mean_x) * anchor_wh[idx * 2 + 0]) * hard;
@@ -197,18 +204,39 @@ __global__ void align_offsets_kernel(int mode, const int *__restrict__ sel_idx, 
     }
 }
 
-extern "C" int m3d_align_offsets(int mode, const int *sel_idx, const float *sel_prob, float thresh, const float *table,
-                                 const float *bbox_x, const float *bbox_y, const float *anchor_wh, float mean_x,
-                                 float std_x, float mean_y, float std_y, float *offmask, int om_cs, int B, int A, int HW,
-                                 int kk, long long box_img_stride, m3d_stream_t stream)
+static int align_offsets_launch(int mode, const int *sel_idx, const float *sel_prob, float thresh, const float *table,
+                                const float *bbox_x, const float *bbox_y, const float *anchor_wh, float mean_x, float std_x,
+                                float mean_y, float std_y, float *offmask, int om_cs, int B, int A, int HW, int kk,
+                                long long box_img_stride, const unsigned char *need, m3d_stream_t stream)
 {
     M3D_REQUIRE(sel_idx && sel_prob && offmask && om_cs >= 3 * kk, "align_offsets: bad arguments");
     M3D_REQUIRE(mode == 0 ? (table != nullptr) : (bbox_x && bbox_y && anchor_wh && kk == 1), "align_offsets: mode inputs");
     hipLaunchKernelGGL(align_offsets_kernel, dim3(cdiv(HW, 256), B), dim3(256), 0, (hipStream_t)stream, mode, sel_idx,
                        sel_prob, thresh, table, bbox_x, bbox_y, anchor_wh, mean_x, std_x, mean_y, std_y, offmask, om_cs,
-                       A, HW, kk, box_img_stride);
+                       A, HW, kk, box_img_stride, need);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
+}
+
+extern "C" int m3d_align_offsets(int mode, const int *sel_idx, const float *sel_prob, float thresh, const float *table,
+                                 const float *bbox_x, const float *bbox_y, const float *anchor_wh, float mean_x,
+                                 float std_x, float mean_y, float std_y, float *offmask, int om_cs, int B, int A, int HW,
+                                 int kk, long long box_img_stride, m3d_stream_t stream)
+{
+    return align_offsets_launch(mode, sel_idx, sel_prob, thresh, table, bbox_x, bbox_y, anchor_wh, mean_x, std_x, mean_y, std_y,
+                                offmask, om_cs, B, A, HW, kk, box_img_stride, nullptr, stream);
+}
+
+// center_align offsets (mode 1) where bbox_x / bbox_y are written at the pixels with need[b * HW + p] != 0 only: offset 0 at the
+// others (their planes may hold anything, NaN included), the mask channel everywhere as in m3d_align_offsets.
+extern "C" int m3d_align_offsets_gated(const int *sel_idx, const float *sel_prob, float thresh, const float *bbox_x,
+                                       const float *bbox_y, const float *anchor_wh, float mean_x, float std_x, float mean_y,
+                                       float std_y, const unsigned char *need, float *offmask, int om_cs, int B, int A, int HW,
+                                       long long box_img_stride, m3d_stream_t stream)
+{
+    M3D_REQUIRE(need, "align_offsets_gated: null need map");
+    return align_offsets_launch(1, sel_idx, sel_prob, thresh, nullptr, bbox_x, bbox_y, anchor_wh, mean_x, std_x, mean_y, std_y,
+                                offmask, om_cs, B, A, HW, 1, box_img_stride, need, stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -27,6 +27,10 @@ from .config import model_flags
 
 BN_EPS = 1e-5
 SELECT_KEYS = os.environ.get("M3D_SELECT_KEYS", "1") != "0"     # anchor_select also writes the detection stage's sort keys
+# Detection-only tail (plan.tail: box heads at the needed pixels only).  A detector asked with sparse_heads=None takes it when at
+# most this fraction of an image's pixels can hold one of the nms_topN_pre rows (min(k, HW) / HW); DESIGN.md section 3, "needed
+# pixels", has the measured cost of the selection pass that the constant stands for.
+SPARSE_HEADS_MAX_FRACTION = 0.5
 PSP_SIZES = (1, 4, 8, 16)
 # channels of the stem, level0 .. level5 (pose_dla_dcn.py:419-440); channels[3] is the width of feats0 and every map after it
 BACKBONE_CHANNELS = {"dla34": (16, 32, 64, 128, 256, 512), "dla102": (16, 32, 128, 256, 512, 1024)}
@@ -214,6 +218,10 @@ class _Plan:
         self.named = {}        # name -> View / tensor (taps for tests)
         self.w44_prev = None   # (index into ops, touch record) of the latest F(4x4) launch: it warms the cache for the next one
         self.branches = []     # (b0, b1, join): ops [b0, b1) on a side stream beside ops [b1, join) (Engine._run_plan)
+        # detection-only tail: ops that stand in for ops[tail_start:-1] (everything behind anchor_select but bundle_outputs) when
+        # only the top-k decode reads the box staging (Engine.run_plan(tail=True)); None: the plan has none
+        self.tail = None
+        self.tail_start = None
 
 
 class Engine:
@@ -776,8 +784,11 @@ class Engine:
         else:
             feats = plan.named["feats"] = feats0
 
+        align_args = {}                  # p -> what a gated form of p's offsets launch needs (detection-only tail)
+
         def center_align(p, x, kx, ky, mi, out):
             om = self._buf(plan, B, fh, fw, 3, 4)
+            align_args[p] = (om, kx, ky, mi)
             self._op(plan, p + ".offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
                 1, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, None, box_ptr(kx), box_ptr(ky),
                 P["anchor_wh"].data_ptr(), float(means[mi]), float(stds[mi]), float(means[mi + 1]),
@@ -824,6 +835,53 @@ class Engine:
             cls_pl.data_ptr(), box_pl.data_ptr(), dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), dst[3].data_ptr(),
             key.data_ptr(), B, A, HW, st)), nbytes=B * R * (NC + 11 + 2 * NC + 4 + 7 + 1) * 4)
         plan.feat = (fh, fw)
+
+        # ---- detection-only tail ------------------------------------------------------
+        # m3d_topk_decode_planar reads the box staging at the nms_topN_pre best rows of an image and nowhere else, the score is a
+        # function of the class head alone (anchor_select has written the keys), and row a * HW + pix belongs to pixel pix: a box
+        # head whose planar output feeds nothing but the decode is needed at the pixels that hold one of those rows.  The centre
+        # alignments are 1x1 (feats_align2d[p] depends on bbox_x[p], bbox_y[p] and the dense `feats`), so with them bbox_x / bbox_y
+        # stay sparse behind gated offsets; bbox_x3d / bbox_y3d feed feats_align3d, which ANAB pools over the whole map: dense.
+        if plan.named.get("keys_by_select"):
+            t0 = plan.named["score_bits_first_write_op"] + 1
+            # zeroed: the dense forward (plan.ops) never writes them, and the list is written up to n_rows only -- they are
+            # published in plan.named and must not show what the allocation held (uninitialised memory)
+            need = torch.zeros(B * HW, device=self.device, dtype=torch.uint8)
+            rows = torch.zeros(B * HW, device=self.device, dtype=torch.int32)
+            n_rows = torch.zeros(1, device=self.device, dtype=torch.int32)
+            thresh = torch.zeros(B, device=self.device, dtype=torch.int32)
+            nb = L.m3d_need_rows_workspace_bytes(B, HW)
+            ws = torch.empty(nb, device=self.device, dtype=torch.uint8)
+            plan.keep += [need, rows, n_rows, thresh, ws]
+            plan.named.update(need=need, need_rows=rows, n_rows=n_rows, need_thresh=thresh)
+            k_pre = plan.named["sparse_k"] = [min(int(self.conf.nms_topN_pre), R)]      # set by the caller at launch time
+            tail = [("need_rows", "select", 0.0, lambda st: _hip.check(L.m3d_need_rows(
+                key.data_ptr(), B, A, HW, int(k_pre[0]), thresh.data_ptr(), need.data_ptr(), rows.data_ptr(), n_rows.data_ptr(),
+                ws.data_ptr(), nb, st)), OpCost(B * R * 4 * 4))]
+            dense_heads = {"bbox_x3d", "bbox_y3d"} if with_center else set()
+
+            def rows_op(op):
+                name, kind, flops, _, arr = op
+                hs = name[:-len(".mlp")].split("+")
+                mask = sum(1 << i for i, h in enumerate(hs) if h not in dense_heads)
+                n = len(hs)
+                return (name, kind, flops, lambda st: _hip.check(L.m3d_head_mlp_forward_rows(
+                    arr, n, rows.data_ptr(), n_rows.data_ptr(), mask, st)), arr)
+
+            def gated_op(op, p):
+                om, kx, ky, mi = align_args[p]
+                return op[:3] + (lambda st: _hip.check(L.m3d_align_offsets_gated(
+                    sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, box_ptr(kx), box_ptr(ky), P["anchor_wh"].data_ptr(),
+                    float(means[mi]), float(stds[mi]), float(means[mi + 1]), float(stds[mi + 1]), need.data_ptr(), om.ptr, om.cs,
+                    B, A, HW, 11 * A * HW, st)), op[4])
+
+            for op in plan.ops[t0:-1]:
+                if op[1] == "head_mlp<3,64>":
+                    op = rows_op(op)
+                elif op[0] == "center_align2d.offsets":
+                    op = gated_op(op, "center_align2d")
+                tail.append(op)
+            plan.tail, plan.tail_start = tail, t0
         return plan
 
 
@@ -1075,17 +1133,36 @@ class Engine:
         self.run_plan(plan)
         return plan.named["feats0"]
 
-    def run_plan(self, plan, start=0, end=None):
+    def run_plan(self, plan, start=0, end=None, tail=False):
         """Issue plan.ops[start:end] on the ENGINE device's current stream (the whole forward by default); the engine's
-        device is made current for the launches, whatever the caller's current device is."""
+        device is made current for the launches, whatever the caller's current device is.
+        tail=True: the detection-only form -- plan.ops[start:plan.tail_start], then plan.tail in place of everything behind it up
+        to bundle_outputs (`end` must be the index of bundle_outputs).  The box staging is then written at the needed pixels only:
+        what follows may be the planar top-k decode, not bundle_outputs.  plan.named["sparse_k"][0] is the k of that decode."""
         with torch.cuda.device(self.device):
-            self._run_plan(plan, start, end)
+            if not tail:
+                return self._run_plan(plan, start, end)
+            if getattr(plan, "tail", None) is None:
+                raise RuntimeError("run_plan(tail=True): this plan has no detection-only tail")
+            if end != len(plan.ops) - 1 or not 0 <= start <= plan.tail_start or plan.branches:
+                raise RuntimeError("run_plan(tail=True): ops [%r, %r) do not end in front of bundle_outputs (op %d) behind a start "
+                                   "in [0, %d]" % (start, end, len(plan.ops) - 1, plan.tail_start))
+            self._run_plan(plan, start, end, plan.ops[start:plan.tail_start] + plan.tail)
 
-    def _run_plan(self, plan, start, end):
+    def sparse_heads_default(self, plan, k):
+        """The plan-time rule of a detector's sparse_heads=None for a decode of the k best rows per image."""
+        if getattr(plan, "tail", None) is None:
+            return False
+        hw = plan.feat[0] * plan.feat[1]
+        return min(int(k), hw) <= SPARSE_HEADS_MAX_FRACTION * hw
+
+    def _run_plan(self, plan, start, end, ops=None):
         st = _Stream.current(self.device)
-        ops = plan.ops[start:end]
+        tail = ops is not None
+        if not tail:
+            ops = plan.ops[start:end]
         if self.profile is None:
-            brs = [br for br in getattr(plan, "branches", ()) if lo_hi_contains(start, end, len(plan.ops), br)]
+            brs = [] if tail else [br for br in getattr(plan, "branches", ()) if lo_hi_contains(start, end, len(plan.ops), br)]
             if brs:
                 # side branches: ops [b0, b1) run on a second stream beside ops [b1, join) (no data dependence between the two
                 # groups: the plan builder vouches for that); fork / join by stream waits, so the pattern is captured by a hipGraph

@@ -46,7 +46,8 @@ class _Detector:
     """What both detectors own: the module, its engine and plan, the input buffers, the refinement's buffers, and the pieces of a
     captured step -- plan ops with the input pointer set, rows -> selection -> optional refinement, the result tuple."""
 
-    def __init__(self, net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, u8_buffers):
+    def __init__(self, net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, u8_buffers,
+                 sparse_heads=None, planar=True):
         net = unwrap(net)                               # (a DataParallel / DDP wrapper of the module, as the reference's scripts pass it)
         self.net, self.conf = net, conf
         dev = next(net.parameters()).device
@@ -72,19 +73,29 @@ class _Detector:
             self.input = self.inputs_u8[0]
         assert self.plan.ops[-1][0] == "bundle_outputs"
         self.n_fwd = len(self.plan.ops) - 1                 # planar form: everything in front of the output bundling
+        # box heads at the needed pixels only (the plan's detection-only tail): None = the engine's plan-time rule; the bundled
+        # form and a plan without a tail (bf16) stay dense whatever is asked
+        if sparse_heads is None:
+            sparse_heads = self.eng.sparse_heads_default(self.plan, conf.nms_topN_pre)
+        self.sparse_heads = bool(sparse_heads) and bool(planar) and getattr(self.plan, "tail", None) is not None
         self._rois = net.rois.to(dev)
         # refine mode: calibration / scale / image size of the batch whose detections the next replay refines
         self._meta = RefineMeta(self.batch, dev) if self.refine else None
 
-    def _forward(self, start, end, buf=0):
+    def _forward(self, start, end, buf=0, tail=False):
+        """plan.ops[start:end]; tail: with the detection-only tail behind anchor_select (end = n_fwd), for a decode of
+        conf.nms_topN_pre rows as it stands now."""
+        if tail:
+            bits = self.plan.named["score_bits"]
+            self.plan.named["sparse_k"][0] = min(int(self.conf.nms_topN_pre), bits.shape[1])
         if self.u8_frame is None:
             self.plan.named["input_ptr"][0] = self.input.data_ptr()
-            self.eng.run_plan(self.plan, start, end)
+            self.eng.run_plan(self.plan, start, end, tail)
             return
         # the stem launch reads (pointer, h, w) of the uint8 frames when it is ISSUED: capture bakes buffer `buf` into the graph
         self.plan.named["input_u8"][:] = [self.inputs_u8[buf].data_ptr(), self.u8_frame[0], self.u8_frame[1]]
         try:
-            self.eng.run_plan(self.plan, start, end)
+            self.eng.run_plan(self.plan, start, end, tail)
         finally:
             self.plan.named["input_u8"][0] = 0
 
@@ -105,9 +116,10 @@ class _Detector:
 
 class PipelinedDetector(_Detector):
     def __init__(self, net, conf, batch, height, width, refine=False, score_thresh=0.75, step_r_init=0.3 * math.pi, r_lim=0.01,
-                 u8_frame=None, planar=None):
-        super().__init__(net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, 2)
-        self.planar = (os.environ.get("M3D_PIPE_PLANAR", "1") != "0") if planar is None else bool(planar)
+                 u8_frame=None, planar=None, sparse_heads=None):
+        planar = (os.environ.get("M3D_PIPE_PLANAR", "1") != "0") if planar is None else bool(planar)
+        super().__init__(net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, 2, sparse_heads, planar)
+        self.planar = planar
         if self.u8_frame is not None:
             # slot i: address of the pinned-host frames that the graph reading buffer i uploads into buffer i ^ 1 (0 = nothing)
             self._slots = torch.zeros(2, dtype=torch.int64).pin_memory()
@@ -161,7 +173,7 @@ class PipelinedDetector(_Detector):
         """The launches behind the join: the rest of the forward, then the key-only pass (planar) or the output bundling."""
         if self.planar:
             if self.n_join < self.n_fwd:
-                self._forward(self.n_join, self.n_fwd, buf)
+                self._forward(self.n_join, self.n_fwd, buf, self.sparse_heads)
             if not self.plan.named.get("keys_by_select"):    # else anchor_select wrote them on the way (engine: SELECT_KEYS)
                 score_keys_planar(self.eng, self.plan)
         else:
@@ -328,10 +340,10 @@ class FrameDetector(_Detector):
     positive value = workgroups per image of ``m3d_topk_decode_planar_mw``."""
 
     def __init__(self, net, conf, height, width, batch=1, refine=False, score_thresh=0.75, step_r_init=0.3 * math.pi, r_lim=0.01,
-                 u8_frame=None, topk_wgs=None):
+                 u8_frame=None, topk_wgs=None, sparse_heads=None):
         if topk_wgs is not None and int(topk_wgs) < 1:
             raise ValueError("topk_wgs must be None or a positive number of workgroups per image, got %r" % (topk_wgs,))
-        super().__init__(net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, 1)
+        super().__init__(net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, 1, sparse_heads)
         if topk_wgs is None:
             self.topk_wgs = 0 if self.batch <= FRAME_MW_MAX_BATCH else 1       # 0: m3d_topk_decode_planar_mw picks the count
         else:
@@ -340,7 +352,7 @@ class FrameDetector(_Detector):
 
     def _run(self):
         """Forward, keys, detection (and refinement) of what ``self.input`` holds, on the current stream."""
-        self._forward(0, self.n_fwd)
+        self._forward(0, self.n_fwd, 0, self.sparse_heads)
         if not self.plan.named.get("keys_by_select"):       # else anchor_select wrote them on the way (engine: SELECT_KEYS)
             score_keys_planar(self.eng, self.plan)
         scale = self._meta.scale if self.refine else None
