@@ -81,7 +81,9 @@ const char *m3d_last_error(void);
  *                  m3d_rpn_targets, m3d_rpn_loss, m3d_rpn_loss_workspace_bytes (additive);
  *                  m3d_topk_decode_planar_mw, m3d_topk_decode_mw_workspace_bytes (additive);
  *                  m3d_conv_wave_forward_wgsplit, m3d_conv_wave_wgsplit_width (additive);
- *                  m3d_need_rows, m3d_need_rows_workspace_bytes, m3d_head_mlp_forward_rows, m3d_align_offsets_gated (additive). */
+ *                  m3d_need_rows, m3d_need_rows_workspace_bytes, m3d_head_mlp_forward_rows, m3d_align_offsets_gated (additive);
+ *                  m3d_dcn_v2_forward_bf16, m3d_dcn_v2_workspace_bytes_bf16, m3d_dcn_v2_backward_bf16,
+ *                  m3d_dcn_v2_backward_workspace_bytes_bf16 (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -478,6 +480,36 @@ int m3d_dcn_v2_backward(const float *input, const float *weight, const float *of
                         int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
                         int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
                         int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
+
+/* The same operator on bf16 tensors (csrc/dcn_bf16.hip): what a training loop under torch.autocast(dtype=bfloat16) hands over.
+ * input [N, C, H, W], weight [Co, C, kh, kw], grad_output / output [N, Co, Ho, Wo] and grad_input are bf16 NCHW contiguous, bias
+ * and grad_bias fp32; offset and mask are fp32 (`*_is_bf16` = 0) or bf16 (1), widened exactly and used as fp32; grad_offset and
+ * grad_mask are written as fp32, grad_weight as bf16 (the type of the weight it belongs to).  Coordinates, the inside rule, floor
+ * and the corner weights are those of the fp32 calls (fp32 arithmetic, the same piecewise rule).  Rounding points: the modulated
+ * sample mask * val -> bf16 once (the MFMA operand), products exact, fp32 accumulation, bias added in fp32, output -> bf16 once;
+ * backward: gcol fp32, col = mask * val bf16, grad_input accumulated in fp32 with float atomics and rounded to bf16 once,
+ * grad_weight rounded once after the split-order sum.  Semantics of the backward as m3d_dcn_v2_backward: every non-NULL gradient
+ * is overwritten, NULL = not wanted, grad_offset / grad_mask / grad_weight / grad_bias bitwise reproducible.
+ * Any C / Co (padded inside, nothing written past the tensors), deformable_group >= 1 dividing C, stride 1 or 2, kernels up to 3x3.
+ * dilation must be 1: the bf16 convolution has none -- M3D_E_ARG "the bf16 path supports dilation 1 only", and the size queries
+ * return -1 for it as for an invalid group count.  The workspace size does not depend on which gradients are asked for;
+ * M3D_E_WORKSPACE carries both sizes. */
+long long m3d_dcn_v2_workspace_bytes_bf16(int batch, int channels, int height, int width, int channels_out,
+                                          int kernel_h, int kernel_w, int stride, int pad, int dilation, int deformable_group);
+int m3d_dcn_v2_forward_bf16(const void *input, const void *weight, const float *bias, const void *offset, int offset_is_bf16,
+                            const void *mask, int mask_is_bf16, void *output, int batch, int channels, int height, int width,
+                            int channels_out, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w,
+                            int dilation_h, int dilation_w, int deformable_group, void *workspace, long long workspace_bytes,
+                            m3d_stream_t stream);
+long long m3d_dcn_v2_backward_workspace_bytes_bf16(int batch, int channels, int height, int width, int channels_out,
+                                                   int kernel_h, int kernel_w, int stride, int pad, int dilation,
+                                                   int deformable_group);
+int m3d_dcn_v2_backward_bf16(const void *input, const void *weight, const void *offset, int offset_is_bf16, const void *mask,
+                             int mask_is_bf16, const void *grad_output,
+                             void *grad_input, float *grad_offset, float *grad_mask, void *grad_weight, float *grad_bias,
+                             int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
+                             int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
+                             int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * RPN_3D_loss on the device (csrc/rpn_loss.hip): target assignment, hard-negative sampling, fused loss + gradients.

@@ -662,7 +662,7 @@ extern "C" int m3d_conv_bf16_forward(const m3d_conv_bf16_desc *d, m3d_stream_t s
     if (d->out_mode == 1) M3D_REQUIRE(d->out_cs % 4 == 0 && ((uintptr_t)d->out & 15) == 0, "conv_bf16: fp32 NHWC output needs out_cs %% 4 == 0");
     if (d->res) M3D_REQUIRE(d->res_cs % 4 == 0 && ((uintptr_t)d->res & 7) == 0, "conv_bf16: residual view alignment");
     if (d->wgt_img_stride) M3D_REQUIRE((ho * wo) % 128 == 0, "conv_bf16: per-image weights need Ho*Wo %% 128 == 0");
-    if (d->dcn_offmask) M3D_REQUIRE(d->stride == 1 && d->groups == 1 && taps <= 9, "conv_bf16: deformable mode is stride 1, ungrouped, <= 9 taps");
+    if (d->dcn_offmask) M3D_REQUIRE(d->stride >= 1 && d->groups == 1 && taps <= 9, "conv_bf16: deformable mode is ungrouped, <= 9 taps");
 
     Bf16Args a;
     a.in = d->in; a.wgt = d->wgt; a.out = d->out; a.scale = d->scale; a.shift = d->shift; a.res = d->res; a.om = d->dcn_offmask;

@@ -1,17 +1,23 @@
 #!/usr/bin/env python
-"""Times m3d_dcn_v2_backward (csrc/dcn_backward.hip) on the deformable layers of the M3DSSD DLA-34 plan at batch 8: the four
-DeformConv shapes of the IDA up-sampling path plus shape_align (3x3, offsets of several pixels) and center_align (1x1).
+"""Times the DCNv2 operator of the training path -- m3d_dcn_v2_backward (csrc/dcn_backward.hip), m3d_dcn_v2_backward_bf16
+(csrc/dcn_bf16.hip) and, with --forward, m3d_dcn_v2_forward / m3d_dcn_v2_forward_bf16 -- on the deformable layers of the M3DSSD
+DLA-34 plan at batch 8: the four DeformConv shapes of the IDA up-sampling path plus shape_align (3x3, offsets of several pixels)
+and center_align (1x1).
 
 HIP events around one call, `--warmup` untimed calls, `--reps` timed ones (>= 50), median and minimum reported.  Besides the full
-call (all five gradients) it times the call with subsets of the gradient pointers set, which isolates the stages:
+backward call (all five gradients) it times the call with subsets of the gradient pointers set, which isolates the stages:
   weight_only   sampling kernel (writes col) + weight-gradient GEMM + slab reduce
   input_only    column-gradient GEMM + sampling kernel with the atomic scatter
   offmask_only  column-gradient GEMM + sampling kernel without atomics
-Budget printed next to the measurement: the scatter adds N*Ho*Wo * kk * 4 corners * C * 4 bytes at the
-chip-wide float-atomic rate of 1.3 TB/s, plus the two GEMMs of 2 * N*Ho*Wo * Co * kk*C FLOP each at the rate the forward's
-wave-granular convolution reaches (94 TFLOP/s).
+--dtype f32 | bf16 | both.  With `both` the two types alternate per shape and mode inside one process -- f32, bf16, f32 again --
+and the line carries, per mode, the medians of the three legs, `spread_ms` = |median of the second f32 leg - median of the first|
+(the run-to-run allowance) and `bf16_not_slower` = bf16 median <= first f32 median + spread.
+Budget printed next to the backward measurement: the scatter adds N*Ho*Wo * kk * 4 corners * C * 4 bytes at
+the chip-wide float-atomic rate of 1.3 TB/s (fp32 atomics in both types), plus the two GEMMs of 2 * N*Ho*Wo * Co * kk*C FLOP each
+at the rate the forward's wave-granular convolution reaches (94 TFLOP/s).
 
-usage: python tools/dcn_backward_bench.py [--reps 50] [--warmup 5] [--batch 8]      (one JSON line per shape on stdout)"""
+usage: python tools/dcn_backward_bench.py [--reps 50] [--warmup 5] [--batch 8] [--dtype f32|bf16|both] [--forward]
+(one JSON line per shape on stdout)"""
 import argparse
 import ctypes
 import json
@@ -38,17 +44,79 @@ SHAPES = [
 MODES = {"all": (1, 1, 1, 1, 1), "weight_only": (0, 0, 0, 1, 0), "input_only": (1, 0, 0, 0, 0), "offmask_only": (0, 1, 1, 0, 0)}
 
 
+class Leg:
+    """One compute type of one shape: its device tensors, workspaces and the two calls."""
+
+    def __init__(self, dtype, data, geom, pad, dev, stream):
+        self.bf16 = dtype == "bf16"
+        L = self.L = _hip.lib()
+        dt = torch.bfloat16 if self.bf16 else torch.float32
+        x, off, m, wt, b, go = data
+        self.x, self.wt, self.go = x.to(dt), wt.to(dt), go.to(dt)
+        self.off, self.m, self.b = off, m, b                       # offsets / masks / bias stay float32 in both types
+        n, c, h, w, co, k = geom
+        self.out = torch.empty(n, co, h, w, device=dev, dtype=dt)
+        self.grads = [torch.empty_like(self.x), torch.empty_like(off), torch.empty_like(m), torch.empty_like(self.wt),
+                      torch.empty(co, device=dev)]
+        q = (n, c, h, w, co, k, k, 1, pad, 1, 1)
+        self.fbytes = (L.m3d_dcn_v2_workspace_bytes_bf16 if self.bf16 else L.m3d_dcn_v2_workspace_bytes_grouped)(*q)
+        self.bbytes = (L.m3d_dcn_v2_backward_workspace_bytes_bf16 if self.bf16 else L.m3d_dcn_v2_backward_workspace_bytes)(*q)
+        self.ws = torch.empty(max(self.fbytes, self.bbytes) + 256, device=dev, dtype=torch.uint8)
+        self.base = (self.ws.data_ptr() + 255) // 256 * 256
+        self.tail = (n, c, h, w, co, k, k, 1, 1, pad, pad, 1, 1, 1, self.base)
+        self.stream = stream
+
+    def forward(self):
+        L, p = self.L, lambda t: t.data_ptr()                      # noqa: E731
+        if self.bf16:
+            rc = L.m3d_dcn_v2_forward_bf16(p(self.x), p(self.wt), p(self.b), p(self.off), 0, p(self.m), 0, p(self.out), *self.tail,
+                                           self.fbytes, self.stream)
+        else:
+            rc = L.m3d_dcn_v2_forward(p(self.x), p(self.wt), p(self.b), p(self.off), p(self.m), p(self.out), *self.tail, self.fbytes,
+                                      self.stream)
+        _hip.check(rc)
+
+    def backward(self, want):
+        L, p = self.L, lambda t: t.data_ptr()                      # noqa: E731
+        ptrs = [t.data_ptr() if wnt else None for t, wnt in zip(self.grads, want)]
+        if self.bf16:
+            rc = L.m3d_dcn_v2_backward_bf16(p(self.x), p(self.wt), p(self.off), 0, p(self.m), 0, p(self.go), *ptrs, *self.tail,
+                                            self.bbytes, self.stream)
+        else:
+            rc = L.m3d_dcn_v2_backward(p(self.x), p(self.wt), p(self.off), p(self.m), p(self.go), *ptrs, *self.tail, self.bbytes,
+                                       self.stream)
+        _hip.check(rc)
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    ts.sort()
+    return {"median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--dtype", choices=("f32", "bf16", "both"), default="f32")
+    ap.add_argument("--forward", action="store_true", help="time the operator's forward instead of the backward")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("dcn_backward_bench: no ROCm device")
     dev = torch.device("cuda:0")
-    L = _hip.lib()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    order = {"f32": ("f32",), "bf16": ("bf16",), "both": ("f32", "bf16", "f32_repeat")}[a.dtype]
     for name, c, co, h, w, k, pad, sigma in SHAPES:
         n, kk = a.batch, k * k
         g = torch.Generator().manual_seed(1)
@@ -57,36 +125,32 @@ def main():
         m = torch.sigmoid(torch.randn(n, kk, h, w, generator=g)).to(dev)
         wt = (torch.randn(co, c, k, k, generator=g) / (c * kk) ** 0.5).to(dev)
         go = torch.randn(n, co, h, w, generator=g).to(dev)
-        outs = [torch.empty_like(x), torch.empty_like(off), torch.empty_like(m), torch.empty_like(wt), torch.empty(co, device=dev)]
-        nbytes = L.m3d_dcn_v2_backward_workspace_bytes(n, c, h, w, co, k, k, 1, pad, 1, 1)
-        ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
-        base = (ws.data_ptr() + 255) // 256 * 256
-
-        def call(want):
-            ptrs = [t.data_ptr() if wnt else None for t, wnt in zip(outs, want)]
-            _hip.check(L.m3d_dcn_v2_backward(x.data_ptr(), wt.data_ptr(), off.data_ptr(), m.data_ptr(), go.data_ptr(), *ptrs, n, c, h, w,
-                                             co, k, k, 1, 1, pad, pad, 1, 1, 1, base, nbytes, stream))
-
-        res = {"shape": name, "batch": n, "reps": a.reps, "workspace_mb": round(nbytes / 2 ** 20, 1)}
-        for mode, want in MODES.items():
-            for _ in range(a.warmup):
-                call(want)
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                call(want)
-                e1.record()
-                e1.synchronize()
-                ts.append(e0.elapsed_time(e1))
-            ts.sort()
-            res[mode + "_ms"] = {"median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4)}
-        P = n * h * w
-        atomic_ms = P * kk * 4 * c * 4 / ATOMIC_BYTES_PER_S * 1e3
-        gemm_ms = 2.0 * P * co * kk * c / GEMM_FLOPS * 1e3
-        res["budget_ms"] = {"atomic_scatter": round(atomic_ms, 4), "each_gemm": round(gemm_ms, 4), "total": round(atomic_ms + 2 * gemm_ms, 4)}
-        res["measured_over_budget"] = round(res["all_ms"]["median"] / (atomic_ms + 2 * gemm_ms), 2)
+        b = torch.zeros(co, device=dev)
+        legs = {d: Leg(d, (x, off, m, wt, b, go), (n, c, h, w, co, k), pad, dev, stream) for d in set(o.split("_")[0] for o in order)}
+        res = {"shape": name, "batch": n, "reps": a.reps, "op": "forward" if a.forward else "backward", "dtype": a.dtype,
+               "workspace_mb": {d: round((lg.fbytes if a.forward else lg.bbytes) / 2 ** 20, 1) for d, lg in legs.items()}}
+        modes = {"forward": None} if a.forward else MODES
+        for mode, want in modes.items():
+            entry = {}
+            for o in order:
+                lg = legs[o.split("_")[0]]
+                entry[o] = timed(lg.forward if a.forward else (lambda: lg.backward(want)), a.warmup, a.reps)
+            if a.dtype == "both":
+                spread = abs(entry["f32_repeat"]["median"] - entry["f32"]["median"])
+                entry["spread_ms"] = round(spread, 4)
+                entry["bf16_not_slower"] = entry["bf16"]["median"] <= entry["f32"]["median"] + spread
+            else:
+                entry = entry[order[0]]
+            res[mode + "_ms"] = entry
+        if not a.forward:
+            P = n * h * w
+            atomic_ms = P * kk * 4 * c * 4 / ATOMIC_BYTES_PER_S * 1e3
+            gemm_ms = 2.0 * P * co * kk * c / GEMM_FLOPS * 1e3
+            res["budget_ms"] = {"atomic_scatter": round(atomic_ms, 4), "each_gemm": round(gemm_ms, 4),
+                                "total": round(atomic_ms + 2 * gemm_ms, 4)}
+            full = res["all_ms"]
+            med = {o: full[o]["median"] for o in order} if a.dtype == "both" else {order[0]: full["median"]}
+            res["measured_over_budget"] = {o: round(v / (atomic_ms + 2 * gemm_ms), 2) for o, v in med.items()}
         print(json.dumps(res), flush=True)
 
 
