@@ -458,7 +458,7 @@ int m3d_dcn_v2_forward(const float *input, const float *weight, const float *bia
                        int pad_w, int dilation_h, int dilation_w, int deformable_group, void *workspace,
                        long long workspace_bytes, m3d_stream_t stream);
 
-/* Drop-in for dcn_v2_cuda_backward (csrc/dcn_backward.hip): NCHW contiguous fp32 device tensors, the reference's argument
+/* Drop-in for dcn_v2_cuda_backward (csrc/dcn_op.hip): NCHW contiguous fp32 device tensors, the reference's argument
  * meaning with `ones` / `columns` replaced by the caller's workspace of m3d_dcn_v2_backward_workspace_bytes() bytes (-1 for an
  * invalid group count; the size does not depend on which gradients are asked for).  Given grad_output [N, Co, Ho, Wo] it
  * produces grad_input [N, C, H, W], grad_offset [N, G*2*kh*kw, Ho, Wo], grad_mask [N, G*kh*kw, Ho, Wo], grad_weight
@@ -481,7 +481,7 @@ int m3d_dcn_v2_backward(const float *input, const float *weight, const float *of
                         int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
                         int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
 
-/* The same operator on bf16 tensors (csrc/dcn_bf16.hip): what a training loop under torch.autocast(dtype=bfloat16) hands over.
+/* The same operator on bf16 tensors (csrc/dcn_op.hip): what a training loop under torch.autocast(dtype=bfloat16) hands over.
  * input [N, C, H, W], weight [Co, C, kh, kw], grad_output / output [N, Co, Ho, Wo] and grad_input are bf16 NCHW contiguous, bias
  * and grad_bias fp32; offset and mask are fp32 (`*_is_bf16` = 0) or bf16 (1), widened exactly and used as fp32; grad_offset and
  * grad_mask are written as fp32, grad_weight as bf16 (the type of the weight it belongs to).  Coordinates, the inside rule, floor

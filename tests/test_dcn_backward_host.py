@@ -39,6 +39,34 @@ def test_backward_workspace_rule():
         assert all(b >= a for a, b in zip(sizes, sizes[1:])), sizes
 
 
+# batch, channels, height, width, channels_out, kernel_h, kernel_w, stride, pad, dilation, deformable_group ->
+# m3d_dcn_v2_workspace_bytes_grouped, m3d_dcn_v2_backward_workspace_bytes, m3d_dcn_v2_workspace_bytes_bf16,
+# m3d_dcn_v2_backward_workspace_bytes_bf16
+WORKSPACE_PINS = [
+    ((1, 24, 10, 12, 8, 3, 3, 1, 1, 1, 3), (110336, 1101568, 35328, 858880)),                      # 3x3, three deformable groups
+    ((2, 32, 13, 17, 128, 3, 3, 1, 1, 1, 1), (480000, 4901888, 386304, 4075520)),                  # Co % 128 == 0: the wide fp32 tile
+    ((1, 8, 10, 12, 72, 3, 3, 2, 1, 1, 2), (183808, 808960, 47616, 603904)),                       # stride 2, two groups, Co = 72
+    ((2, 16, 7, 9, 16, 1, 1, 1, 0, 1, 1), (34560, 212992, 18432, 156416)),                         # 1x1 pad 0
+    ((1, 6, 12, 10, 5, 3, 3, 1, 2, 2, 3), (110336, 1101568, -1, -1)),                              # dilation 2 pad 2: no bf16 form
+    ((4, 256, 24, 80, 256, 3, 3, 1, 1, 1, 1), (18948096, 236819456, 13836288, 159341568)),         # network size: 256 -> 256 at 24x80
+    ((2, 6, 12, 10, 5, 3, 3, 1, 1, 1, 4), (-1, -1, -1, -1)),                                       # 4 does not divide 6
+    ((3, 20, 11, 13, 72, 3, 3, 1, 1, 1, 1), (374272, 4827136, 260864, 4020992)),                   # odd everything, Co = 72
+    ((1, 72, 5, 7, 12, 3, 3, 1, 1, 1, 1), (240640, 961536, 88576, 720128)),                        # C past one wave, 35 pixels
+]
+
+
+@pytest.mark.parametrize("shape,expected", WORKSPACE_PINS)
+def test_workspace_queries_are_pinned(shape, expected):
+    """The four workspace queries of the DCNv2 operator are ABI: callers size their buffers by them and the M3D_E_WORKSPACE
+    messages quote them.  The expected byte counts were taken from the library built at commit e8e42fb, the last one with a
+    separate fp32 and bf16 workspace planner (the queries are host arithmetic and ran on a machine without a GPU); they are not
+    recomputed from the code under test."""
+    L = _hip.lib()
+    got = tuple(int(f(*shape)) for f in (L.m3d_dcn_v2_workspace_bytes_grouped, L.m3d_dcn_v2_backward_workspace_bytes,
+                                         L.m3d_dcn_v2_workspace_bytes_bf16, L.m3d_dcn_v2_backward_workspace_bytes_bf16))
+    assert got == expected
+
+
 @pytest.mark.parametrize("spec", R.PIN_CASES)
 def test_yardstick_forward_matches_the_oracle(spec):
     """The float32 forward of the restatement against oracle.dcn.dcn_v2_forward: <= 2e-6 * (1 + |ref|) (measured 7.5e-7)."""

@@ -16,7 +16,9 @@ import torch.nn.functional as F
 
 from m3dssd_amd import _hip
 from gpu_common import *  # noqa: F401,F403
+import dcn_bf16_cases as C
 import dcn_grad_ref as R
+import exact_inputs as X
 
 pytestmark = pytest.mark.gpu
 
@@ -114,6 +116,19 @@ def test_backward_matches_float64_reference(spec):
     _, refs = R.ref_grads(ts, go, args)
     grads = Problem(ts, go, args).run()
     _check("parity %s" % (spec,), grads, refs)
+
+
+@pytest.mark.parametrize("spec", C.EXACT_BWD_CASES)
+def test_backward_is_exact_on_the_lattice(spec):
+    """The five lattice cases of the bf16 operator (tests/dcn_bf16_cases.py) through the fp32 entry point: no step rounds there
+    (tests/test_dcn_bf16_host.py asserts it on the CPU, grad_input's atomic sums included), so all five gradients equal the float64
+    reference bit for bit.  The sampling kernel is one template for both types: this pins its fp32 instantiation."""
+    _, go, ts, args = C.exact_bwd_case(spec)
+    _, refs = C.ref_grads64(ts, go, args)
+    grads = Problem(ts, go, args).run()
+    for name, g, r in zip(NAMES, grads, refs):
+        bad, msg = X.compare_exact(torch.from_numpy(g), r, torch.float32)
+        assert bad == 0, "grad_%s: %s" % (name, msg)
 
 
 # ======================================================================================== 6. closed forms

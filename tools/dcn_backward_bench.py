@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Times the DCNv2 operator of the training path -- m3d_dcn_v2_backward (csrc/dcn_backward.hip), m3d_dcn_v2_backward_bf16
-(csrc/dcn_bf16.hip) and, with --forward, m3d_dcn_v2_forward / m3d_dcn_v2_forward_bf16 -- on the deformable layers of the M3DSSD
+"""Times the DCNv2 operator of the training path -- m3d_dcn_v2_backward, m3d_dcn_v2_backward_bf16 and, with
+--forward, m3d_dcn_v2_forward / m3d_dcn_v2_forward_bf16 (all four in csrc/dcn_op.hip) -- on the deformable layers of the M3DSSD
 DLA-34 plan at batch 8: the four DeformConv shapes of the IDA up-sampling path plus shape_align (3x3, offsets of several pixels)
 and center_align (1x1).
 
