@@ -1,4 +1,6 @@
-// libm3dssd_hip.so: error reporting, events, source hashes, ABI version and the clock probe.
+// libm3dssd_hip.so: error reporting, launcher state, events, source hashes, ABI version and the clock probe.
+#include <stdlib.h>
+
 #include "common.h"
 
 static thread_local char g_err[512] = "";
@@ -12,6 +14,59 @@ void m3d_set_error(const char *fmt, ...)
 }
 
 extern "C" const char *m3d_last_error(void) { return g_err; }
+
+// ---- launcher state (common.h) ---------------------------------------------------------------------------------------------------
+int m3d_env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+int m3d_raise_dyn_lds_(const void *kernel, int bytes, m3d_lds_state &state, const char *what, const char *file, int line)
+{
+    int dev = 0;
+    M3D_HIP(hipGetDevice(&dev));
+    const int err = *state.get(dev, [&]() {
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) (void)hipGetLastError();
+        return std::optional<int>((int)e);
+    });
+    if (err != (int)hipSuccess) {
+        m3d_set_error("hipFuncSetAttribute(%s, hipFuncAttributeMaxDynamicSharedMemorySize, %d) failed: %s (%s:%d)", what, bytes,
+                      hipGetErrorString((hipError_t)err), file, line);
+        return M3D_E_HIP;
+    }
+    return M3D_OK;
+}
+
+int m3d_cu_count()
+{
+    static PerDevice<int> count;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;                  // no current device: no slot, the fallback
+    return *count.get(dev, [&]() {
+        int ncu = 0;
+        if (dev < 0 || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
+            (void)hipGetLastError();
+            ncu = 256;
+        }
+        return std::optional<int>(ncu);
+    });
+}
+
+int m3d_scratch_bytes_(const void *const *kernels, int n)
+{
+    long long sum = 0;
+    for (int i = 0; i < n; ++i) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, kernels[i]) != hipSuccess) {
+            (void)hipGetLastError();
+            return -1;
+        }
+        sum += (long long)fa.localSizeBytes;
+    }
+    return (int)sum;
+}
 extern "C" int m3d_abi_version(void) { return M3D_ABI_VERSION; }
 // "name:sha256[:16];..." of every source this library was built from (build/src_hash.h, written by the Makefile): lets a
 // measurement taken with one build (profiles/*_hbm_traffic.json) be told apart from the build that is loaded now.

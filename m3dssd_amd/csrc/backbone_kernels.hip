@@ -1,7 +1,6 @@
 // HBM-bound helpers of the backbone / up-sampling path (NHWC, 16-byte vector access along C):
 // weight packing, layout changes at the op boundary, the 7x7 stem, 2x2 max-pool and the
 // depthwise transposed-conv up-sampler fused with the IDA skip add.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -440,8 +439,7 @@ extern "C" int m3d_conv3x3_c16(const float *in, int in_cs, const float *wgt, con
                 "conv3x3_c16: bad arguments");
     M3D_REQUIRE((((uintptr_t)in | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
                 "conv3x3_c16: in / out / scale / shift must be 16-byte aligned (float4 accesses)");
-    static int valu = -1;                        // tuning knob (experiments only): M3D_L0_VALU=1 selects the VALU kernel
-    if (valu < 0) { const char *e = getenv("M3D_L0_VALU"); valu = e ? atoi(e) : 0; }
+    static const int valu = m3d_env_int("M3D_L0_VALU", 0);           // tuning knob (experiments only): 1 selects the VALU kernel
     const long long in_bytes = (long long)N * H * W * in_cs * 4;
     if (!valu && in_bytes < (1ll << 31))
         hipLaunchKernelGGL(conv3x3_c16_mfma_kernel, dim3(cdiv(W, L0M_TW), cdiv(H, L0M_TH), N), dim3(256), 0, (hipStream_t)stream,
@@ -592,7 +590,8 @@ extern "C" int m3d_upload_indirect(const void *const *src_slot, void *dst, long 
     if (bytes == 0) return M3D_OK;
     // 8 workgroups (measured, tools/feed_probe.py, step = 6.07 ms resident): 1 -> 6.98 ms (the upload outlasts the forward),
     // 2 -> 6.39, 4 -> 6.19, 16 -> 6.19, 64 -> 6.24: a few workgroups keep enough loads in flight for PCIe and leave the CUs alone
-    static const int wgs = []() { const char *e = getenv("M3D_UPLOAD_WGS"); const int v = e ? atoi(e) : 8; return v > 0 ? v : 8; }();
+    static const int knob = m3d_env_int("M3D_UPLOAD_WGS", 8);
+    const int wgs = knob > 0 ? knob : 8;
     hipLaunchKernelGGL(upload_indirect_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, src_slot, (u32x4 *)dst, bytes);
     M3D_LAUNCH_CHECK();
     return M3D_OK;

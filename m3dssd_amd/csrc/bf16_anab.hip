@@ -17,7 +17,6 @@
 //   The q fragments of the wave's 32 pixels (12 x 16 bytes per lane) stay in registers for both passes.
 //   Differences to the three-launch form: the logits are recomputed instead of stored (same MFMA sequence, same values), and the
 //   bf16 rounding is applied to exp(S - m) instead of exp(S - m) / l (the division happens in fp32 on the accumulator).
-#include <stdlib.h>
 
 #include "bf16_tile.h"
 
@@ -269,7 +268,7 @@ extern "C" int m3d_anab_attend_bf16(const void *q, int q_cs, const void *khat, c
     a.q = q; a.khat = khat; a.vhat = vhatT; a.q_cs = q_cs; a.HW = HW; a.keys = keys; a.keys_pad = keys_pad;
     a.ep.out = out; a.ep.out_cs = out_cs; a.ep.out_mode = 0; a.ep.Cout = Cv; a.ep.scale = scale; a.ep.shift = shift;
     a.ep.res = res; a.ep.res_cs = res_cs; a.ep.res_mode = 1; a.ep.act = act ? 1 : 0; a.ep.sigmoid_from = -1;
-    static const int online = []() { const char *e = getenv("M3D_ANAB_ONLINE"); return e ? atoi(e) : 1; }();   // 0: the two-pass form (A/B)
+    static const int online = m3d_env_int("M3D_ANAB_ONLINE", 1);   // 0: the two-pass form (A/B)
     if (online) hipLaunchKernelGGL(bf16_anab_attend_kernel<true>, dim3(B * (HW / 128)), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(bf16_anab_attend_kernel<false>, dim3(B * (HW / 128)), dim3(256), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();

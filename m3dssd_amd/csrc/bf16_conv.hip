@@ -14,7 +14,6 @@
 //   Out-of-image taps, rows past M and the zero padding of K use buffer loads whose masked lanes read 0.
 //   blockIdx -> tile mapping is XCD-aware: each XCD owns a contiguous range of tiles, and the channel tiles of one pixel tile
 //   are adjacent (they re-read the same pixels from that XCD's L2).
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -606,8 +605,7 @@ static int ilog2_exact(int v)
 // (8x32 / 4 waves with 128x64 wave tiles: 819, spills).
 static int halo_env()
 {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("M3D_BF16_HALO"); v = e ? atoi(e) : 1; }
+    static const int v = m3d_env_int("M3D_BF16_HALO", 1);
     return v;
 }
 static int conv_bf16_variant(const m3d_conv_bf16_desc *d, long long *tiles)
@@ -697,8 +695,7 @@ extern "C" int m3d_conv_bf16_forward(const m3d_conv_bf16_desc *d, m3d_stream_t s
         a.tiles_m = (int)htiles;
         const dim3 hgrid(a.tiles_m * a.tiles_n);
 #define HLAUNCH(BN_, TW_, BM_, WV_, WK_) hipLaunchKernelGGL((bf16_conv3x3_halo_kernel<BN_, TW_, BM_, WV_, WK_>), hgrid, dim3(WV_ * 64), 0, st, a)
-        static int wk32 = -1;                 // M3D_BF16_HALO_WK=64: 64-channel weight steps for the 8 x 16 tile too (A/B)
-        if (wk32 < 0) { const char *e = getenv("M3D_BF16_HALO_WK"); wk32 = (e && atoi(e) == 64) ? 0 : 1; }
+        static const int wk32 = m3d_env_int("M3D_BF16_HALO_WK", 32) != 64;   // =64: 64-channel weight steps for the 8 x 16 tile too (A/B)
         if (variant == 2) HLAUNCH(64, 32, 256, 8, 64);
         else if (bn == 128) { if (wk32) HLAUNCH(128, 16, 128, 4, 32); else HLAUNCH(128, 16, 128, 4, 64); }
         else if (bn == 64) HLAUNCH(64, 16, 128, 4, 64);

@@ -229,8 +229,7 @@ __global__ __launch_bounds__(C6_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 // 1 if the kernel serves the descriptor (M3D_BF16_C64=0: the halo-tile kernel, A/B)
 int conv_c64_applicable(const m3d_conv_bf16_desc *d)
 {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("M3D_BF16_C64"); on = e ? atoi(e) : 1; }
+    static const int on = m3d_env_int("M3D_BF16_C64", 1);
     if (!on || d->dcn_offmask || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->groups != 1 || d->wgt_img_stride) return 0;
     if (d->Cin != 64 || d->Cout_pad != 64 || d->Kpad != 576 || d->out_mode != 0 || d->sigmoid_from >= 0) return 0;
     return d->W % 32 == 0 && d->H % 8 == 0;
@@ -240,14 +239,7 @@ int launch_conv_c64(const Bf16Args &a0, const m3d_conv_bf16_desc *d, hipStream_t
 {
     Bf16Args a = a0;
     a.res_bytes = d->res ? (unsigned)((long long)d->N * d->Ho * d->Wo * d->res_cs * 2) : 0u;
-    static int wgs = -1;
-    if (wgs < 0) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipGetLastError();
-        wgs = (cus / 8) * 8;                                       // one persistent workgroup per CU, a multiple of the 8 XCDs
-        if (wgs < 8) wgs = 8;
-    }
+    const int wgs = std::max(8, (m3d_cu_count() / 8) * 8);           // one persistent workgroup per CU, a multiple of the 8 XCDs
     if (d->res) hipLaunchKernelGGL(bf16_conv3x3_c64_kernel<true>, dim3(wgs), dim3(C6_NT), 0, st, a);
     else hipLaunchKernelGGL(bf16_conv3x3_c64_kernel<false>, dim3(wgs), dim3(C6_NT), 0, st, a);
     M3D_LAUNCH_CHECK();

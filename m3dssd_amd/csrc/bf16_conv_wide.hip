@@ -17,7 +17,6 @@
 //     16-byte loads per lane) goes out once per chunk right behind a weight issue and is written to LDS eight positions later.
 //   * Epilogue: bf16_tile.h (folded BatchNorm / bias, residual, LeakyReLU), through the wave's LDS region in whole pixel rows.
 // Weights: m3dssd_amd.engine_bf16.PackedBf16.wave3x3() -- [Cout_pad/128][Cin/32][9 taps][2 K-steps][4 channel blocks][64 lanes][8].
-#include <mutex>
 #include <type_traits>
 
 #include "bf16_tile.h"
@@ -344,6 +343,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     CW_TRACE();
 }
 
+#ifndef BF16_TRACE
+static int wide_scratch_bytes()
+{
+    static const int v = m3d_scratch_bytes(&bf16_conv3x3_wide_kernel<true>, &bf16_conv3x3_wide_kernel<false>);
+    return v;
+}
+#endif
+
 // 1 if the kernel serves the descriptor (geometry / modes only; the caller passes fragment-ordered weights in d->wgt_wave)
 int conv_wide_applicable(const m3d_conv_bf16_desc *d)
 {
@@ -353,21 +360,10 @@ int conv_wide_applicable(const m3d_conv_bf16_desc *d)
     // hand-counted vmcnt: a build in which the compiler spills (scratch loads / stores inside the K loop shift every wait) must not
     // run -- probed ONCE here, so that the engine routes the layer to the halo-tile kernel instead of failing at launch time
     // (launch_conv_wide keeps its REQUIRE as the backstop).  No device / probe failure = unknown = served.
-    static std::once_flag once;
-    static int on = 1;
-    std::call_once(once, []() {
-        const char *e = getenv("M3D_BF16_WIDE");
-        on = e ? atoi(e) : 1;
+    static const int on = m3d_env_int("M3D_BF16_WIDE", 1);
 #ifndef BF16_TRACE
-        hipFuncAttributes fa, fb;
-        if (on && hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&bf16_conv3x3_wide_kernel<true>)) == hipSuccess &&
-            hipFuncGetAttributes(&fb, reinterpret_cast<const void *>(&bf16_conv3x3_wide_kernel<false>)) == hipSuccess) {
-            if (fa.localSizeBytes + fb.localSizeBytes) on = 0;
-        } else {
-            (void)hipGetLastError();
-        }
+    if (on && wide_scratch_bytes() > 0) return 0;
 #endif
-    });
     return on;
 }
 
@@ -384,22 +380,13 @@ int launch_conv_wide(const Bf16Args &a, const m3d_conv_bf16_desc *d, hipStream_t
     const long long ob = (long long)d->N * d->H * d->W * d->out_cs * 2;
     M3D_REQUIRE(ob < (1ll << 31), "conv_bf16 (wide): output view must be < 2 GiB");
     wa.out_bytes = (unsigned)ob;
-    static bool attr = false;
-    if (!attr) {
-        M3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bf16_conv3x3_wide_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    4 * CW_WAVE_LDS));
-        M3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bf16_conv3x3_wide_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    4 * CW_WAVE_LDS));
-        hipFuncAttributes fa, fb;
-        M3D_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&bf16_conv3x3_wide_kernel<true>)));
-        M3D_HIP(hipFuncGetAttributes(&fb, reinterpret_cast<const void *>(&bf16_conv3x3_wide_kernel<false>)));
-        fa.localSizeBytes += fb.localSizeBytes;
-        // hand-counted vmcnt: a spill (scratch load / store) inside the K loop would shift every wait
+    static m3d_lds_state lds_res, lds_nores;
+    if (const int rc = m3d_raise_dyn_lds(&bf16_conv3x3_wide_kernel<true>, 4 * CW_WAVE_LDS, lds_res)) return rc;
+    if (const int rc = m3d_raise_dyn_lds(&bf16_conv3x3_wide_kernel<false>, 4 * CW_WAVE_LDS, lds_nores)) return rc;
+    // hand-counted vmcnt: a spill (scratch load / store) inside the K loop would shift every wait
 #ifndef BF16_TRACE
-        M3D_REQUIRE(fa.localSizeBytes == 0, "conv_bf16 (wide): this build of the kernel spills %d bytes per lane", (int)fa.localSizeBytes);
+    M3D_REQUIRE(wide_scratch_bytes() == 0, "conv_bf16 (wide): this build of the kernel spills %d bytes per lane", wide_scratch_bytes());
 #endif
-        attr = true;
-    }
     const dim3 grid(cdiv(wa.npatch, 4), d->Cout_pad / 128);
     if (d->res) hipLaunchKernelGGL(bf16_conv3x3_wide_kernel<true>, grid, dim3(256), 4 * CW_WAVE_LDS, st, wa);
     else hipLaunchKernelGGL(bf16_conv3x3_wide_kernel<false>, grid, dim3(256), 4 * CW_WAVE_LDS, st, wa);

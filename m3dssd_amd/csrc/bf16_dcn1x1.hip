@@ -141,8 +141,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // 1 if the kernel serves the descriptor (M3D_BF16_DCN1X1=0: the generic deformable tile, A/B)
 int dcn1x1_applicable(const m3d_conv_bf16_desc *d)
 {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("M3D_BF16_DCN1X1"); on = e ? atoi(e) : 1; }
+    static const int on = m3d_env_int("M3D_BF16_DCN1X1", 1);
     if (!on || !d->dcn_offmask || d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad != 0 || d->groups != 1 || d->wgt_img_stride) return 0;
     if (d->Cin != 128 || d->Cout_pad != 128 || d->Kpad != 128 || d->out_mode != 0 || d->sigmoid_from >= 0 || d->dcn_om_cs < 3) return 0;
     return 1;

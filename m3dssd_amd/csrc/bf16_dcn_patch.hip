@@ -24,7 +24,6 @@
 // the radius exceeds RMAX it only raises the tile's flag word in dcn_ws; the implicit-GEMM kernel launched behind this one recomputes
 // the 128-pixel tiles that touch a flagged patch tile and nothing else.  No pre-pass, no host round trip, and a few outlier pixels
 // no longer send a whole launch to the slow kernel.
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -369,8 +368,7 @@ void bf16_dcn_patch_kernel(const Bf16Args a, const void *__restrict__ wgt16, uns
 // Which patch kernel serves a descriptor: 0 = none (the implicit-GEMM kernel only), 16 / 8 = rows of the pixel patch.
 int dcn_patch_variant(const m3d_conv_bf16_desc *d)
 {
-    static int on = -1;                   // M3D_BF16_DCN_PATCH=0: implicit-GEMM kernel everywhere (A/B)
-    if (on < 0) { const char *e = getenv("M3D_BF16_DCN_PATCH"); on = e ? atoi(e) : 1; }
+    static const int on = m3d_env_int("M3D_BF16_DCN_PATCH", 1);                   // M3D_BF16_DCN_PATCH=0: implicit-GEMM kernel everywhere (A/B)
     if (!on || !d->dcn_offmask || !d->wgt_f16 || !d->dcn_ws) return 0;
     if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->groups != 1 || d->wgt_img_stride != 0) return 0;
     if (d->Cin % 32 != 0 || d->Cout_pad % 128 != 0 || d->W % 16 != 0 || d->dcn_om_cs < 28 || d->dcn_om_cs % 4 != 0) return 0;

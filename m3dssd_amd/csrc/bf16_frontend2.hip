@@ -549,20 +549,12 @@ extern "C" int m3d_frontend2_bf16_forward(const void *img, int is_u8, int img_h,
     a.trace = g_front2_trace;
 #endif
     // persistent workgroups: occupancy x CUs of them (a multiple of the 8 XCDs), fewer when the launch has fewer tiles
-    int dev = 0, ncu = 0;
-    M3D_HIP(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+    const int ncu = m3d_cu_count();
     const int occ = front2_occ();
     const int slots = imin(a.tiles_per_xcd, (occ * ncu / 8 > 0 ? occ * ncu / 8 : 1));
     const int grid = slots * 8;
     // (a spill would be restored over the data of an in-flight asm load: refuse a build that uses scratch memory)
-    static int scratch = -1;
-    if (scratch < 0) {
-        hipFuncAttributes fa0, fa1;
-        M3D_HIP(hipFuncGetAttributes(&fa0, reinterpret_cast<const void *>(&bf16_frontend2_kernel<2, false>)));
-        M3D_HIP(hipFuncGetAttributes(&fa1, reinterpret_cast<const void *>(&bf16_frontend2_kernel<2, true>)));
-        scratch = (int)(fa0.localSizeBytes + fa1.localSizeBytes);
-    }
+    static const int scratch = m3d_scratch_bytes(&bf16_frontend2_kernel<2, false>, &bf16_frontend2_kernel<2, true>);
     M3D_REQUIRE(scratch == 0, "frontend2_bf16: the kernel was built with register spills (%d bytes of scratch)", scratch);
     if (is_u8) hipLaunchKernelGGL((bf16_frontend2_kernel<2, true>), dim3(grid), dim3(F2_NT), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((bf16_frontend2_kernel<2, false>), dim3(grid), dim3(F2_NT), 0, (hipStream_t)stream, a);

@@ -333,12 +333,7 @@ extern "C" int m3d_head_mlp_bf16_forward(const m3d_head_bf16_desc *d, m3d_stream
     a.trace = g_head_trace;
 #endif
     // one workgroup per CU (132 KB of LDS): the CUs are split between the heads of the launch and every workgroup walks tiles
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
+    const int ncu = m3d_cu_count();
     const int nb = std::max(1, std::min(a.tiles_m, ncu / d->groups));
     hipLaunchKernelGGL(bf16_head_mlp_kernel, dim3(nb, d->groups), dim3(512), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();

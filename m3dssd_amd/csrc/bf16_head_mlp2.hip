@@ -481,18 +481,8 @@ extern "C" int m3d_head_tail2_bf16_forward(const m3d_tail2_bf16_desc *d, m3d_str
     Tail2Args a;
     a.in = d->in; a.waf = d->waf; a.wbf = d->wbf; a.t1 = d->t1; a.t2 = d->t2; a.out = d->out; a.out_img_stride = d->out_img_stride;
     a.in_cs = d->in_cs; a.M = (int)d->M; a.HW = d->HW; a.Cout = d->Cout; a.tiles_m = cdiv(d->M, 128);
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
-    static int scratch = -1;
-    if (scratch < 0) {
-        hipFuncAttributes fa;
-        M3D_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&bf16_tail2_kernel)));
-        scratch = (int)fa.localSizeBytes;
-    }
+    const int ncu = m3d_cu_count();
+    static const int scratch = m3d_scratch_bytes(&bf16_tail2_kernel);
     M3D_REQUIRE(scratch == 0, "head_tail2_bf16: the kernel was built with register spills (%d bytes of scratch)", scratch);
     hipLaunchKernelGGL(bf16_tail2_kernel, dim3(std::max(1, std::min(a.tiles_m, ncu))), dim3(512), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();
@@ -614,12 +604,7 @@ extern "C" int m3d_anab_qkvs_bf16_forward(const m3d_qkvs_bf16_desc *d, m3d_strea
     a.in = d->in; a.wf = d->wf; a.q = d->q; a.kv = d->kv; a.s = d->s;
     a.in_cs = d->in_cs; a.q_cs = d->q_cs; a.kv_cs = d->kv_cs; a.s_cs = d->s_cs; a.M = (int)d->M; a.tiles_m = cdiv(d->M, 128);
     a.q_rows = d->q_rows; a.kv_rows = d->kv_rows; a.s_rows = d->s_rows;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
+    const int ncu = m3d_cu_count();
     hipLaunchKernelGGL(bf16_qkvs_kernel, dim3(std::max(1, std::min(a.tiles_m, ncu))), dim3(512), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
@@ -640,18 +625,8 @@ extern "C" int m3d_head_mlp2_bf16_forward(const m3d_head2_bf16_desc *d, m3d_stre
     a.trace = g_head2_trace;
 #endif
     // one workgroup per CU (130 KB of LDS, 512 threads): the CUs are split between the heads of the launch, every workgroup walks tiles
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
-    static int scratch = -1;          // resident weights in registers: a spilled build would re-read them from scratch memory per tile
-    if (scratch < 0) {
-        hipFuncAttributes fa;
-        M3D_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&bf16_head2_kernel)));
-        scratch = (int)fa.localSizeBytes;
-    }
+    const int ncu = m3d_cu_count();
+    static const int scratch = m3d_scratch_bytes(&bf16_head2_kernel);          // resident weights in registers: a spilled build would re-read them from scratch memory per tile
     M3D_REQUIRE(scratch == 0, "head_mlp2_bf16: the kernel was built with register spills (%d bytes of scratch)", scratch);
     const int nb = std::max(1, std::min(a.tiles_m, ncu / d->groups));
     hipLaunchKernelGGL(bf16_head2_kernel, dim3(nb, d->groups), dim3(512), 0, (hipStream_t)stream, a);

@@ -6,7 +6,6 @@
 //   m3d_upsample2x_add_bf16 . IDAUp depthwise ConvTranspose2d(4, s2, p1) + skip add (pose_dla_dcn.py:536-538,550-552)
 //   m3d_f32_to_bf16 ......... operand conversion (pooled ANAB keys / values)
 //   m3d_softmax_rows_bf16 ... nn.Softmax(dim=-1) on the fp32 logits, probabilities written as bf16 (attention.py:208)
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -334,7 +333,7 @@ extern "C" int m3d_upsample2x_add_bf16(const void *in, int in_cs, const float *w
 {
     M3D_REQUIRE(in && wgt && out && C % 8 == 0 && in_cs % 8 == 0 && out_cs % 8 == 0 && (!skip || skip_cs % 8 == 0),
                 "upsample2x_add_bf16: C and strides must be x8");
-    static const int rows_form = []() { const char *e = getenv("M3D_UPSAMPLE_ROWS"); return e ? atoi(e) : 1; }();
+    static const int rows_form = m3d_env_int("M3D_UPSAMPLE_ROWS", 1);
     if (rows_form == 1 && (C == 128 || C == 256 || C == 64) && N <= 65535) {
         const int nseg = 256 / (C / 8), P = cdiv(W, nseg);
         const dim3 grid(2 * H, N);

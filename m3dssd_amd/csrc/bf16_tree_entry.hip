@@ -22,7 +22,6 @@
 // 0.16 / 0.19 ms), and persistent workgroups with the next tile's loads in flight under the MFMAs on top of that (0.25 / 0.21 / 0.16
 // / 0.23 ms): the per-tile VALU work -- piece addresses, bf16 -> fp16, store addresses: ~600 instructions per wave against 80-160
 // MFMAs -- is what bounds the kernel, not the exposed latencies.
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -243,7 +242,7 @@ extern "C" int m3d_tree_entry_bf16_forward(const m3d_tree_entry_bf16_desc *d, m3
     a.in_cs = d->in_cs; a.t_cs = d->t_cs; a.res_cs = d->res_cs; a.bottom_cs = d->bottom_cs;
     a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.Ho = d->H / 2; a.Wo = d->W / 2;
     a.tiles_x = cdiv(a.Wo, TE_TW); a.tiles_y = cdiv(a.Ho, TE_TH); a.nchunks = d->Cin / 32;
-    static const int cb64 = []() { const char *e = getenv("M3D_TE_CB64"); return e ? atoi(e) : 0; }();   // experiments: 64-channel blocks everywhere
+    static const int cb64 = m3d_env_int("M3D_TE_CB64", 0);   // experiments: 64-channel blocks everywhere
     const bool wide = d->Cout % 128 == 0 && !cb64;
     a.cblocks = d->Cout / (wide ? 128 : 64);
     const long long grid = (long long)a.tiles_x * a.tiles_y * d->N * a.cblocks;

@@ -4,7 +4,10 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "m3dssd_hip.h"
+#include "per_device.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -160,6 +163,33 @@ int m3d_pack_conv_weight_slice(const float *w, int Ctot, int c0, float *packed, 
             return M3D_E_HIP;                                                       \
         }                                                                           \
     } while (0)
+
+// ---- launcher state: what a host-side launcher finds out once (definitions in api.hip) -----------------------
+// Per DEVICE ordinal (per_device.h): the raised dynamic-LDS limit, the CU count, the zero page of igemm_conv.hip.  Per PROCESS: the
+// spilled bytes of a kernel (a property of the code object, the same on every device) and the M3D_* tuning knobs.
+//
+// hipFuncAttributeMaxDynamicSharedMemorySize is taken to be a PER-DEVICE attribute of the kernel: a process that drives several GPUs
+// (nn.DataParallel replica engines, one engine per device) needs it on each of them, so it is set on the current device, once per
+// ordinal (assumed, not measured on a multi-GPU host; right either way).  Each call site owns a `static m3d_lds_state` (inside a
+// template: one per instantiation).  M3D_OK, or M3D_E_HIP with the message of M3D_HIP; the outcome is remembered, a refusal included.
+typedef PerDevice<int> m3d_lds_state;            // the hipError_t of the raise
+int m3d_raise_dyn_lds_(const void *kernel, int bytes, m3d_lds_state &state, const char *what, const char *file, int line);
+#define m3d_raise_dyn_lds(kernel, bytes, state) \
+    m3d_raise_dyn_lds_(reinterpret_cast<const void *>(kernel), bytes, state, #kernel, __FILE__, __LINE__)
+int m3d_cu_count();                              // CUs of the current device; 256 when the runtime cannot tell (its error is cleared)
+// Sum of hipFuncAttributes::localSizeBytes (register spills) of the kernels, -1 when a probe fails (no device; the runtime's error
+// is cleared).  Callers keep the result in a `static const int`: it belongs to the code object, not to a device.
+int m3d_scratch_bytes_(const void *const *kernels, int n);
+template <typename... K>
+static inline int m3d_scratch_bytes(K... kernels)
+{
+    const void *const k[] = {reinterpret_cast<const void *>(kernels)...};
+    return m3d_scratch_bytes_(k, (int)sizeof...(K));
+}
+// A tuning knob, `e ? atoi(e) : dflt`: kept by its reader in a function-local `static const int` (read once per process,
+// thread-safe); a knob read in more than one file has its accessor here.
+int m3d_env_int(const char *name, int dflt);
+static inline int m3d_knob_ablate() { static const int v = m3d_env_int("M3D_ABLATE", 0); return v; }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline int imin(int a, int b) { return a < b ? a : b; }

@@ -17,7 +17,6 @@
 //   * B operands: [Cout_pad, kh*kw*Cin] tap-major weights in MFMA-fragment order [Cout_pad/32][K/8][h=2][r=32][t=4]
 //     (m3dssd_amd.engine.pack_frag): one coalesced 1 KB load per column tile and k-group, two register sets.
 // A step covers the 32 channels (one 128-byte line) of one tap: 4 k-groups x 16 MFMAs.
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -537,10 +536,9 @@ static int conv_wave_plan(const m3d_conv_desc *d, bool enforce_min, int *splits,
     const long long M = (long long)d->N * d->Ho * d->Wo;
     const long long base = ((M + 31) / 32) * (d->Cout_pad / cw);
     if (base >= (1ll << 28)) return 0;
-    static int wave_min = -1, dcn_min = -1, splitk = -1;
-    if (wave_min < 0) { const char *e = getenv("M3D_CONV_WAVE_MIN"); wave_min = e ? atoi(e) : 900; }
-    if (dcn_min < 0) { const char *e = getenv("M3D_DCN_WAVE_MIN"); dcn_min = e ? atoi(e) : 1500; }
-    if (splitk < 0) { const char *e = getenv("M3D_CONV_WAVE_SPLITK"); splitk = e ? atoi(e) : 1; }
+    static const int wave_min = m3d_env_int("M3D_CONV_WAVE_MIN", 900);
+    static const int dcn_min = m3d_env_int("M3D_DCN_WAVE_MIN", 1500);
+    static const int splitk = m3d_env_int("M3D_CONV_WAVE_SPLITK", 1);
     const long long need = d->dcn_offmask ? dcn_min : wave_min;
     const int nss = *ss_per;
     if (base < need && splitk && d->splitk_ws) {
@@ -621,8 +619,7 @@ static int conv_wave_run(const m3d_conv_desc *d_, hipStream_t stream, bool wgspl
     const int cw = d->Cout_pad % 128 == 0 ? 128 : (d->Cout_pad % 64 == 0 ? 64 : 32);
     a.M = (int)M; a.KG = d->kh * d->kw * d->Cin / 8; a.tiles_n = d->Cout_pad / cw;
     a.act = d->act; a.res_mode = d->res_mode; a.sigmoid_from = d->sigmoid_from; a.w_img_stride = d->wgt_img_stride;
-    static int vec_epi = -1;       // M3D_WAVE_VEC_EPILOGUE=0: 4-byte stores straight from the accumulators (A/B)
-    if (vec_epi < 0) { const char *e = getenv("M3D_WAVE_VEC_EPILOGUE"); vec_epi = e ? atoi(e) : 1; }
+    static const int vec_epi = m3d_env_int("M3D_WAVE_VEC_EPILOGUE", 1);       // M3D_WAVE_VEC_EPILOGUE=0: 4-byte stores straight from the accumulators (A/B)
     a.vec_out = vec_epi && d->out_cs % 4 == 0 && ((uintptr_t)d->out & 15) == 0 &&
                 (!d->res || (d->res_cs % 4 == 0 && ((uintptr_t)d->res & 15) == 0)) &&
                 (!d->scale || ((uintptr_t)d->scale & 15) == 0) && (!d->shift || ((uintptr_t)d->shift & 15) == 0);

@@ -364,12 +364,8 @@ static int launch_mlp(const std::conditional_t<ROWS, MlpBatchRows, MlpBatch> &b,
 {
     constexpr size_t smem = (size_t)(MLP_BM * MLP_LDA) * sizeof(float) + (ROWS ? MLP_BM * sizeof(int) : 0);
     auto kern = head_mlp_kernel<HAS_L1, N3, CIN, ROWS>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        M3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem));
-        attr_set = true;
-    }
+    static m3d_lds_state lds;                    // one per kernel instantiation
+    if (const int rc = m3d_raise_dyn_lds(kern, (int)smem, lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(cdiv(b.head[0].M, MLP_BM), n), dim3(256), smem, stream, b);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
@@ -393,8 +389,7 @@ static int fill_mlp_args(const m3d_mlp_desc *d, MlpArgs &a)
     a.scale[0] = d->s1; a.scale[1] = d->s2; a.scale[2] = d->s3;
     a.shift[0] = d->t1; a.shift[1] = d->t2; a.shift[2] = d->t3;
     a.out = d->out; a.out_img_stride = d->out_img_stride; a.Cout = d->Cout; a.Cout_pad = d->Cout_pad;
-    static int abl = -1;
-    if (abl < 0) { const char *e = getenv("M3D_ABLATE_MLP"); abl = e ? atoi(e) : 0; }
+    static const int abl = m3d_env_int("M3D_ABLATE_MLP", 0);
     a.ablate = abl;
     return M3D_OK;
 }

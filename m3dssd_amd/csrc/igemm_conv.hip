@@ -19,7 +19,6 @@
 //   sigmoid, and writes NHWC (lanes along channels: 128 B per half-wave) or, in SWAP mode, planar
 //   NCHW (operands swapped so lanes run along pixels) -- the layout the RPN outputs need.
 // * blockIdx is remapped so each XCD (private L2) works on a contiguous range of tiles.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -431,12 +430,8 @@ static int launch_igemm(const IgemmArgs &a, hipStream_t stream)
 {
     constexpr size_t smem = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
     auto kern = igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, DEFORM, SWAP>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        M3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
+    static m3d_lds_state lds;                    // one per tile instantiation
+    if (const int rc = m3d_raise_dyn_lds(kern, (int)smem, lds)) return rc;
     IgemmArgs b = a;
     b.tiles_m = cdiv(a.M, BM);
     b.tiles_n = cdiv(a.Cout_pad, BN);
@@ -461,8 +456,7 @@ static int choose_split(const m3d_conv_desc *d, const TileChoice &t, int *kt_per
     const long long M = (long long)d->N * d->Ho * d->Wo;
     const int KT = d->kh * d->kw * d->Cin / t.bk;
     *kt_per = KT;
-    static int enabled = -1;                     // tuning knob (experiments only): M3D_SPLITK=0 disables
-    if (enabled < 0) { const char *e = getenv("M3D_SPLITK"); enabled = e ? atoi(e) : 1; }
+    static const int enabled = m3d_env_int("M3D_SPLITK", 1);          // tuning knob (experiments only): 0 disables
     if (!enabled || d->out_nchw || d->wgt_img_stride) return 1;
     const long long blocks = ((M + t.bm - 1) / t.bm) * ((d->Cout_pad + t.bn - 1) / t.bn);
     if (blocks > 256) return 1;
@@ -484,16 +478,12 @@ static int choose_tile(const m3d_conv_desc *d, TileChoice *t)
     if (t->bk == 16) t->bn = 32;
     t->bm = 128;
     if (t->bn >= 64) {
-        static int thr = -1;                     // tuning knob (experiments only): M3D_BM_THRESHOLD
-        if (thr < 0) { const char *e = getenv("M3D_BM_THRESHOLD"); thr = e ? atoi(e) : 400; }
+        static const int thr = m3d_env_int("M3D_BM_THRESHOLD", 400);  // tuning knob (experiments only)
         const long long blocks128 = ((M + 127) / 128) * ((d->Cout_pad + t->bn - 1) / t->bn);
         if (blocks128 < thr) t->bm = 64;         // under two blocks per CU: smaller tiles fill the chip
     }
-    {
-        static int fbn = -1;                     // tuning knob (experiments only): M3D_FORCE_BN
-        if (fbn < 0) { const char *e = getenv("M3D_FORCE_BN"); fbn = e ? atoi(e) : 0; }
-        if (fbn && t->bk == 32 && t->bn > fbn && !d->out_nchw) t->bn = fbn;
-    }
+    static const int fbn = m3d_env_int("M3D_FORCE_BN", 0);            // tuning knob (experiments only)
+    if (fbn && t->bk == 32 && t->bn > fbn && !d->out_nchw) t->bn = fbn;
     if (d->wgt_img_stride && (d->Ho * d->Wo) % t->bm != 0) {
         t->bm = 64;
         if ((d->Ho * d->Wo) % 64 != 0) return -1;
@@ -525,16 +515,15 @@ extern "C" int m3d_conv2d_tile(const m3d_conv_desc *d, int *bm, int *bn, int *bk
 // 256 zero bytes per device: padding taps of the igemm load from here (hipMalloc'ed once, never freed).
 static const float *zero_page()
 {
-    static const float *pages[64] = {nullptr};
+    static PerDevice<const float *> pages;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    if (!pages[dev]) {
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= M3D_MAX_DEVICES) return nullptr;
+    return pages.get(dev, []() -> std::optional<const float *> {   // a failed allocation is not remembered: the next call tries again
         void *p = nullptr;
-        if (hipMalloc(&p, 256) != hipSuccess) return nullptr;
-        if (hipMemset(p, 0, 256) != hipSuccess) return nullptr;
-        pages[dev] = (const float *)p;
-    }
-    return pages[dev];
+        if (hipMalloc(&p, 256) != hipSuccess) return std::nullopt;
+        if (hipMemset(p, 0, 256) != hipSuccess) return std::nullopt;
+        return (const float *)p;
+    }).value_or(nullptr);
 }
 
 extern "C" int m3d_conv2d_forward(const m3d_conv_desc *d, m3d_stream_t stream_)
@@ -570,11 +559,7 @@ extern "C" int m3d_conv2d_forward(const m3d_conv_desc *d, m3d_stream_t stream_)
     a.M = (int)M; a.Ktot = d->kh * d->kw * d->Cin; a.KT = a.Ktot / t.bk;
     a.tiles_m = a.tiles_n = 0;
     a.act = d->act; a.sigmoid_from = d->sigmoid_from; a.res_mode = d->res_mode;
-    {
-        static int abl = -1;
-        if (abl < 0) { const char *e = getenv("M3D_ABLATE"); abl = e ? atoi(e) : 0; }
-        a.ablate = abl;
-    }
+    a.ablate = m3d_knob_ablate();
 
     a.ws = nullptr; a.splits = 1; a.kt_per = a.KT;
 #ifdef IGEMM_TRACE

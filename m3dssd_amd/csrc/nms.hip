@@ -271,7 +271,7 @@ extern "C" int m3d_nms_sorted_dev(const float *boxes_dev, int B, int n, int box_
     M3D_REQUIRE(boxes_dev && mask_ws && keep_dev, "nms: null pointer");
     M3D_REQUIRE(box_stride >= 4, "nms: box_stride must be >= 4");
     const int cb = (n + NMS_TPB - 1) / NMS_TPB;
-    static const int div_form = []() { const char *e = getenv("M3D_NMS_DIV"); return e ? atoi(e) : 0; }();
+    static const int div_form = m3d_env_int("M3D_NMS_DIV", 0);
     if (div_form) hipLaunchKernelGGL(nms_mask_div_kernel, dim3(cb, cb, B), dim3(NMS_TPB), 0, stream, n, box_stride, thresh, boxes_dev,
                                      (unsigned long long *)mask_ws);
     else hipLaunchKernelGGL(nms_mask_kernel, dim3(cb, cb, B), dim3(NMS_TPB), 0, stream, n, box_stride, thresh, boxes_dev,

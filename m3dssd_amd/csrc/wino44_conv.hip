@@ -17,10 +17,6 @@
 //   * A^T M A (36 -> 16 values per (tile, channel)), folded BatchNorm / bias, residual and LeakyReLU run in registers.
 // fp32 error: the F(4x4,3x3) transforms amplify rounding ~7x relative to F(2x2,3x3) / direct summation (rms 1.5e-6 vs 2.2e-7
 // of the output scale at Cin = 128, max 1.5e-5; tools/ and DESIGN.md); U = G g G^T is computed in fp64 and rounded once.
-#include <stdlib.h>
-
-#include <mutex>
-
 #include <type_traits>
 
 #include "common.h"
@@ -666,21 +662,12 @@ extern "C" int m3d_conv3x3_c16_wino(const float *in, int in_cs, const float *U, 
 // r3).  No device / probe failure = unknown = served (the launcher keeps its own REQUIRE as the backstop).
 static int w44_scratch_bytes()
 {
-    static std::once_flag once;
-    static int scratch = 0;
-    std::call_once(once, []() {
 #ifndef WINO_TRACE
-        hipFuncAttributes f1, f2, f3, f4;
-        if (hipFuncGetAttributes(&f1, reinterpret_cast<const void *>(&wino44_kernel<1, 1>)) == hipSuccess &&
-            hipFuncGetAttributes(&f2, reinterpret_cast<const void *>(&wino44_kernel<2, 1>)) == hipSuccess &&
-            hipFuncGetAttributes(&f3, reinterpret_cast<const void *>(&wino44_kernel<1, 2>)) == hipSuccess &&
-            hipFuncGetAttributes(&f4, reinterpret_cast<const void *>(&wino44_kernel<1, 2, 2>)) == hipSuccess)
-            scratch = (int)(f1.localSizeBytes + f2.localSizeBytes + f3.localSizeBytes + f4.localSizeBytes);
-        else
-            (void)hipGetLastError();
+    static const int v = m3d_scratch_bytes(&wino44_kernel<1, 1>, &wino44_kernel<2, 1>, &wino44_kernel<1, 2>, &wino44_kernel<1, 2, 2>);
+    return v < 0 ? 0 : v;
+#else
+    return 0;
 #endif
-    });
-    return scratch;
 }
 static int w44_build_ok() { return w44_scratch_bytes() == 0 ? 1 : 0; }
 
@@ -700,10 +687,11 @@ extern "C" int m3d_wino44_applicable(const m3d_conv_desc *d)
 // Form of the split-K launches: M3D_W44_SPLIT_NB = 2 (128-channel workgroups, one per CU) or 1 (64-channel workgroups, two per CU:
 // `fill` = 480 workgroups); M3D_W44_SPLIT_FILL overrides the number of workgroups a layer must reach to run unsplit.
 // 3 = K-pair workgroups (64-channel, 512 threads, one per CU) inside every global slice: half the slices, half the workspace.
-static int w44_split_nb() { static const int v = []() { const char *e = getenv("M3D_W44_SPLIT_NB"); return e ? atoi(e) : 1; }(); return (v == 2 || v == 3) ? v : 1; }
+static int w44_split_nb() { static const int v = m3d_env_int("M3D_W44_SPLIT_NB", 1); return (v == 2 || v == 3) ? v : 1; }
+static int w44_occ2() { static const int v = m3d_env_int("M3D_W44_OCC2", 1); return v; }   // 0: one 64-channel workgroup per CU
 static int w44_split_fill()
 {
-    static const int v = []() { const char *e = getenv("M3D_W44_SPLIT_FILL"); return e ? atoi(e) : 0; }();
+    static const int v = m3d_env_int("M3D_W44_SPLIT_FILL", 0);
     return v > 0 ? v : (w44_split_nb() == 1 ? 400 : 200);
 }
 
@@ -733,11 +721,10 @@ extern "C" int m3d_wino44_splitk_plan(const m3d_conv_desc *d, int *splits, long 
 extern "C" int m3d_wino44_kpair(const m3d_conv_desc *d)
 {
     if (!d || !m3d_wino44_applicable(d)) return 0;
-    static const int kpair_max = []() { const char *e = getenv("M3D_W44_KPAIR_MAX"); return e ? atoi(e) : 300; }();
-    static const int occ2 = []() { const char *e = getenv("M3D_W44_OCC2"); return e ? atoi(e) : 1; }();
+    static const int kpair_max = m3d_env_int("M3D_W44_KPAIR_MAX", 300);
     const int ns = d->Cin / 16;
     const long long wgs = (long long)cdiv(d->N * (d->H / 4) * (d->W / 4), 16) * (d->Cout_pad / 64);
-    return (occ2 && wgs <= kpair_max && ns % 2 == 0 && ns / 2 >= 4) ? 1 : 0;
+    return (w44_occ2() && wgs <= kpair_max && ns % 2 == 0 && ns / 2 >= 4) ? 1 : 0;
 }
 
 extern "C" int m3d_wino44_conv3x3_forward_touch(const m3d_conv_desc *d, int nb, const void *touch, long long touch_bytes,
@@ -796,7 +783,6 @@ extern "C" int m3d_wino44_conv3x3_forward_touch(const m3d_conv_desc *d, int nb, 
     // 64-channel workgroups, two per CU (round 4: faster than the 128-channel form on every layer measured); nb = 2 asks for the
     // 128-channel form (one per CU, the whole register file) explicitly
     const bool nb2 = d->Cout_pad % 128 == 0 && nb == 2;
-    static const int occ2 = []() { const char *e = getenv("M3D_W44_OCC2"); return e ? atoi(e) : 1; }();
     // K-pair workgroups (512 threads, the two halves of the input channels side by side) where the 64-channel workgroups would
     // leave more than ~40 % of the 512 CU slots empty and each half still runs >= 4 stages
     if (!nb2 && m3d_wino44_kpair(d)) {
@@ -806,7 +792,7 @@ extern "C" int m3d_wino44_conv3x3_forward_touch(const m3d_conv_desc *d, int nb, 
         return M3D_OK;
     }
     if (nb2) hipLaunchKernelGGL((wino44_kernel<2, 1>), dim3(strips, d->Cout_pad / 128), dim3(256), 0, (hipStream_t)stream, a);
-    else if (occ2) hipLaunchKernelGGL((wino44_kernel<1, 2>), dim3(strips, d->Cout_pad / 64), dim3(256), 0, (hipStream_t)stream, a);
+    else if (w44_occ2()) hipLaunchKernelGGL((wino44_kernel<1, 2>), dim3(strips, d->Cout_pad / 64), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((wino44_kernel<1, 1>), dim3(strips, d->Cout_pad / 64), dim3(256), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();
     return M3D_OK;

@@ -16,7 +16,6 @@
 //   * v_mfma_f32_32x32x2_f32 with the k-permuted fragment order (lane half h, step t -> k = 8g + 4h + t);
 //   * the 16 accumulated M[xi] meet in LDS, A^T M A + affine/residual/LeakyReLU/sigmoid are applied per (tile, cout)
 //     and written NHWC with lanes along channels.
-#include <stdlib.h>
 #include <type_traits>
 
 #include "common.h"
@@ -620,10 +619,9 @@ __global__ __launch_bounds__(64) void wino_wave_kernel(const WinoArgs a)
 // wave threshold, M3D_WINO_SPLITK=1 recommends the split form (off: it measured slower than the LDS kernel).
 static int wino_plan(const m3d_conv_desc *d, bool have_ws, int *splits, int *ks_per)
 {
-    static int wave_min = -1, variant = -1, splitk = -1;
-    if (wave_min < 0) { const char *e = getenv("M3D_WINO_WAVE_MIN"); wave_min = e ? atoi(e) : 800; }
-    if (variant < 0) { const char *e = getenv("M3D_WINO_VARIANT"); variant = e ? atoi(e) : 1; }
-    if (splitk < 0) { const char *e = getenv("M3D_WINO_SPLITK"); splitk = e ? atoi(e) : 0; }
+    static const int wave_min = m3d_env_int("M3D_WINO_WAVE_MIN", 800);
+    static const int variant = m3d_env_int("M3D_WINO_VARIANT", 1);
+    static const int splitk = m3d_env_int("M3D_WINO_SPLITK", 0);
     const int KS = d->Cin / 8;
     *splits = 1;
     *ks_per = KS;
@@ -682,21 +680,13 @@ extern "C" int m3d_wino_conv3x3_forward_ex(const m3d_conv_desc *d, int variant, 
     a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.Cout_pad = d->Cout_pad;
     a.TH = d->H / 2; a.TW = d->W / 2; a.NT = d->N * a.TH * a.TW; a.tiles_n = d->Cout_pad / 32;
     a.act = d->act; a.sigmoid_from = d->sigmoid_from; a.res_mode = d->res_mode;
-    {
-        static int abl = -1;
-        if (abl < 0) { const char *e = getenv("M3D_ABLATE"); abl = e ? atoi(e) : 0; }
-        a.ablate = abl;
-    }
+    a.ablate = m3d_knob_ablate();
 #ifdef WINO_TRACE
     a.trace = g_wino_trace;
 #endif
     constexpr size_t smem = (size_t)16 * WINO_T * WINO_LDM * sizeof(float);   // 135,168 B (>= 2 V buffers: 131,072 B)
-    static bool attr_set = false;
-    if (!attr_set) {
-        M3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wino_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem));
-        attr_set = true;
-    }
+    static m3d_lds_state lds;
+    if (const int rc = m3d_raise_dyn_lds(wino_kernel, (int)smem, lds)) return rc;
     M3D_REQUIRE(variant >= -1 && variant <= 1, "wino: variant must be -1 (auto), 0 (LDS kernel) or 1 (wave kernel)");
     int splits = 1, ks_per = d->Cin / 8;
     const int planned = wino_plan(d, d->splitk_ws != nullptr, &splits, &ks_per);

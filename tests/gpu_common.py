@@ -121,22 +121,22 @@ def _parity_log(name, payload):
 
 
 # ------------------------------------------------------------------------------------ fused head + graph
-def _head_case(seed, cin, cout, cpad, dev, n=2, h=13, w=21):
-    """One 3-/2-layer head: returns (MlpDesc, device output, torch reference, keep-alive list)."""
+def _head_case(seed, cin, cout, cpad, dev, n=2, h=13, w=21, ref_dtype=torch.float32):
+    """One 3-/2-layer head: returns (MlpDesc, device output, torch reference (computed in ref_dtype), keep-alive list)."""
     from m3dssd_amd import _hip
     from m3dssd_amd.engine import pack_frag
     from m3dssd_amd.host import standalone as S
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(n, cin, h, w, generator=g)
     layers = []
-    ref = x
+    ref = x.to(ref_dtype)
     chans = ([cin, 256] if cin == 128 else [256]) + [256, cout]
     for li in range(len(chans) - 1):
         wt = torch.randn(chans[li + 1], chans[li], 1, 1, generator=g) / chans[li] ** 0.5
         b = torch.randn(chans[li + 1], generator=g) * 0.1
         last = li == len(chans) - 2
         bn = None
-        ref = F.conv2d(ref, wt, b)
+        ref = F.conv2d(ref, wt.to(ref_dtype), b.to(ref_dtype))
         if not last:
             bn = torch.nn.BatchNorm2d(chans[li + 1]).eval()
             with torch.no_grad():
@@ -144,7 +144,8 @@ def _head_case(seed, cin, cout, cpad, dev, n=2, h=13, w=21):
                 bn.bias.normal_(0, 0.2, generator=g)
                 bn.running_mean.normal_(0, 0.2, generator=g)
                 bn.running_var.uniform_(0.5, 1.5, generator=g)
-            ref = F.leaky_relu(bn(ref), 0.01)
+            ref = F.leaky_relu(bn.to(ref_dtype)(ref), 0.01)
+            bn = bn.float()
         layers.append((wt, b, bn, last))
     v, _ = S._to_nhwc(x.to(dev))
     d = _hip.MlpDesc()

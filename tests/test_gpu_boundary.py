@@ -115,6 +115,118 @@ def test_module_on_a_device_that_is_not_current():
         net.engine().forward(x.cpu().to("cuda:0") if n_dev > 1 else x[:, :, :100])   # wrong device / bad size
 
 
+_FIRST_LAUNCH_SCRIPT = r"""
+import ctypes, json, sys
+import numpy as np
+import torch
+import torch.nn.functional as F
+sys.path[:0] = [%(root)r, %(tests)r]
+import gpu_common as G
+from m3dssd_amd import _hip
+from m3dssd_amd.host import standalone as S
+
+L = _hip.lib()
+BF16 = torch.bfloat16
+
+
+def bf16_close(got, ref):                   # tests/test_gpu_bf16.py:_check, bf16 output: one rounding of the result + fp32 summation noise
+    scale = ref.abs().max().item() + 1e-6
+    bad = (got.double() - ref).abs() > 2.0 ** -8 * ref.abs() + 1e-3 * scale
+    assert not bad.any(), ((got.double() - ref).abs().max().item(), scale, int(bad.sum()))
+
+
+def families(dev):
+    out = {}
+    # F(2x2,3x3) Winograd, 135 168 B of LDS, on the shape of WINO_CASES[0] (tests/test_gpu_conv.py: _relerr < 2e-4)
+    n, ci, h, w, co = G.WINO_CASES[0][:5]
+    g = torch.Generator().manual_seed(1)
+    x, wt = torch.randn(n, ci, h, w, generator=g), torch.randn(co, ci, 3, 3, generator=g) / (ci * 9) ** 0.5
+    v, _ = S._to_nhwc(x.to(dev))
+    o, keep = S.conv_nhwc(v, wt.to(dev), None, None, 1, 1, act=1, wino=True)
+    out["wino"] = S._to_nchw(o, co).cpu()
+    assert G._relerr(out["wino"], F.leaky_relu(F.conv2d(x.double(), wt.double(), padding=1), 0.01)) < 2e-4
+    # fused head MLP: the smallest case of test_fused_head_mlp_matches_torch (_relerr < 2e-4)
+    d, o, ref, keep = G._head_case(133, 128, 5, 64, dev, ref_dtype=torch.float64)
+    _hip.check(L.m3d_head_mlp_forward(ctypes.byref(d), S._stream()))
+    out["head_mlp"] = o.view(ref.shape).cpu()
+    assert G._relerr(out["head_mlp"], ref) < 2e-4
+    # implicit GEMM on its 128 x 128 x 32 tile, the only one above 64 KB of LDS (test_conv_igemm_matches_torch: _relerr < 2e-4)
+    n, ci, h, w, co = 1, 32, 128, 200, 256
+    x, wt = torch.randn(n, ci, h, w, generator=g), torch.randn(co, ci, 1, 1, generator=g) / ci ** 0.5
+    v, _ = S._to_nhwc(x.to(dev))
+    wp, _, cop, _, _ = S._pack(wt.to(dev), v.c, 32)
+    sc, sh = S._affine(co, None, None, dev)
+    o = torch.empty(n * h * w * co, device=dev)
+    d = _hip.ConvDesc()
+    d.inp, d.in_cs, d.N, d.H, d.W, d.Cin = v.ptr, v.cs, n, h, w, v.c
+    d.wgt, d.Cout, d.Cout_pad = wp.data_ptr(), co, cop
+    d.kh, d.kw, d.stride, d.pad, d.dil, d.Ho, d.Wo = 1, 1, 1, 0, 1, h, w
+    d.out, d.out_cs, d.scale, d.shift, d.sigmoid_from = o.data_ptr(), co, sc.data_ptr(), sh.data_ptr(), -1
+    t = [ctypes.c_int() for _ in range(4)]
+    _hip.check(L.m3d_conv2d_tile(ctypes.byref(d), *[ctypes.byref(c) for c in t]))
+    assert [c.value for c in t[:3]] == [128, 128, 32], [c.value for c in t]
+    _hip.check(L.m3d_conv2d_forward(ctypes.byref(d), S._stream()))
+    out["igemm"] = o.view(n, h, w, co).permute(0, 3, 1, 2).cpu()
+    assert G._relerr(out["igemm"], F.conv2d(x.double(), wt.double())) < 2e-4
+    # bf16: the wide wave-tile kernel (variant 5, WIDE_CASES[0]) and the persistent-grid 64 -> 64 kernel (variant 8, sized by the CU count)
+    for name, (n, ci, h, w, co), variant in (("wide", (1, 64, 8, 16, 128), 5), ("c64", (1, 64, 8, 32, 64), 8)):
+        x = torch.randn(n, ci, h, w, generator=g).to(BF16).float()
+        wt = (torch.randn(co, ci, 3, 3, generator=g) / (ci * 9) ** 0.5).to(BF16).float()
+        b = torch.randn(co, generator=g) * 0.1
+        out[name] = G._run_conv(x, wt, b, None, 1, 1, 0, None, 0, -1, 0, in_cs=ci + 8, variant=variant, wide=variant == 5)
+        bf16_close(out[name], F.conv2d(x.double(), wt.double(), b.double(), padding=1))
+    # top-k select + decode with k = 8192 (4096 is the largest k that needs no raise): test_topk_decode_matches_stable_sort
+    R, k, A = 16384, 8192, 36
+    scores = torch.rand(R, generator=g) ** 6
+    ins = [u.to(dev).contiguous() for u in G._topk_inputs(R, A, 3, scores)]
+    bits = G._sortable_bits(scores)
+    bits_dev = torch.from_numpy(bits.numpy().astype(np.uint32).view(np.int32)).to(dev)
+    ab, rows = torch.empty(1, k, 14, device=dev), torch.empty(1, k, device=dev, dtype=torch.int32)
+    nb = L.m3d_topk_decode_workspace_bytes(1, R)
+    ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+    _hip.check(L.m3d_topk_decode(bits_dev.data_ptr(), *[u.data_ptr() for u in ins], ab.data_ptr(), rows.data_ptr(), ws.data_ptr(),
+                                 nb, 1, R, k, G._stream()))
+    order = np.lexsort((np.arange(R), -bits.numpy().astype(np.int64)))[:k]
+    want = torch.empty(1, k, 14, device=dev)
+    rows64 = torch.from_numpy(order[None].astype(np.int64)).to(dev)
+    _hip.check(L.m3d_decode_rows(rows64.data_ptr(), *[u.data_ptr() for u in ins], want.data_ptr(), 1, R, k, G._stream()))
+    torch.cuda.synchronize()
+    assert np.array_equal(rows[0].cpu().numpy().astype(np.int64), order) and torch.equal(ab, want)
+    out["topk"] = ab.cpu()
+    return out
+
+
+n_dev = torch.cuda.device_count()
+res = {}
+for i in reversed(range(n_dev)):            # highest ordinal first, device 0 last: no launcher has run on a device before its turn
+    dev = torch.device("cuda", i)
+    torch.cuda.set_device(dev)
+    G._dev = lambda dev=dev: dev
+    res[i] = families(dev)
+for i in range(1, n_dev):
+    for name, t in res[0].items():
+        assert torch.equal(t, res[i][name]), (i, name)
+print(json.dumps({"FIRST_LAUNCH_OK": n_dev, "families": sorted(res[0])}))
+"""
+
+
+def test_first_launch_on_every_device(tmp_path):
+    """The launchers' once-per-device state (csrc/common.h: raised LDS limits, CU count, zero page) in a FRESH process: on every
+    visible device, highest ordinal first and device 0 last, the first call of each family that raises its dynamic-LDS limit (F(2x2)
+    Winograd, fused head MLP, the 128 x 128 x 32 implicit-GEMM tile, the bf16 wide tile, top-k with k = 8192) and of one
+    persistent-grid launcher (bf16 64 -> 64) meets that family's own tolerance against torch fp64, and every device gives the bits
+    of device 0.  With one visible device this is one iteration; the multi-device half needs torch.cuda.device_count() >= 2."""
+    script = tmp_path / "first_launch.py"
+    script.write_text(_FIRST_LAUNCH_SCRIPT % dict(root=ROOT, tests=os.path.join(ROOT, "tests")))
+    res = subprocess.run([sys.executable, str(script)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300,
+                         cwd=ROOT)
+    assert res.returncode == 0, res.stdout[-3000:]
+    got = json.loads(res.stdout.strip().splitlines()[-1])
+    assert got["FIRST_LAUNCH_OK"] == torch.cuda.device_count() >= 1
+    assert got["families"] == ["c64", "head_mlp", "igemm", "topk", "wide", "wino"]
+    _log("first_launch_on_every_device", {"devices": got["FIRST_LAUNCH_OK"]})
+
+
 def test_rccl_single_rank_collective_runs():
     """RCCL itself on the leased GPU: a 1-rank nccl process group runs the same all_gather_into_tensor the N > 1 path issues."""
     import subprocess
