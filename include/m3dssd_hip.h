@@ -83,7 +83,8 @@ const char *m3d_last_error(void);
  *                  m3d_conv_wave_forward_wgsplit, m3d_conv_wave_wgsplit_width (additive);
  *                  m3d_need_rows, m3d_need_rows_workspace_bytes, m3d_head_mlp_forward_rows, m3d_align_offsets_gated (additive);
  *                  m3d_dcn_v2_forward_bf16, m3d_dcn_v2_workspace_bytes_bf16, m3d_dcn_v2_backward_bf16,
- *                  m3d_dcn_v2_backward_workspace_bytes_bf16 (additive). */
+ *                  m3d_dcn_v2_backward_workspace_bytes_bf16 (additive);
+ *                  m3d_anab_attend_f32_rows (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -691,6 +692,14 @@ int m3d_anab_pool_nested_bf16_ex(const void *kv, int kv_cs, const float *s, int 
 int m3d_anab_attend_f32(const float *q, int q_cs, const float *khat, int k_cs, const float *vhatT, int B, int HW, int Ck,
                         int keys, int keys_pad, int Cv, const float *res, int res_cs, int res_mode, const float *scale,
                         const float *shift, int act, float *out, int out_cs, m3d_stream_t stream);
+/* Row-list form: the same attention at the *n_rows (device) pixels rows[j] = b * HW + pix only (ascending: what m3d_need_rows
+ * writes).  q, res and out are read / written at listed pixels and nowhere else, and there the output is bit-equal to the dense
+ * call's; khat / vhatT are the whole images' as above.  An image may list no pixel, and entries at or past *n_rows are never read.
+ * Nothing is read back: the grid is the dense one, and the workgroups past an image's part of the list return at once. */
+int m3d_anab_attend_f32_rows(const float *q, int q_cs, const float *khat, int k_cs, const float *vhatT, int B, int HW, int Ck,
+                             int keys, int keys_pad, int Cv, const float *res, int res_cs, int res_mode, const float *scale,
+                             const float *shift, int act, float *out, int out_cs, const int *rows, const int *n_rows,
+                             m3d_stream_t stream);
 /* In-place softmax over the first `valid` columns of each row; columns [valid, cs) are zeroed. */
 int m3d_softmax_rows(float *x, int rows, int valid, int cs, m3d_stream_t stream);
 

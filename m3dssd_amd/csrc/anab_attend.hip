@@ -36,19 +36,17 @@ struct AnabF32Args {
     int q_cs, k_cs, HW, Ck, keys, keys_pad, res_cs, out_cs, res_mode, act;
 };
 
-template <int CK, int NSPLIT = 1>      // key / query channels (multiple of 8); value-channel groups of AF_CV (grid.y)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void anab_attend_f32_kernel(const AnabF32Args a)
+// The body shared by the dense and the row-list launch: the workgroup's image, this lane's pixel (linear over the batch) and
+// whether the lane stores.  A lane that does not store still takes part in the staging and multiplies the pixel it was handed.
+template <int CK, int NSPLIT>          // key / query channels (multiple of 8); value-channel groups of AF_CV (grid.y)
+__device__ __forceinline__ void anab_attend_f32_body(const AnabF32Args &a, const int img, const int mq, const bool store)
 {
     constexpr int KROW = CK * 4 + 16;    // bytes per khat tile row in LDS (+16: rows of 8 neighbouring keys start in different banks)
     constexpr int NS4 = CK / 8;          // groups of four MFMA steps
     __shared__ __attribute__((aligned(16))) unsigned char lds[AF_KT * KROW + AF_CV * AF_VROW];
     unsigned char *Ks = lds, *Vs = lds + AF_KT * KROW;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
-    const int tiles_per_img = a.HW / 128;
-    const int img = blockIdx.x / tiles_per_img;
-    const int mq = blockIdx.x * 128 + wave * 32 + l31;            // this lane's pixel (linear over the batch)
 
     // ---- q: B operands of the QK steps, lane (pixel, h) holds k = 8t + 4h + {0..3} ---------------------------------------------------
     f32x4 qf[NS4];
@@ -182,13 +180,83 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 v = v * sc + sh;
             }
             v = __builtin_elementwise_max(v, v * slope);
-            *reinterpret_cast<f32x4 *>(op + c) = v;
+            if (store) *reinterpret_cast<f32x4 *>(op + c) = v;
         }
 }
 
-extern "C" int m3d_anab_attend_f32(const float *q, int q_cs, const float *khat, int k_cs, const float *vhatT, int B, int HW, int Ck,
-                                   int keys, int keys_pad, int Cv, const float *res, int res_cs, int res_mode, const float *scale,
-                                   const float *shift, int act, float *out, int out_cs, m3d_stream_t stream)
+template <int CK, int NSPLIT = 1>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void anab_attend_f32_kernel(const AnabF32Args a)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tiles_per_img = a.HW / 128;
+    const int img = blockIdx.x / tiles_per_img;
+    const int mq = blockIdx.x * 128 + wave * 32 + (threadIdx.x & 31);   // this lane's pixel (linear over the batch)
+    anab_attend_f32_body<CK, NSPLIT>(a, img, mq, true);
+}
+
+// ---- row-list form -------------------------------------------------------------------------------------------------------------------
+// The pixels are the *n_rows entries of rows[] (n * HW + pix, ascending: what m3d_need_rows writes).  The grid is the dense one and
+// a workgroup keeps its image: workgroup (img, tile) takes entries [128 tile, 128 tile + 128) of the image's run of the list, so a
+// workgroup stages one image's khat / vhat^T as the dense one does and no tile is walked twice; an image lists at most HW pixels,
+// so its HW / 128 workgroups cover its run, and the ones past it return before their first load of a feature.  A lane past the
+// run's end is handed the tile's first pixel and does not store.  Per pixel the arithmetic is the dense kernel's (the columns of
+// an MFMA are independent): the output is bit-equal at the listed pixels.
+// The workgroups are numbered TILE-major (blockIdx.x = tile * B + img), so the ones that have work come first and the dispatcher
+// hands each a compute unit of its own before the early-returning ones follow.  Image-major (the dense kernel's order) interleaves
+// every image's busy tiles with its empty ones, and busy workgroups end up two to a compute unit beside idle units: 121 us against
+// 74 us at 0.36 of 8 x 7 680 pixels listed (dense: 132 us; kernel trace of the benchmark, profiles/README.md).
+
+// First j in [0, n) with rows[j] >= target (n if none), the same value in every lane: a 64-ary search, one probe per lane and
+// level (3 dependent loads for 2^18 entries where a binary search takes 18).  No entry at or past n is read.  The probe indices stay
+// below n + 64: the host refuses n + 64 >= 2^31.
+__device__ __forceinline__ int af_lower_bound(const int *rows, const int n, const int target)
+{
+    const int lane = threadIdx.x & 63;
+    int lo = 0, len = n;                                        // the answer lies in [lo, lo + len]
+    while (len > 0) {
+        const int step = (len + 63) >> 6;
+        const int idx = lo + (lane + 1) * step - 1;
+        const bool less = idx < lo + len && rows[idx] < target;    // ascending list: true for the first c lanes
+        const int c = __popcll(__ballot(less));
+        const int end = lo + len;
+        lo += c * step;
+        len = min(step - 1, end - lo);
+    }
+    return __builtin_amdgcn_readfirstlane(lo);
+}
+
+template <int CK, int NSPLIT = 1>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void anab_attend_f32_rows_kernel(
+    const AnabF32Args a, const int *__restrict__ rows, const int *__restrict__ n_rows, const int cap)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tiles_per_img = a.HW / 128;
+    const int n_img = gridDim.x / tiles_per_img;
+    const int tile = blockIdx.x / n_img;                        // tile-major: see above
+    const int img = blockIdx.x - tile * n_img;
+    const int n = min(max(*n_rows, 0), cap);
+    if (128 * tile >= n) return;                                // (workgroup-uniform, like every return here)
+    const int e0 = af_lower_bound(rows, n, img * a.HW) + 128 * tile;      // the tile's first entry
+    if (e0 >= n) return;
+    const int img_end = (img + 1) * a.HW;
+    const int first = rows[e0];
+    if (first >= img_end) return;                               // the image's run ends in front of this tile
+    const int e = e0 + wave * 32 + (threadIdx.x & 31);
+    int mq = first;
+    bool store = false;
+    if (e < n) {
+        const int r = rows[e];
+        store = r < img_end;
+        mq = store ? r : first;
+    }
+    anab_attend_f32_body<CK, NSPLIT>(a, img, mq, store);
+}
+
+// rows == nullptr: the dense launch
+static int anab_attend_f32_launch(const float *q, int q_cs, const float *khat, int k_cs, const float *vhatT, int B, int HW, int Ck,
+                                  int keys, int keys_pad, int Cv, const float *res, int res_cs, int res_mode, const float *scale,
+                                  const float *shift, int act, float *out, int out_cs, const int *rows, const int *n_rows,
+                                  m3d_stream_t stream)
 {
     M3D_REQUIRE(q && khat && vhatT && out, "anab_attend_f32: null pointer");
     M3D_REQUIRE((Ck == 168 || Ck == 64 || Ck == 128) && (Cv == AF_CV || Cv == 2 * AF_CV),
@@ -200,20 +268,46 @@ extern "C" int m3d_anab_attend_f32(const float *q, int q_cs, const float *khat, 
     M3D_REQUIRE((((uintptr_t)q | (uintptr_t)khat | (uintptr_t)vhatT | (uintptr_t)out | (uintptr_t)res | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
                 "anab_attend_f32: 16-byte aligned views");
     M3D_REQUIRE((long long)B * HW < 0x7FFFFFFFLL, "anab_attend_f32: too many pixels");
+    M3D_REQUIRE(Cv == AF_CV || Ck == 168, "anab_attend_f32: Cv = %d is built for Ck = 168 (got %d)", 2 * AF_CV, Ck);
     AnabF32Args a;
     a.q = q; a.khat = khat; a.vhat = vhatT; a.res = res; a.scale = scale; a.shift = shift; a.out = out;
     a.q_cs = q_cs; a.k_cs = k_cs; a.HW = HW; a.Ck = Ck; a.keys = keys; a.keys_pad = keys_pad; a.res_cs = res_cs; a.out_cs = out_cs;
     a.res_mode = res_mode; a.act = act ? 1 : 0;
-    if (Cv == 2 * AF_CV) {                                     // two value-channel halves per pixel tile (see the top of the file)
-        M3D_REQUIRE(Ck == 168, "anab_attend_f32: Cv = %d is built for Ck = 168 (got %d)", 2 * AF_CV, Ck);
-        hipLaunchKernelGGL((anab_attend_f32_kernel<168, 2>), dim3(B * (HW / 128), 2), dim3(256), 0, (hipStream_t)stream, a);
-        M3D_LAUNCH_CHECK();
-        return M3D_OK;
+    // Cv = 256: two value-channel halves per pixel tile (see the top of the file)
+    const dim3 grid(B * (HW / 128), Cv / AF_CV);
+    const hipStream_t st = (hipStream_t)stream;
+    if (rows) {
+        const int cap = B * HW;
+        if (Cv == 2 * AF_CV) hipLaunchKernelGGL((anab_attend_f32_rows_kernel<168, 2>), grid, dim3(256), 0, st, a, rows, n_rows, cap);
+        else if (Ck == 168) hipLaunchKernelGGL(anab_attend_f32_rows_kernel<168>, grid, dim3(256), 0, st, a, rows, n_rows, cap);
+        else if (Ck == 128) hipLaunchKernelGGL(anab_attend_f32_rows_kernel<128>, grid, dim3(256), 0, st, a, rows, n_rows, cap);
+        else hipLaunchKernelGGL(anab_attend_f32_rows_kernel<64>, grid, dim3(256), 0, st, a, rows, n_rows, cap);
+    } else {
+        if (Cv == 2 * AF_CV) hipLaunchKernelGGL((anab_attend_f32_kernel<168, 2>), grid, dim3(256), 0, st, a);
+        else if (Ck == 168) hipLaunchKernelGGL(anab_attend_f32_kernel<168>, grid, dim3(256), 0, st, a);
+        else if (Ck == 128) hipLaunchKernelGGL(anab_attend_f32_kernel<128>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(anab_attend_f32_kernel<64>, grid, dim3(256), 0, st, a);
     }
-    const dim3 grid(B * (HW / 128));
-    if (Ck == 168) hipLaunchKernelGGL(anab_attend_f32_kernel<168>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else if (Ck == 128) hipLaunchKernelGGL(anab_attend_f32_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(anab_attend_f32_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
+}
+
+extern "C" int m3d_anab_attend_f32(const float *q, int q_cs, const float *khat, int k_cs, const float *vhatT, int B, int HW, int Ck,
+                                   int keys, int keys_pad, int Cv, const float *res, int res_cs, int res_mode, const float *scale,
+                                   const float *shift, int act, float *out, int out_cs, m3d_stream_t stream)
+{
+    return anab_attend_f32_launch(q, q_cs, khat, k_cs, vhatT, B, HW, Ck, keys, keys_pad, Cv, res, res_cs, res_mode, scale, shift, act,
+                                  out, out_cs, nullptr, nullptr, stream);
+}
+
+extern "C" int m3d_anab_attend_f32_rows(const float *q, int q_cs, const float *khat, int k_cs, const float *vhatT, int B, int HW, int Ck,
+                                        int keys, int keys_pad, int Cv, const float *res, int res_cs, int res_mode,
+                                        const float *scale, const float *shift, int act, float *out, int out_cs, const int *rows,
+                                        const int *n_rows, m3d_stream_t stream)
+{
+    M3D_REQUIRE(rows && n_rows, "anab_attend_f32_rows: null row list");
+    // (the list search probes entry indices up to n + 63 in 32-bit arithmetic)
+    M3D_REQUIRE((long long)B * HW < 0x7FFFFFFFLL - 64, "anab_attend_f32_rows: too many pixels");
+    return anab_attend_f32_launch(q, q_cs, khat, k_cs, vhatT, B, HW, Ck, keys, keys_pad, Cv, res, res_cs, res_mode, scale, shift, act,
+                                  out, out_cs, rows, n_rows, stream);
 }

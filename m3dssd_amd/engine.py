@@ -169,6 +169,9 @@ def pack_wino44_c16(weight, device):
 
 WINO_MIN_BLOCKS = int(os.environ.get("M3D_WINO_MIN_BLOCKS", "128"))
 FUSED_ANAB = os.environ.get("M3D_FUSED_ANAB", "1") != "0"       # logits + softmax + P.V of ANAB in one launch (csrc/anab_attend.hip)
+# detection-only tail: the one-launch attention at the listed pixels only (m3d_anab_attend_f32_rows); 0: the dense launch there too.
+# On by default: it met the step-time criterion ("The ANAB attention at the needed pixels").
+ANAB_ROWS = os.environ.get("M3D_ANAB_ROWS", "1") != "0"
 USE_ANAB_WAVE = os.environ.get("M3D_ANAB_WAVE", "1") != "0"
 USE_ANAB_NESTED = os.environ.get("M3D_ANAB_NESTED", "1") != "0"
 USE_DCN_WAVE = os.environ.get("M3D_DCN_WAVE", "1") != "0"
@@ -814,7 +817,8 @@ class Engine:
 
         # ---- ANAB ---------------------------------------------------------------------
         if with_anab:
-            gl = self._buf(plan, B, fh, fw, c3, name="feats_gl")
+            # zeroed: the tail's row-list attention writes it at the listed pixels only, and it is published in plan.named
+            gl = self._buf(plan, B, fh, fw, c3, name="feats_gl", zero=True)
             self._anab_ops(plan, f3d, gl, P["anab.bn.scale"], P["anab.bn.shift"], act=1, res_mode=1)
             head("bbox_z3d", gl, box_planar(6))
         else:
@@ -875,9 +879,15 @@ class Engine:
                     float(means[mi]), float(stds[mi]), float(means[mi + 1]), float(stds[mi + 1]), need.data_ptr(), om.ptr, om.cs,
                     B, A, HW, 11 * A * HW, st)), op[4])
 
+            # feats_gl feeds bbox_z3d and nothing else, and that head runs at the listed pixels: so does the attention behind the
+            # dense K | V | S projection and pooling (its queries, softmax, P.V and epilogue are per-pixel functions)
+            attend_rows = getattr(plan, "anab_attend", None) if ANAB_ROWS else None
+
             for op in plan.ops[t0:-1]:
                 if op[1] == "head_mlp<3,64>":
                     op = rows_op(op)
+                elif op[0] == "anab.attend" and attend_rows is not None:
+                    op = op[:3] + (attend_rows(L.m3d_anab_attend_f32_rows, rows.data_ptr(), n_rows.data_ptr()), op[4])
                 elif op[0] == "center_align2d.offsets":
                     op = gated_op(op, "center_align2d")
                 tail.append(op)
@@ -1009,9 +1019,15 @@ class Engine:
             rp, rcs = (x.ptr, x.cs) if x is not None else (None, 0)
             sp = scale.data_ptr() if scale is not None else None
             hp = shift.data_ptr() if shift is not None else None
-            self._op(plan, "anab.attend", "anab_attend", lambda st: _hip.check(L.m3d_anab_attend_f32(
-                qv.ptr, qv.cs, khat.data_ptr(), self.ck_pad, vhatT.data_ptr(), B, HW, self.ck, n_bins, keys_pad, self.cv, rp, rcs,
-                res_mode, sp, hp, 1 if act else 0, out.ptr, out.cs, st)), flops=2.0 * B * HW * n_bins * (self.ck + self.cv),
+
+            def attend(fn, *row_list):      # the launch through the dense entry point, or through the row-list one with its list
+                return lambda st: _hip.check(fn(
+                    qv.ptr, qv.cs, khat.data_ptr(), self.ck_pad, vhatT.data_ptr(), B, HW, self.ck, n_bins, keys_pad, self.cv, rp,
+                    rcs, res_mode, sp, hp, 1 if act else 0, out.ptr, out.cs, *row_list, st))
+
+            plan.anab_attend = attend       # (the detection-only tail builds its row-list form from it)
+            self._op(plan, "anab.attend", "anab_attend", attend(L.m3d_anab_attend_f32),
+                     flops=2.0 * B * HW * n_bins * (self.ck + self.cv),
                 nbytes=B * HW * (self.ck + 3 * self.cv) * 4 + B * keys_pad * (self.ck + self.cv) * 4)
             return
         logits = self._buf(plan, B, fh, fw, keys_pad)
