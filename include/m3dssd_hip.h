@@ -84,7 +84,8 @@ const char *m3d_last_error(void);
  *                  m3d_need_rows, m3d_need_rows_workspace_bytes, m3d_head_mlp_forward_rows, m3d_align_offsets_gated (additive);
  *                  m3d_dcn_v2_forward_bf16, m3d_dcn_v2_workspace_bytes_bf16, m3d_dcn_v2_backward_bf16,
  *                  m3d_dcn_v2_backward_workspace_bytes_bf16 (additive);
- *                  m3d_anab_attend_f32_rows (additive). */
+ *                  m3d_anab_attend_f32_rows (additive);
+ *                  m3d_head_mlp2_bf16_forward_rows, m3d_anab_attend_bf16_rows (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -333,6 +334,13 @@ typedef struct m3d_head2_bf16_desc {
     int groups;
 } m3d_head2_bf16_desc;
 int m3d_head_mlp2_bf16_forward(const m3d_head2_bf16_desc *d, m3d_stream_t stream);
+/* Row-list form: the same heads -- all d->groups of the launch -- evaluated only at the *n_rows (device) pixels rows[j] =
+ * img * HW + pix (ascending: what m3d_need_rows writes).  Tile t of the launch takes list entries [128 t, 128 t + 128), gathers
+ * their input rows and scatters its planar stores per entry, so a tile may straddle images.  At the listed pixels the outputs are
+ * bit-equal to m3d_head_mlp2_bf16_forward on the same descriptor; every other element of the output planes is left as it was.
+ * Nothing is read back on the host (the grid is the dense launch's), and entries at or past *n_rows are never read.  A NULL row
+ * list (rows or n_rows) is refused. */
+int m3d_head_mlp2_bf16_forward_rows(const m3d_head2_bf16_desc *d, const int *rows, const int *n_rows, m3d_stream_t stream);
 /* The two 1x1 layers behind the 3x3 convolution of the class head (M3d_inference_align.py:66-76: 256 -> 256 + affine + LeakyReLU,
  * 256 -> Cout <= 256 + affine) in one launch, same scheme: waf bf16 / wbf fp16 fragments [8 waves][16 K-steps][64 lanes][8] in the
  * layout of w2f above (scales folded, rows >= Cout of wbf zero), t1 / t2 fp32 [256] shifts (t2 past Cout ignored); input bf16
@@ -398,6 +406,13 @@ int m3d_frontend2_bf16_forward(const void *img, int is_u8, int img_h, int img_w,
 int m3d_anab_attend_bf16(const void *q, int q_cs, const void *khat, const void *vhatT, int B, int HW, int Ck_pad, int keys,
                          int keys_pad, int Cv, const void *res, int res_cs, const float *scale, const float *shift, int act,
                          void *out, int out_cs, m3d_stream_t stream);
+/* Row-list form, the contract of m3d_anab_attend_f32_rows: the same attention at the *n_rows (device) pixels rows[j] =
+ * b * HW + pix only (ascending: what m3d_need_rows writes).  q, res and out are read / written at the listed pixels and nowhere
+ * else, khat / vhatT are the whole images' as above, and the output is bit-equal to the dense call's there.  An image may list no
+ * pixel, and entries at or past *n_rows are never read.  Built for the one-pass kernel: refused under M3D_ANAB_ONLINE=0. */
+int m3d_anab_attend_bf16_rows(const void *q, int q_cs, const void *khat, const void *vhatT, int B, int HW, int Ck_pad, int keys,
+                              int keys_pad, int Cv, const void *res, int res_cs, const float *scale, const float *shift, int act,
+                              void *out, int out_cs, const int *rows, const int *n_rows, m3d_stream_t stream);
 int m3d_maxpool2x2_bf16(const void *in, int in_cs, void *out, int out_cs, int N, int H, int W, int C, m3d_stream_t stream);
 int m3d_upsample2x_add_bf16(const void *in, int in_cs, const float *wgt /*[4][4][C] fp32*/, const void *skip, int skip_cs,
                             void *out, int out_cs, int N, int H, int W, int C, m3d_stream_t stream);

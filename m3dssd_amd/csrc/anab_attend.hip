@@ -206,25 +206,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // every image's busy tiles with its empty ones, and busy workgroups end up two to a compute unit beside idle units: 121 us against
 // 74 us at 0.36 of 8 x 7 680 pixels listed (dense: 132 us; kernel trace of the benchmark, profiles/README.md).
 
-// First j in [0, n) with rows[j] >= target (n if none), the same value in every lane: a 64-ary search, one probe per lane and
-// level (3 dependent loads for 2^18 entries where a binary search takes 18).  No entry at or past n is read.  The probe indices stay
-// below n + 64: the host refuses n + 64 >= 2^31.
-__device__ __forceinline__ int af_lower_bound(const int *rows, const int n, const int target)
-{
-    const int lane = threadIdx.x & 63;
-    int lo = 0, len = n;                                        // the answer lies in [lo, lo + len]
-    while (len > 0) {
-        const int step = (len + 63) >> 6;
-        const int idx = lo + (lane + 1) * step - 1;
-        const bool less = idx < lo + len && rows[idx] < target;    // ascending list: true for the first c lanes
-        const int c = __popcll(__ballot(less));
-        const int end = lo + len;
-        lo += c * step;
-        len = min(step - 1, end - lo);
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
-
 template <int CK, int NSPLIT = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void anab_attend_f32_rows_kernel(
     const AnabF32Args a, const int *__restrict__ rows, const int *__restrict__ n_rows, const int cap)
@@ -236,7 +217,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int img = blockIdx.x - tile * n_img;
     const int n = min(max(*n_rows, 0), cap);
     if (128 * tile >= n) return;                                // (workgroup-uniform, like every return here)
-    const int e0 = af_lower_bound(rows, n, img * a.HW) + 128 * tile;      // the tile's first entry
+    const int e0 = rows_lower_bound(rows, n, img * a.HW) + 128 * tile;      // the tile's first entry
     if (e0 >= n) return;
     const int img_end = (img + 1) * a.HW;
     const int first = rows[e0];

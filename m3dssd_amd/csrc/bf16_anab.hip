@@ -41,19 +41,17 @@ struct AnabArgs {
 // accumulators are rescaled by exp(m_old - m_new) (64 multiplies per tile) -- instead of a pass for the maximum and a second one
 // that recomputes the logits; the next tile's khat / vhat pieces are in flight (registers) while the current tile is multiplied,
 // and the 12 logit MFMAs run as two independent chains (two workgroups per CU instead of three: 20 + 16 more registers).  22 -> 11 staged tiles per workgroup, 352 -> 220 MFMAs per wave.
+// The body shared by the dense and the row-list launch: the workgroup's image, this lane's pixel (linear over the batch) and
+// whether the lane stores.  A lane that does not store still takes part in the staging and multiplies the pixel it was handed;
+// it reads no residual.
 template <bool ONLINE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONLINE ? 2 : 3, ONLINE ? 2 : 3))) void bf16_anab_attend_kernel(const AnabArgs a)
+__device__ __forceinline__ void bf16_anab_attend_body(const AnabArgs &a, const int img, const int mq, const bool store)
 {
     __shared__ __attribute__((aligned(16))) unsigned char lds[32 * AN_KROW + AN_CV * AN_VROW];
     unsigned char *Ks = lds, *Vs = lds + 32 * AN_KROW;
 
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
-    const int tiles_per_img = a.HW / 128;
-    const int img = blockIdx.x / tiles_per_img;
-    const int m0 = blockIdx.x * 128;                       // first pixel (linear index) of the workgroup
-    const int mq = m0 + wave * 32 + l31;                   // this lane's pixel
 
     // ---- q fragments: B operand, lane (pixel, lh) holds channels 16s + 8*lh .. + 7 ----------------------------------------------
     bf16x8 qf[AN_CKP / 16];
@@ -248,13 +246,57 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONLINE ? 2 
     for (int j = 0; j < AN_CV / 32; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][0][r] = o[j][r] * inv;
-    const int mpix[1] = {mq};
+    const int mpix[1] = {store ? mq : -1};
     conv_epilogue<AN_CV / 32, 1>(a.ep, acc, mpix, 0, 0, lh, 0);
 }
 
-extern "C" int m3d_anab_attend_bf16(const void *q, int q_cs, const void *khat, const void *vhatT, int B, int HW, int Ck_pad, int keys,
-                                    int keys_pad, int Cv, const void *res, int res_cs, const float *scale, const float *shift, int act,
-                                    void *out, int out_cs, m3d_stream_t stream)
+template <bool ONLINE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONLINE ? 2 : 3, ONLINE ? 2 : 3))) void bf16_anab_attend_kernel(const AnabArgs a)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tiles_per_img = a.HW / 128;
+    const int img = blockIdx.x / tiles_per_img;
+    const int mq = blockIdx.x * 128 + wave * 32 + (threadIdx.x & 31);   // this lane's pixel (linear over the batch)
+    bf16_anab_attend_body<ONLINE>(a, img, mq, true);
+}
+
+// ---- row-list form: the arrangement of anab_attend_f32_rows_kernel (anab_attend.hip) ------------------------------------------------
+// The pixels are the *n_rows entries of rows[] (img * HW + pix, ascending: what m3d_need_rows writes).  The grid is the dense one and
+// a workgroup keeps its image: workgroup (img, tile) takes entries [128 tile, 128 tile + 128) of the image's run of the list, found
+// by a search over the list, so it stages one image's khat / vhat^T as the dense one does; the ones past the run return before their
+// first load of a feature.  A lane past the run's end is handed the tile's first pixel and does not store.  Per pixel the arithmetic
+// is the dense kernel's (the columns of an MFMA are independent): the output is bit-equal at the listed pixels.  The workgroups are
+// numbered TILE-major (blockIdx.x = tile * B + img), so that the ones that have work are dispatched first.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void bf16_anab_attend_rows_kernel(
+    const AnabArgs a, const int *__restrict__ rows, const int *__restrict__ n_rows, const int cap)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tiles_per_img = a.HW / 128;
+    const int n_img = gridDim.x / tiles_per_img;
+    const int tile = blockIdx.x / n_img;
+    const int img = blockIdx.x - tile * n_img;
+    const int n = min(max(*n_rows, 0), cap);
+    if (128 * tile >= n) return;                                // (workgroup-uniform, like every return here)
+    const int e0 = rows_lower_bound(rows, n, img * a.HW) + 128 * tile;    // the tile's first entry
+    if (e0 >= n) return;
+    const int img_end = (img + 1) * a.HW;
+    const int first = rows[e0];
+    if (first >= img_end) return;                               // the image's run ends in front of this tile
+    const int e = e0 + wave * 32 + (threadIdx.x & 31);
+    int mq = first;
+    bool store = false;
+    if (e < n) {
+        const int r = rows[e];
+        store = r < img_end;
+        mq = store ? r : first;
+    }
+    bf16_anab_attend_body<true>(a, img, mq, store);
+}
+
+// rows == nullptr: the dense launch
+static int anab_attend_bf16_launch(const void *q, int q_cs, const void *khat, const void *vhatT, int B, int HW, int Ck_pad, int keys,
+                                   int keys_pad, int Cv, const void *res, int res_cs, const float *scale, const float *shift, int act,
+                                   void *out, int out_cs, const int *rows, const int *n_rows, m3d_stream_t stream)
 {
     M3D_REQUIRE(q && khat && vhatT && out, "anab_attend_bf16: null pointer");
     M3D_REQUIRE(Ck_pad == AN_CKP && Cv == AN_CV, "anab_attend_bf16: built for Ck_pad = %d, Cv = %d (got %d, %d)", AN_CKP, AN_CV, Ck_pad, Cv);
@@ -269,8 +311,30 @@ extern "C" int m3d_anab_attend_bf16(const void *q, int q_cs, const void *khat, c
     a.ep.out = out; a.ep.out_cs = out_cs; a.ep.out_mode = 0; a.ep.Cout = Cv; a.ep.scale = scale; a.ep.shift = shift;
     a.ep.res = res; a.ep.res_cs = res_cs; a.ep.res_mode = 1; a.ep.act = act ? 1 : 0; a.ep.sigmoid_from = -1;
     static const int online = m3d_env_int("M3D_ANAB_ONLINE", 1);   // 0: the two-pass form (A/B)
-    if (online) hipLaunchKernelGGL(bf16_anab_attend_kernel<true>, dim3(B * (HW / 128)), dim3(256), 0, (hipStream_t)stream, a);
+    if (rows) {
+        M3D_REQUIRE(online, "anab_attend_bf16_rows: the row-list form is built for the one-pass kernel (M3D_ANAB_ONLINE=0 is set)");
+        hipLaunchKernelGGL(bf16_anab_attend_rows_kernel, dim3(B * (HW / 128)), dim3(256), 0, (hipStream_t)stream, a, rows, n_rows, B * HW);
+    } else if (online) hipLaunchKernelGGL(bf16_anab_attend_kernel<true>, dim3(B * (HW / 128)), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(bf16_anab_attend_kernel<false>, dim3(B * (HW / 128)), dim3(256), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
+}
+
+extern "C" int m3d_anab_attend_bf16(const void *q, int q_cs, const void *khat, const void *vhatT, int B, int HW, int Ck_pad, int keys,
+                                    int keys_pad, int Cv, const void *res, int res_cs, const float *scale, const float *shift, int act,
+                                    void *out, int out_cs, m3d_stream_t stream)
+{
+    return anab_attend_bf16_launch(q, q_cs, khat, vhatT, B, HW, Ck_pad, keys, keys_pad, Cv, res, res_cs, scale, shift, act, out, out_cs,
+                                   nullptr, nullptr, stream);
+}
+
+extern "C" int m3d_anab_attend_bf16_rows(const void *q, int q_cs, const void *khat, const void *vhatT, int B, int HW, int Ck_pad, int keys,
+                                         int keys_pad, int Cv, const void *res, int res_cs, const float *scale, const float *shift,
+                                         int act, void *out, int out_cs, const int *rows, const int *n_rows, m3d_stream_t stream)
+{
+    M3D_REQUIRE(rows && n_rows, "anab_attend_bf16_rows: null row list");
+    // (the list search probes entry indices up to n + 63 in 32-bit arithmetic)
+    M3D_REQUIRE((long long)B * HW < 0x7FFFFFFFLL - 64, "anab_attend_bf16_rows: too many pixels");
+    return anab_attend_bf16_launch(q, q_cs, khat, vhatT, B, HW, Ck_pad, keys, keys_pad, Cv, res, res_cs, scale, shift, act, out, out_cs,
+                                   rows, n_rows, stream);
 }

@@ -56,6 +56,7 @@ struct Head2Args {
 #define H2_W3 (32768 + 65536)       // [64 ch][256 k] fp16, 512-byte rows
 #define H2_SH (32768 + 65536 + 32768)   // t1 [256], t2 [256], t3 [64] fp32
 #define H2_LDS (H2_SH + 576 * 4)
+#define H2_PIX H2_LDS               // row-list form only: the tile's 128 list entries (img * HW + pix; -1 past the list)
 
 // byte offset of 16-byte chunk c of row r (rb = bytes per row, 256 or 512): chunks XOR-swizzled by the row inside each 256-byte half
 __device__ __forceinline__ int h2_off(int r, int c, int rb) { return r * rb + ((((c & 15) ^ (r & 15)) | (c & 16)) << 4); }
@@ -85,9 +86,23 @@ __device__ __forceinline__ unsigned h2_leaky_pack(float lo, float hi)
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(y, y * sl));
 }
 
-__global__ __launch_bounds__(512) void bf16_head2_kernel(const Head2Args a)
+// The body of the dense kernel (ROWS = false: bf16_head2_kernel, `rows` / `n_rows` unused) and of the row-list one
+// (bf16_head2_rows_kernel, m3d_head_mlp2_bf16_forward_rows).  ROWS: the pixels are the *n_rows entries of rows[] (img * HW + pix,
+// ascending: what m3d_need_rows writes) and tile t takes entries [128 t, 128 t + 128).  Its input rows are gathered when the tile is
+// fetched (one tile ahead: the dense prefetch), the tile's 128 list entries stay in LDS (H2_PIX, -1 past the list) and the
+// planar stores are scattered per entry, so a tile may straddle images.  Per pixel the arithmetic is the dense kernel's (the
+// columns of an MFMA are independent): the outputs are bit-equal at the listed pixels and nothing else is written.  The grid is
+// the dense one; a workgroup whose first tile lies past the list returns before it loads anything but the count.
+template <bool ROWS>
+__device__ __forceinline__ void bf16_head2_body(const Head2Args &a, const int *__restrict__ rows, const int *__restrict__ n_rows)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[H2_LDS];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[H2_LDS + (ROWS ? 128 * 4 : 0)];
+    int n_list = 0;
+    if constexpr (ROWS) {
+        n_list = min(max(*n_rows, 0), a.M);                    // (an entry at or past it is never read)
+        if ((int)blockIdx.x * 128 >= n_list) return;           // (workgroup-uniform)
+    }
+    const int tiles = ROWS ? (n_list + 127) >> 7 : a.tiles_m;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
@@ -129,9 +144,16 @@ __global__ __launch_bounds__(512) void bf16_head2_kernel(const Head2Args a)
     auto load_input = [&](int tile) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            const int m = tile * 128 + p * 32 + r0;
+            int m = tile * 128 + p * 32 + r0;
             vin[p] = u32x4{0u, 0u, 0u, 0u};
-            if (tile < a.tiles_m && m < a.M) vin[p] = *reinterpret_cast<const u32x4 *>((const __bf16 *)a.in + (size_t)m * a.in_cs + c16 * 8);
+            if constexpr (ROWS) {
+                if (m < n_list) {                                // (a tile past the list: every m >= n_list)
+                    m = rows[m];
+                    vin[p] = *reinterpret_cast<const u32x4 *>((const __bf16 *)a.in + (size_t)m * a.in_cs + c16 * 8);
+                }
+            } else {
+                if (tile < a.tiles_m && m < a.M) vin[p] = *reinterpret_cast<const u32x4 *>((const __bf16 *)a.in + (size_t)m * a.in_cs + c16 * 8);
+            }
         }
     };
     load_input(blockIdx.x);
@@ -207,12 +229,18 @@ __global__ __launch_bounds__(512) void bf16_head2_kernel(const Head2Args a)
     // Where things live during a tile (H = the 64 KB hidden region, rows of 512 bytes; IN = the 32 KB input region):
     //   h1: H rows 0-127.  h2 of pixels 0-63: IN (the input is dead behind barrier B), of pixels 64-127: H rows 0-63 (h1 rows every
     //   wave has read when it passes barrier C).  Output transposition: H rows 64-127 (dead behind barrier D), 4 KB per wave.
-    for (int tile = blockIdx.x; tile < a.tiles_m; tile += gridDim.x, ++iter) {
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x, ++iter) {
         const int m0 = tile * 128;
         H2TRACE();
         // ---- input tile -> LDS (swizzled), next tile's input in flight ---------------------------------------------------------
 #pragma unroll
         for (int p = 0; p < 4; ++p) *reinterpret_cast<u32x4 *>(lds + H2_IN + h2_off(p * 32 + r0, c16, 256)) = vin[p];
+        if constexpr (ROWS) {
+            // the tile's list entries (the gather read them one tile ago: a cache hit, and the wait is the one the next tile's gather
+            // has anyway); read behind barrier D, rewritten behind E.  (Kept in a register from the prefetch on, they would be one more
+            // live value across the whole tile in a kernel that stands at its 256 registers.)
+            if (tid < 128) reinterpret_cast<int *>(lds + H2_PIX)[tid] = m0 + tid < n_list ? rows[m0 + tid] : -1;
+        }
         load_input(tile + gridDim.x);
         __syncthreads();                                        // A: input tile (and, first time, W3 / shifts) complete
         H2TRACE();
@@ -276,7 +304,21 @@ __global__ __launch_bounds__(512) void bf16_head2_kernel(const Head2Args a)
         __builtin_amdgcn_s_waitcnt(0xc07f);                     // lgkmcnt(0): the wave's own LDS writes (no other wave reads them)
         __builtin_amdgcn_wave_barrier();
         const int mq = m0 + 32 * cb3;                           // first pixel of this wave's block
-        if (a.HW % 32 == 0 && mq + 32 <= a.M) {
+        if constexpr (ROWS) {
+            // lane = (entry l31 of the block, channel parity lh): the entry's image and pixel once, then its 16 channel rows
+            const int m = reinterpret_cast<const int *>(lds + H2_PIX)[32 * cb3 + l31];
+            if (m >= 0) {
+                const int img = m / a.HW, pp = m - img * a.HW;
+                // (a running pointer with a uniform step: sixteen per-lane channel offsets are loop invariants that the compiler
+                // hoists out of the tile loop, into registers this kernel does not have)
+                float *ob = a.out + g * a.out_goff + (size_t)img * a.out_img_stride + (size_t)(32 * rb + lh) * a.HW + pp;
+#pragma unroll
+                for (int k = 0; k < 16; ++k, ob += 2 * a.HW) {
+                    const int c = 2 * k + lh;
+                    if (32 * rb + c < a.Cout) *ob = ot[c * 32 + l31];
+                }
+            }
+        } else if (a.HW % 32 == 0 && mq + 32 <= a.M) {
             const int img = mq / a.HW, p0 = mq - img * a.HW;
             float *ob = a.out + g * a.out_goff + (size_t)img * a.out_img_stride + p0;
 #pragma unroll
@@ -298,6 +340,13 @@ __global__ __launch_bounds__(512) void bf16_head2_kernel(const Head2Args a)
         __syncthreads();                                        // E: the input region (h2 of pixels 0-63) and the hidden region are free
         H2TRACE();
     }
+}
+
+__global__ __launch_bounds__(512) void bf16_head2_kernel(const Head2Args a) { bf16_head2_body<false>(a, nullptr, nullptr); }
+
+__global__ __launch_bounds__(512) void bf16_head2_rows_kernel(const Head2Args a, const int *__restrict__ rows, const int *__restrict__ n_rows)
+{
+    bf16_head2_body<true>(a, rows, n_rows);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -610,7 +659,8 @@ extern "C" int m3d_anab_qkvs_bf16_forward(const m3d_qkvs_bf16_desc *d, m3d_strea
     return M3D_OK;
 }
 
-extern "C" int m3d_head_mlp2_bf16_forward(const m3d_head2_bf16_desc *d, m3d_stream_t stream)
+// rows == nullptr: the dense launch
+static int head_mlp2_bf16_launch(const m3d_head2_bf16_desc *d, const int *rows, const int *n_rows, m3d_stream_t stream)
 {
     M3D_REQUIRE(d && d->in && d->w1f && d->w2f && d->w3 && d->out && d->t1 && d->t2 && d->t3, "head_mlp2_bf16: null pointer");
     M3D_REQUIRE(d->in_cs % 8 == 0 && d->in_cs >= 128 && ((uintptr_t)d->in & 15) == 0, "head_mlp2_bf16: 128 input channels, 16-byte aligned rows");
@@ -626,10 +676,23 @@ extern "C" int m3d_head_mlp2_bf16_forward(const m3d_head2_bf16_desc *d, m3d_stre
 #endif
     // one workgroup per CU (130 KB of LDS, 512 threads): the CUs are split between the heads of the launch, every workgroup walks tiles
     const int ncu = m3d_cu_count();
-    static const int scratch = m3d_scratch_bytes(&bf16_head2_kernel);          // resident weights in registers: a spilled build would re-read them from scratch memory per tile
+    static const int scratch = m3d_scratch_bytes(&bf16_head2_kernel, &bf16_head2_rows_kernel);   // resident weights in registers: a spilled build would re-read them from scratch memory per tile
     M3D_REQUIRE(scratch == 0, "head_mlp2_bf16: the kernel was built with register spills (%d bytes of scratch)", scratch);
+    // (the row-list form keeps the dense grid: the length of the list is known on the device only)
     const int nb = std::max(1, std::min(a.tiles_m, ncu / d->groups));
-    hipLaunchKernelGGL(bf16_head2_kernel, dim3(nb, d->groups), dim3(512), 0, (hipStream_t)stream, a);
+    if (rows) hipLaunchKernelGGL(bf16_head2_rows_kernel, dim3(nb, d->groups), dim3(512), 0, (hipStream_t)stream, a, rows, n_rows);
+    else hipLaunchKernelGGL(bf16_head2_kernel, dim3(nb, d->groups), dim3(512), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
+}
+
+extern "C" int m3d_head_mlp2_bf16_forward(const m3d_head2_bf16_desc *d, m3d_stream_t stream)
+{
+    return head_mlp2_bf16_launch(d, nullptr, nullptr, stream);
+}
+
+extern "C" int m3d_head_mlp2_bf16_forward_rows(const m3d_head2_bf16_desc *d, const int *rows, const int *n_rows, m3d_stream_t stream)
+{
+    M3D_REQUIRE(rows && n_rows, "head_mlp2_bf16_rows: null row list");
+    return head_mlp2_bf16_launch(d, rows, n_rows, stream);
 }

@@ -243,6 +243,26 @@ __device__ __forceinline__ unsigned int f32_sortable(float f)
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// Search in an ascending row list (m3d_need_rows), shared by the row-list attention kernels (anab_attend.hip, bf16_anab.hip):
+// first j in [0, n) with rows[j] >= target (n if none), the same value in every lane: a 64-ary search, one probe per lane and
+// level (3 dependent loads for 2^18 entries where a binary search takes 18).  No entry at or past n is read.  The probe indices stay
+// below n + 64: the host refuses n + 64 >= 2^31.
+__device__ __forceinline__ int rows_lower_bound(const int *rows, const int n, const int target)
+{
+    const int lane = threadIdx.x & 63;
+    int lo = 0, len = n;                                        // the answer lies in [lo, lo + len]
+    while (len > 0) {
+        const int step = (len + 63) >> 6;
+        const int idx = lo + (lane + 1) * step - 1;
+        const bool less = idx < lo + len && rows[idx] < target;    // ascending list: true for the first c lanes
+        const int c = __popcll(__ballot(less));
+        const int end = lo + len;
+        lo += c * step;
+        len = min(step - 1, end - lo);
+    }
+    return __builtin_amdgcn_readfirstlane(lo);
+}
+
 // ---- deterministic split-K reduction shared by the LDS-tiled and the wave-granular implicit GEMMs (igemm_conv.hip) -----------
 // ws holds `splits` raw partial sums [split][M][Cout_pad]; they are added in split order and the conv epilogue is applied.
 struct SplitkReduceArgs {

@@ -1153,14 +1153,16 @@ class Engine:
         """Issue plan.ops[start:end] on the ENGINE device's current stream (the whole forward by default); the engine's
         device is made current for the launches, whatever the caller's current device is.
         tail=True: the detection-only form -- plan.ops[start:plan.tail_start], then plan.tail in place of everything behind it up
-        to bundle_outputs (`end` must be the index of bundle_outputs).  The box staging is then written at the needed pixels only:
+        to bundle_outputs (`end` must be the index of bundle_outputs), all on the current stream: side branches are not forked in
+        this form.  The box staging is then written at the needed pixels only:
         what follows may be the planar top-k decode, not bundle_outputs.  plan.named["sparse_k"][0] is the k of that decode."""
         with torch.cuda.device(self.device):
             if not tail:
                 return self._run_plan(plan, start, end)
             if getattr(plan, "tail", None) is None:
                 raise RuntimeError("run_plan(tail=True): this plan has no detection-only tail")
-            if end != len(plan.ops) - 1 or not 0 <= start <= plan.tail_start or plan.branches:
+            # (a plan with side branches -- the bf16 one, ANAB beside the size heads -- is issued in line here, on one stream)
+            if end != len(plan.ops) - 1 or not 0 <= start <= plan.tail_start:
                 raise RuntimeError("run_plan(tail=True): ops [%r, %r) do not end in front of bundle_outputs (op %d) behind a start "
                                    "in [0, %d]" % (start, end, len(plan.ops) - 1, plan.tail_start))
             self._run_plan(plan, start, end, plan.ops[start:plan.tail_start] + plan.tail)

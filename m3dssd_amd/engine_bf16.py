@@ -34,6 +34,14 @@ BRANCH = os.environ.get("M3D_BF16_BRANCH", "1") != "0"         # ANAB + z3d head
 TREE_ENTRY = os.environ.get("M3D_BF16_TREE_ENTRY", "1") != "0"   # max-pool + project + stride-2 conv1 of a tree in one launch (csrc/bf16_tree_entry.hip)
 HEADS2 = os.environ.get("M3D_BF16_HEADS2", "1") != "0"         # round-5 form of the fused heads (csrc/bf16_head_mlp2.hip)
 SHAPE_PATCH = os.environ.get("M3D_BF16_SHAPE_PATCH", "0") != "0"   # shape_align through the LDS-patch DCNv2 kernel (per-tile decision)
+# Detection-only tail of the bf16 plan (plan.tail: the bf16_head2 launches and the one-launch attention at the needed pixels only;
+# DESIGN.md section 3, "Needed pixels").  SPARSE_TAIL = False builds the plan without it (tests compare plan.ops with and without).
+SPARSE_TAIL = True
+# the tail's attention through m3d_anab_attend_bf16_rows; 0: the dense launch there too
+ANAB_ROWS = os.environ.get("M3D_BF16_ANAB_ROWS", "1") != "0"
+# what a detector's sparse_heads=None means on a bf16 module: "1" takes the tail wherever the plan has one, "0" never does; unset:
+# the plan-time rule of the fp32 engine (EngineBF16.sparse_heads_default)
+SPARSE_HEADS = os.environ.get("M3D_BF16_SPARSE_HEADS")
 
 
 
@@ -635,7 +643,8 @@ class EngineBF16(Engine):
         def anab_z3d(x):
             """ANAB + the z3d head behind it (reads x = feats_align3d, writes its own planar rows); returns its first op."""
             b0 = len(plan.ops)
-            gl = self._buf16(plan, B, fh, fw, 128, name="feats_gl")
+            # zeroed: the tail's row-list attention writes it at the listed pixels only, and it is published in plan.named
+            gl = self._buf16(plan, B, fh, fw, 128, name="feats_gl", zero=True)
             self._anab_bf16(plan, x, gl)
             heads(["bbox_z3d"], gl, 6)
             return b0
@@ -705,12 +714,14 @@ class EngineBF16(Engine):
         else:
             feats = plan.named["feats"] = feats0
 
+        align_args = {}                  # p -> what a gated form of p's offsets launch needs (detection-only tail)
         if with_center:
             heads(["bbox_x", "bbox_y"], feats, 0)
             heads(["bbox_x3d", "bbox_y3d"], feats, 4)
 
             def center_align(p, x, kx, ky, mi, out):
                 om = self._buf16(plan, B, fh, fw, 3, 4, dtype=torch.float32)
+                align_args[p] = (om, kx, ky, mi)
                 self._op(plan, p + ".offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
                     1, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, None, box_ptr(kx), box_ptr(ky),
                     P["anchor_wh"].data_ptr(), float(means[mi]), float(stds[mi]), float(means[mi + 1]),
@@ -761,7 +772,65 @@ class EngineBF16(Engine):
         self._op(plan, "bundle_outputs", "bundle", lambda st: _hip.check(L.m3d_bundle_outputs(
             cls_pl.data_ptr(), box_pl.data_ptr(), dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), dst[3].data_ptr(),
             key.data_ptr(), B, A, HW, st)), nbytes=B * R * (NC + 11 + 2 * NC + 4 + 7 + 1) * 4)
+
+        # ---- detection-only tail ------------------------------------------------------
+        # The fp32 plan's argument (Engine._build_plan) carries over: the top-k decode reads the box staging at the nms_topN_pre best
+        # rows of an image, the score is a function of the class head alone, row a * HW + pix belongs to pixel pix, and every box head
+        # and the 1x1 centre alignments are per-pixel functions.  What the selection reads and writes is fp32 / integer here too, so
+        # m3d_need_rows and m3d_align_offsets_gated serve as they are.  A launch of this plan is wholly sparse or wholly dense:
+        # bbox_x3d + bbox_y3d have a launch of their own, and with the centre alignments they feed feats_align3d, which ANAB pools
+        # over the whole map.  Ops in front of anchor_select (ANAB + z3d of the ANAB-only configuration) stay dense, and so do heads
+        # that do not run as bf16_head2.  Issued on one stream (Engine.run_plan(tail=True)): the side branch is time-neutral here.
+        if SPARSE_TAIL and plan.named.get("keys_by_select"):
+            t0 = plan.named["score_bits_first_write_op"] + 1
+            # zeroed: the dense forward (plan.ops) never writes them, and the list is written up to n_rows only -- they are
+            # published in plan.named and must not show what the allocation held (uninitialised memory)
+            need = torch.zeros(B * HW, device=self.device, dtype=torch.uint8)
+            rows = torch.zeros(B * HW, device=self.device, dtype=torch.int32)
+            n_rows = torch.zeros(1, device=self.device, dtype=torch.int32)
+            thresh = torch.zeros(B, device=self.device, dtype=torch.int32)
+            nb = L.m3d_need_rows_workspace_bytes(B, HW)
+            ws = torch.empty(nb, device=self.device, dtype=torch.uint8)
+            plan.keep += [need, rows, n_rows, thresh, ws]
+            plan.named.update(need=need, need_rows=rows, n_rows=n_rows, need_thresh=thresh)
+            k_pre = plan.named["sparse_k"] = [min(int(self.conf.nms_topN_pre), R)]      # set by the caller at launch time
+            tail = [("need_rows", "select", 0.0, lambda st: _hip.check(L.m3d_need_rows(
+                key.data_ptr(), B, A, HW, int(k_pre[0]), thresh.data_ptr(), need.data_ptr(), rows.data_ptr(), n_rows.data_ptr(),
+                ws.data_ptr(), nb, st)), OpCost(B * R * 4 * 4))]
+
+            def rows_op(op):
+                ref = ctypes.byref(op[4])
+                return op[:3] + (lambda st: _hip.check(L.m3d_head_mlp2_bf16_forward_rows(
+                    ref, rows.data_ptr(), n_rows.data_ptr(), st)), op[4])
+
+            def gated_op(op, p):
+                om, kx, ky, mi = align_args[p]
+                return op[:3] + (lambda st: _hip.check(L.m3d_align_offsets_gated(
+                    sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, box_ptr(kx), box_ptr(ky), P["anchor_wh"].data_ptr(),
+                    float(means[mi]), float(stds[mi]), float(means[mi + 1]), float(stds[mi + 1]), need.data_ptr(), om.ptr, om.cs,
+                    B, A, HW, 11 * A * HW, st)), op[4])
+
+            # feats_gl feeds bbox_z3d and nothing else, and that head runs at the listed pixels: so does the attention behind the
+            # dense Q | K | V | S projection and pooling
+            attend_rows = getattr(plan, "anab_attend", None) if ANAB_ROWS else None
+            for op in plan.ops[t0:-1]:
+                if op[1] == "bf16_head2" and not (with_center and op[0] == "bbox_x3d+bbox_y3d.mlp"):
+                    op = rows_op(op)
+                elif op[0] == "anab.attend" and attend_rows is not None:
+                    op = op[:3] + (attend_rows(L.m3d_anab_attend_bf16_rows, rows.data_ptr(), n_rows.data_ptr()), op[4])
+                elif op[0] == "center_align2d.offsets":
+                    op = gated_op(op, "center_align2d")
+                tail.append(op)
+            plan.tail, plan.tail_start = tail, t0
         return plan
+
+    def sparse_heads_default(self, plan, k):
+        """The plan-time rule of a detector's sparse_heads=None on a bf16 module: the fp32 rule (min(k, HW) at most
+        SPARSE_HEADS_MAX_FRACTION of HW) -- the tail met the step-time criterion on bf16 too ("Needed pixels on
+        the bf16 engine").  M3D_BF16_SPARSE_HEADS=0 is the way back to dense; =1 takes the tail wherever the plan has one."""
+        if SPARSE_HEADS is not None:
+            return SPARSE_HEADS != "0" and getattr(plan, "tail", None) is not None
+        return super().sparse_heads_default(plan, k)
 
     def _anab_bf16(self, plan, x, out):
         """ANAB (attention.py:183-216) + the BN / LeakyReLU that follows it: Q as bf16, K|V|S in fp32 for the gated pyramid
@@ -858,9 +927,14 @@ class EngineBF16(Engine):
             # logits + softmax + P.V in one launch: the fp32 logits / bf16 probabilities (1.1 GB at bs = 64) never reach HBM
             sc, sh = P["anab.bn.scale"], P["anab.bn.shift"]
             plan.keep += [sc, sh]
-            self._op(plan, "anab.attend", "bf16_anab", lambda st: _hip.check(L.m3d_anab_attend_bf16(
-                q.ptr, q.cs, khat16.data_ptr(), vhat16.data_ptr(), B, HW, ck_pad, n_bins, keys_pad, cv, x.ptr, x.cs,
-                sc.data_ptr(), sh.data_ptr(), 1, out.ptr, out.cs, st)))
+
+            def attend(fn, *row_list):      # the launch through the dense entry point, or through the row-list one with its list
+                return lambda st: _hip.check(fn(
+                    q.ptr, q.cs, khat16.data_ptr(), vhat16.data_ptr(), B, HW, ck_pad, n_bins, keys_pad, cv, x.ptr, x.cs,
+                    sc.data_ptr(), sh.data_ptr(), 1, out.ptr, out.cs, *row_list, st))
+
+            plan.anab_attend = attend       # (the detection-only tail builds its row-list form from it)
+            self._op(plan, "anab.attend", "bf16_anab", attend(L.m3d_anab_attend_bf16))
             plan.ops[-1] = plan.ops[-1][:2] + (2.0 * B * HW * n_bins * (ck + cv),) + plan.ops[-1][3:]
             return
         logits = self._buf16(plan, B, fh, fw, n_bins, keys_pad, dtype=torch.float32)

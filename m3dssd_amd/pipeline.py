@@ -73,8 +73,9 @@ class _Detector:
             self.input = self.inputs_u8[0]
         assert self.plan.ops[-1][0] == "bundle_outputs"
         self.n_fwd = len(self.plan.ops) - 1                 # planar form: everything in front of the output bundling
-        # box heads at the needed pixels only (the plan's detection-only tail): None = the engine's plan-time rule; the bundled
-        # form and a plan without a tail (bf16) stay dense whatever is asked
+        # box heads at the needed pixels only (the plan's detection-only tail): None = the engine's plan-time rule (by
+        # nms_topN_pre; bf16: M3D_BF16_SPARSE_HEADS=0 / 1 overrides it); the bundled form and a plan without a tail stay dense
+        # whatever is asked
         if sparse_heads is None:
             sparse_heads = self.eng.sparse_heads_default(self.plan, conf.nms_topN_pre)
         self.sparse_heads = bool(sparse_heads) and bool(planar) and getattr(self.plan, "tail", None) is not None
