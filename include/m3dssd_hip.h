@@ -85,7 +85,9 @@ const char *m3d_last_error(void);
  *                  m3d_dcn_v2_forward_bf16, m3d_dcn_v2_workspace_bytes_bf16, m3d_dcn_v2_backward_bf16,
  *                  m3d_dcn_v2_backward_workspace_bytes_bf16 (additive);
  *                  m3d_anab_attend_f32_rows (additive);
- *                  m3d_head_mlp2_bf16_forward_rows, m3d_anab_attend_bf16_rows (additive). */
+ *                  m3d_head_mlp2_bf16_forward_rows, m3d_anab_attend_bf16_rows (additive);
+ *                  m3d_dcn_v2_psroi_pooling_forward, m3d_dcn_v2_psroi_pooling_backward,
+ *                  m3d_dcn_v2_psroi_pooling_workspace_bytes (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -526,6 +528,59 @@ int m3d_dcn_v2_backward_bf16(const void *input, const void *weight, const void *
                              int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
                              int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
                              int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Deformable position-sensitive RoI pooling (csrc/psroi_pool.hip): the drop-ins for dcn_v2_psroi_pooling_cuda_forward /
+ * _backward, the operator behind DCNv2PoolingFunction (model/DCNv2/dcn_v2_func.py:76-146).  fp32 contiguous device tensors:
+ *   data  [batch, channels, height, width];  rois [num_rois, 5] = (batch index, x1, y1, x2, y2) in image pixels;
+ *   trans [trans_rows >= num_rois, 2 * num_classes, part_size, part_size], ignored (may be NULL) when no_trans;
+ *   out, top_count [num_rois, output_dim, pooled_size, pooled_size]; top_count may be NULL.
+ * With P = pooled_size, S = sample_per_part, G = group_size, D = output_dim: K = 1 when no_trans, else num_classes;
+ * channels_each_class = D / K.  For output (i, c, ph, pw) every value below is fp32 and every operation is rounded once, in
+ * this order, with no fused multiply-add:
+ *   rs_w = roundf(x1) * spatial_scale - 0.5 (roundf: halves away from zero), re_w = (roundf(x2) + 1) * spatial_scale - 0.5,
+ *   rs_h / re_h likewise from y1 / y2;  roi_w = max(re_w - rs_w, 0.1), roi_h likewise;
+ *   bin_w = roi_w / P, sub_w = bin_w / S (IEEE divisions), the same for h;
+ *   part_w = floorf((float)pw / P * part_size), part_h = floorf((float)ph / P * part_size)   (float32, not (pw * part) / P);
+ *   gw = clamp(floorf((float)pw * G / P), 0, G - 1), gh likewise;  class = c / channels_each_class;
+ *   tx = trans[i, 2 * class, part_h, part_w] * trans_std, ty = trans[i, 2 * class + 1, part_h, part_w] * trans_std (0 if no_trans);
+ *   wstart = (pw * bin_w + rs_w) + tx * roi_w, hstart = (ph * bin_h + rs_h) + ty * roi_h;
+ *   sample (ih, iw), 0 <= ih, iw < S: w = wstart + iw * sub_w, h = hstart + ih * sub_h;  input channel (c * G + gh) * G + gw.
+ * A sample counts iff both coordinates are finite, -0.5 <= w <= width - 0.5 and -0.5 <= h <= height - 0.5.  A counted sample is
+ * clamped to [0, width - 1] x [0, height - 1] and read bilinearly between floor and ceil of each coordinate with weight
+ * w - floor(w) on the ceil side (at an integer coordinate both corners coincide).  top_count = the number of counted samples;
+ * out = their sum divided by top_count (one fp32 division), 0 when top_count is 0.
+ * Backward, given grad_out: grad_data receives, per counted sample, grad_out / count times the four corner weights at the four
+ * corners; grad_trans[i, 2 * class (+1), part_h, part_w] receives, per counted sample, trans_std * roi_w * grad_out / count *
+ * d val / d w (the y element: roi_h and d / d h), the bilinear slope between the floor and ceil columns, 0 at an integer or clamped
+ * coordinate.  The count is recomputed, not taken from the caller.  rois get no gradient; rows of trans past num_rois get zeros.
+ * Where this library is stricter than the reference (which dereferences without looking):
+ *   - a region whose batch index is not an integer in [0, batch), or with a non-finite corner, gives zeros, count 0 and no
+ *     gradient; nothing is read or written for it beyond its own output rows;
+ *   - channels < D * G * G, D not divisible by K, trans_rows < num_rois, P / S / G / part_size < 1 and trans_std outside [0, 1]
+ *     are M3D_E_ARG; no input can make a kernel address memory outside its tensors;
+ *   - every non-NULL gradient is OVERWRITTEN (the reference adds into tensors its caller has zeroed); a NULL gradient pointer =
+ *     not wanted, and the work only it needs is skipped; with no_trans grad_trans is ignored;
+ *   - grad_trans is bitwise reproducible from run to run (butterfly over the lanes, then a fixed order over the bins of a part
+ *     cell; no atomics); grad_data is summed with float atomics, as in the reference, and may differ in its last bits.
+ * The workspace (256-byte aligned) holds a pixel-major copy of the first D * G * G channels of data and, for the backward
+ * (`backward` != 0 in the query), the fp32 staging buffer of grad_data and the per-wave partials of grad_trans; no result
+ * depends on what it held.  The query returns -1 for invalid sizes; num_classes = 1 for no_trans.  M3D_E_WORKSPACE carries both
+ * sizes.  num_rois = 0 returns M3D_OK without a kernel launch (the backward then zero-fills the gradients asked for).
+ * ------------------------------------------------------------------------------------------ */
+long long m3d_dcn_v2_psroi_pooling_workspace_bytes(int batch, int channels, int height, int width, int num_rois,
+                                                   int num_classes, int output_dim, int group_size, int pooled_size,
+                                                   int backward);
+int m3d_dcn_v2_psroi_pooling_forward(const float *data, const float *rois, const float *trans, float *out, float *top_count,
+                                     int batch, int channels, int height, int width, int num_rois, int trans_rows,
+                                     int num_classes, int no_trans, float spatial_scale, int output_dim, int group_size,
+                                     int pooled_size, int part_size, int sample_per_part, float trans_std, void *workspace,
+                                     long long workspace_bytes, m3d_stream_t stream);
+int m3d_dcn_v2_psroi_pooling_backward(const float *grad_out, const float *data, const float *rois, const float *trans,
+                                      float *grad_data, float *grad_trans, int batch, int channels, int height, int width,
+                                      int num_rois, int trans_rows, int num_classes, int no_trans, float spatial_scale,
+                                      int output_dim, int group_size, int pooled_size, int part_size, int sample_per_part,
+                                      float trans_std, void *workspace, long long workspace_bytes, m3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * RPN_3D_loss on the device (csrc/rpn_loss.hip): target assignment, hard-negative sampling, fused loss + gradients.

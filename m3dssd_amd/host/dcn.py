@@ -1,5 +1,6 @@
 """DCNv2 / DCN modules with the reference's interface (model/DCNv2/dcn_v2.py:14-70,
-model/DCNv2/dcn_v2_func.py:13-38), backed by m3d_dcn_v2_forward."""
+model/DCNv2/dcn_v2_func.py:13-38), backed by m3d_dcn_v2_forward, and the pooling half of the same two files (dcn_v2.py:73-171,
+dcn_v2_func.py:76-146), backed by m3d_dcn_v2_psroi_pooling_forward / _backward."""
 import math
 
 import torch
@@ -80,3 +81,84 @@ class DCN(DCNv2):
                               self.deformable_groups)
         from .standalone import dcn_layer_forward
         return dcn_layer_forward(self, input)
+
+
+class DCNv2PoolingFunction:
+    """Callable with the reference's legacy instance-style convention (dcn_v2_func.py:76-146):
+    ``DCNv2PoolingFunction(spatial_scale, pooled_size, output_dim, no_trans, ...)(data, rois, offset)``.  Differentiable in ``data``
+    and ``offset`` through ``ops.psroi_pooling``; ``rois`` get no gradient.  ``offset`` is not looked at when ``no_trans`` (the
+    modules pass ``data.new()`` there)."""
+
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4, trans_std=.0):
+        self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans = spatial_scale, pooled_size, output_dim, no_trans
+        self.group_size = group_size
+        self.part_size = pooled_size if part_size is None else part_size
+        self.sample_per_part, self.trans_std = sample_per_part, trans_std
+        assert self.trans_std >= 0.0 and self.trans_std <= 1.0
+
+    def __call__(self, data, rois, offset):
+        return self.forward(data, rois, offset)
+
+    def _conf(self):
+        return (self.no_trans, self.spatial_scale, self.output_dim, self.group_size, self.pooled_size, self.part_size,
+                self.sample_per_part, self.trans_std)
+
+    def forward(self, data, rois, offset):
+        if not data.is_cuda:
+            raise NotImplementedError
+        if torch.is_grad_enabled() and (data.requires_grad or (not self.no_trans and offset.requires_grad)):
+            return ops.psroi_pooling(data, rois, offset, *self._conf())
+        with torch.no_grad():
+            return ops.psroi_pooling_forward(data, rois, offset, *self._conf())[0]
+
+    def _infer_shape(self, data, rois):
+        return (rois.shape[0], self.output_dim, self.pooled_size, self.pooled_size)
+
+
+class DCNv2Pooling(nn.Module):
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4, trans_std=.0):
+        super().__init__()
+        self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans = spatial_scale, pooled_size, output_dim, no_trans
+        self.group_size = group_size
+        self.part_size = pooled_size if part_size is None else part_size
+        self.sample_per_part, self.trans_std = sample_per_part, trans_std
+        self.func = DCNv2PoolingFunction(self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans, self.group_size,
+                                         self.part_size, self.sample_per_part, self.trans_std)
+
+    def forward(self, data, rois, offset):
+        if self.no_trans:
+            offset = data.new_empty(0)
+        return self.func(data, rois, offset)
+
+
+class DCNPooling(DCNv2Pooling):
+    """DCNv2Pooling whose offsets and mask come from its own fully connected layers (dcn_v2.py:108-171): pool without offsets,
+    offset_fc / mask_fc (last layers zero-initialised), pool with the offsets, times the mask."""
+
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4, trans_std=.0,
+                 deform_fc_dim=1024):
+        super().__init__(spatial_scale, pooled_size, output_dim, no_trans, group_size, part_size, sample_per_part, trans_std)
+        self.deform_fc_dim = deform_fc_dim
+        if not no_trans:
+            self.func_offset = DCNv2PoolingFunction(self.spatial_scale, self.pooled_size, self.output_dim, True, self.group_size,
+                                                    self.part_size, self.sample_per_part, self.trans_std)
+            feat = self.pooled_size * self.pooled_size * self.output_dim
+            self.offset_fc = nn.Sequential(nn.Linear(feat, self.deform_fc_dim), nn.ReLU(inplace=True),
+                                           nn.Linear(self.deform_fc_dim, self.deform_fc_dim), nn.ReLU(inplace=True),
+                                           nn.Linear(self.deform_fc_dim, self.pooled_size * self.pooled_size * 2))
+            self.mask_fc = nn.Sequential(nn.Linear(feat, self.deform_fc_dim), nn.ReLU(inplace=True),
+                                         nn.Linear(self.deform_fc_dim, self.pooled_size * self.pooled_size * 1), nn.Sigmoid())
+            with torch.no_grad():
+                self.offset_fc[4].weight.zero_()
+                self.offset_fc[4].bias.zero_()
+                self.mask_fc[2].weight.zero_()
+                self.mask_fc[2].bias.zero_()
+
+    def forward(self, data, rois):
+        if self.no_trans:
+            return self.func(data, rois, data.new_empty(0))
+        n = rois.shape[0]
+        x = self.func_offset(data, rois, data.new_empty(0))
+        offset = self.offset_fc(x.view(n, -1)).view(n, 2, self.pooled_size, self.pooled_size)
+        mask = self.mask_fc(x.view(n, -1)).view(n, 1, self.pooled_size, self.pooled_size)
+        return self.func(data, rois, offset) * mask

@@ -153,6 +153,121 @@ def dcn_v2(inp, offset, mask, weight, bias, stride, padding, dilation=1, deforma
     return _DCNv2.apply(inp, offset, mask, weight, bias, stride, padding, dilation, deformable_groups)
 
 
+def _psroi_prepare(name, data, rois, offset, no_trans, output_dim, group_size, pooled_size, part_size, sample_per_part, trans_std):
+    """The checks the pooling forward and backward share.  Returns (rois, offset or None, (N, C, H, W, n, rows, K))."""
+    _require_cuda(data, rois)
+    if not no_trans:
+        _require_cuda(offset)
+    for t, what in ((data, "data"), (rois, "rois")) + (() if no_trans else ((offset, "offset"),)):
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: %s is %s; only float32 is supported" % (name, what, t.dtype))
+    if not (0.0 <= trans_std <= 1.0):
+        raise RuntimeError("%s: trans_std must lie in [0, 1]" % name)            # the reference's assert (dcn_v2_func.py:97)
+    if data.dim() != 4 or rois.dim() != 2 or rois.shape[1] != 5:
+        raise RuntimeError("%s: data must be [N, C, H, W] and rois [n, 5]" % name)
+    if not data.is_contiguous():
+        raise RuntimeError("input tensor has to be contiguous")
+    N, C, H, W = data.shape
+    n = rois.shape[0]
+    rows, K = 0, 1
+    if not no_trans:
+        if offset.dim() != 4 or offset.shape[1] % 2 or offset.shape[1] < 2 or tuple(offset.shape[2:]) != (part_size, part_size):
+            raise RuntimeError("%s: offset must be [>= n, 2 * classes, part_size, part_size]" % name)
+        rows, K = offset.shape[0], offset.shape[1] // 2
+        offset = offset.contiguous()
+    return rois.contiguous(), (None if no_trans else offset), (N, C, H, W, n, rows, K)
+
+
+def _psroi_workspace(L, name, dims, output_dim, group_size, pooled_size, backward, device):
+    N, C, H, W, n, rows, K = dims
+    nbytes = L.m3d_dcn_v2_psroi_pooling_workspace_bytes(N, C, H, W, n, K, output_dim, group_size, pooled_size, int(backward))
+    if nbytes < 0:
+        raise RuntimeError("%s: bad shape (data channels %d, output_dim %d, group_size %d, classes %d)" % (name, C, output_dim, group_size, K))
+    return _workspace(nbytes, device) + (nbytes,)
+
+
+def psroi_pooling_forward(data, rois, offset, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                          sample_per_part, trans_std):
+    """DCNv2PoolingFunction.forward (model/DCNv2/dcn_v2_func.py:99-115) on the HIP library: m3d_dcn_v2_psroi_pooling_forward.
+    float32 only.  Returns (output, output_count), both [n, output_dim, pooled_size, pooled_size]; ``offset`` is ignored when
+    ``no_trans``."""
+    name = "psroi_pooling_forward"
+    rois, offset, dims = _psroi_prepare(name, data, rois, offset, no_trans, output_dim, group_size, pooled_size, part_size,
+                                        sample_per_part, trans_std)
+    N, C, H, W, n, rows, K = dims
+    L = _hip.lib()
+    out = torch.empty(n, output_dim, pooled_size, pooled_size, device=data.device, dtype=torch.float32)
+    count = torch.empty_like(out)
+    ws, base, nbytes = _psroi_workspace(L, name, dims, output_dim, group_size, pooled_size, False, data.device)
+    with torch.cuda.device(data.device):
+        _hip.check(L.m3d_dcn_v2_psroi_pooling_forward(data.data_ptr(), rois.data_ptr(), None if offset is None else offset.data_ptr(),
+                                                      out.data_ptr(), count.data_ptr(), N, C, H, W, n, rows, K, int(bool(no_trans)),
+                                                      float(spatial_scale), output_dim, group_size, pooled_size, part_size,
+                                                      sample_per_part, float(trans_std), base, nbytes, _stream()))
+    return out, count
+
+
+def psroi_pooling_backward(grad_output, data, rois, offset, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                           sample_per_part, trans_std, needs=(True, True)):
+    """DCNv2PoolingFunction.backward (model/DCNv2/dcn_v2_func.py:117-140) on the HIP library: returns (grad_data, grad_offset),
+    freshly written; an entry of ``needs`` that is False (or grad_offset under ``no_trans``) gives None and skips its work.  The
+    sample counts are recomputed by the kernel."""
+    name = "psroi_pooling_backward"
+    _require_cuda(grad_output)
+    rois, offset, dims = _psroi_prepare(name, data, rois, offset, no_trans, output_dim, group_size, pooled_size, part_size,
+                                        sample_per_part, trans_std)
+    N, C, H, W, n, rows, K = dims
+    if tuple(grad_output.shape) != (n, output_dim, pooled_size, pooled_size):
+        raise RuntimeError("%s: grad_output shape does not match the output size" % name)
+    if grad_output.dtype != torch.float32:
+        raise RuntimeError("%s: grad_output is %s; only float32 is supported" % (name, grad_output.dtype))
+    L = _hip.lib()
+    grad_output = grad_output.contiguous()
+    gdata = torch.empty_like(data) if needs[0] else None
+    goff = torch.empty_like(offset) if needs[1] and offset is not None else None
+    ws, base, nbytes = _psroi_workspace(L, name, dims, output_dim, group_size, pooled_size, True, data.device)
+    with torch.cuda.device(data.device):
+        _hip.check(L.m3d_dcn_v2_psroi_pooling_backward(grad_output.data_ptr(), data.data_ptr(), rois.data_ptr(),
+                                                       None if offset is None else offset.data_ptr(),
+                                                       None if gdata is None else gdata.data_ptr(),
+                                                       None if goff is None else goff.data_ptr(), N, C, H, W, n, rows, K,
+                                                       int(bool(no_trans)), float(spatial_scale), output_dim, group_size, pooled_size,
+                                                       part_size, sample_per_part, float(trans_std), base, nbytes, _stream()))
+    return gdata, goff
+
+
+class _PSROIPooling(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, data, rois, offset, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size, sample_per_part,
+                trans_std):
+        ctx.conf = (no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size, sample_per_part, trans_std)
+        ctx.save_for_backward(data, rois, offset)
+        out, count = psroi_pooling_forward(data, rois, offset, *ctx.conf)
+        ctx.mark_non_differentiable(count)
+        return out, count
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output, _grad_count):
+        data, rois, offset = ctx.saved_tensors
+        gdata, goff = psroi_pooling_backward(grad_output, data, rois, offset, *ctx.conf,
+                                             needs=(ctx.needs_input_grad[0], ctx.needs_input_grad[2]))
+        if ctx.needs_input_grad[2] and goff is None:            # no_trans: the offsets are not used
+            goff = torch.zeros_like(offset)
+        return (gdata, None, goff) + (None,) * 8
+
+
+def psroi_pooling(data, rois, offset, no_trans, spatial_scale, output_dim, group_size=1, pooled_size=7, part_size=None,
+                  sample_per_part=4, trans_std=0.0, return_count=False):
+    """Deformable PS-ROI pooling, differentiable in ``data`` and ``offset`` (``rois`` get None): m3d_dcn_v2_psroi_pooling_forward
+    with m3d_dcn_v2_psroi_pooling_backward behind it.  ``offset`` may be an empty tensor when ``no_trans``."""
+    _require_cuda(data, rois)
+    part_size = pooled_size if part_size is None else part_size
+    out, count = _PSROIPooling.apply(data, rois, offset, bool(no_trans), spatial_scale, output_dim, group_size, pooled_size, part_size,
+                                     sample_per_part, trans_std)
+    return (out, count) if return_count else out
+
+
 def rpn_targets(cls, prob, anchors, conf_vec, gt_table, feat_size):
     """compute_targets (lib/rpn_util.py:430-532) for a whole batch on the device: m3d_rpn_targets.  ``anchors`` float64 device
     [A, 9], ``conf_vec`` from ``host.loss.pack_conf``, ``gt_table`` from ``host.loss.pack_gts``; see host/loss.py."""
