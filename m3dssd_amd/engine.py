@@ -1030,15 +1030,36 @@ class Engine:
                      flops=2.0 * B * HW * n_bins * (self.ck + self.cv),
                 nbytes=B * HW * (self.ck + 3 * self.cv) * 4 + B * keys_pad * (self.ck + self.cv) * 4)
             return
+
+        def image(v, i):
+            return View(v.t, 1, v.h, v.w, v.c, v.cs, v.ptr + 4 * i * v.h * v.w * v.cs)
+
+        def image_gemm(name, inp, outv, wgt, stride, frag, res=None, **kw):
+            """1x1 convolution whose weights differ per image (`stride` floats apart in wgt).  The wave kernel and the igemm take
+            them in one launch, the igemm picking a tile's weights by the image of the tile's first row: no tile may straddle two
+            images, which holds for H*W % 64 == 0.  Any other map gets one igemm launch per image, with that image's weights as
+            shared weights, as ONE plan op."""
+            if frag or HW % 64 == 0:
+                self._conv(plan, name, None, inp, outv, 1, 0, res=res, wgt_ptr=wgt.data_ptr(), wgt_img_stride=stride, kh=1, kw=1,
+                           wgt_frag=frag, **kw)
+                return
+            sub = _Plan()
+            for i in range(B):
+                self._conv(sub, name, None, image(inp, i), image(outv, i), 1, 0, res=None if res is None else image(res, i),
+                           wgt_ptr=wgt.data_ptr() + 4 * i * stride, kh=1, kw=1, **kw)
+            assert len(sub.ops) == B and len({op[1] for op in sub.ops}) == 1, [op[:2] for op in sub.ops]
+            plan.keep += sub.keep
+            fns = [op[3] for op in sub.ops]
+            plan.ops.append((name, sub.ops[0][1][:-1] + ",per_image>", sum(op[2] for op in sub.ops),
+                             lambda st: [fn(st) for fn in fns], sub.ops[0][4]))
+
         logits = self._buf(plan, B, fh, fw, keys_pad)
-        self._conv(plan, "anab.logits", None, qv, logits, 1, 0, act=0, affine=False, wgt_ptr=khat.data_ptr(),
-                   wgt_img_stride=keys_pad * self.ck_pad, cout=n_bins, cout_pad=keys_pad, kh=1, kw=1, cin_true=self.ck,
-                   wgt_frag=wave_logits)
+        image_gemm("anab.logits", qv, logits, khat, keys_pad * self.ck_pad, wave_logits, act=0, affine=False, cout=n_bins,
+                   cout_pad=keys_pad, cin_true=self.ck)
         self._op(plan, "anab.softmax", "softmax", lambda st: _hip.check(L.m3d_softmax_rows(
             logits.ptr, B * HW, n_bins, keys_pad, st)), nbytes=B * HW * n_bins * 8)
-        self._conv(plan, "anab.pv", None, logits, out, 1, 0, act=act, res=x, res_mode=res_mode,
-                   wgt_ptr=vhatT.data_ptr(), wgt_img_stride=self.cv * keys_pad, cout=self.cv,
-                   cout_pad=_rup(self.cv, 32), kh=1, kw=1, scale=scale, shift=shift, cin_true=n_bins, wgt_frag=wave_pv)
+        image_gemm("anab.pv", logits, out, vhatT, self.cv * keys_pad, wave_pv, res=x, act=act, res_mode=res_mode, cout=self.cv,
+                   cout_pad=_rup(self.cv, 32), scale=scale, shift=shift, cin_true=n_bins)
 
     @classmethod
     def anab_standalone(cls, mod, x):

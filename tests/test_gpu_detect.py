@@ -117,32 +117,7 @@ def test_detect_matches_oracle_given_same_network_outputs(pre):
     """decode + top-k + NMS on the device vs oracle/detect.py fed with the ENGINE's network outputs:
     kept anchors/classes identical, coordinates to fp32 roundoff.  pre = 6000: nms_topN_pre beyond the 4096 rows one wave's
     registers hold (round 5: sort keys / "removed" words in LDS up to 16384; the reference has no limit)."""
-    from lib.rpn_util import im_detect_3d, detect_batch
-    from model.M3d_inference_align import build
-    from oracle import detect as odet
-    dev = _dev()
-    crop, B = (128, 320), 2
-    conf = synth.synth_conf(crop, 0, batch_size=B, device="cuda:0")
-    if pre:
-        conf.nms_topN_pre = pre
-    net = build(conf, "test")
-    net.load_state_dict(synth.synth_state_dict(0))
-    net = net.to(dev)
-    x = synth.synth_frames(B, crop, 1234)
-    ab = im_detect_3d(x[0], net, conf)
-    with torch.no_grad():
-        cls, prob, b2, b3, fs, rois = (t.cpu() for t in net(x[:1].to(dev)))
-    ref, keep, top = odet.detect_image(prob[0], b2[0], b3[0], rois, conf)
-    assert ab.shape == ref.shape
-    assert np.array_equal(ab[:, 13], ref[:, 13]) and np.array_equal(ab[:, 5], ref[:, 5])
-    # pure fp32 decode arithmetic on IDENTICAL network outputs: per column, to fp32 roundoff (expf differs by an ulp or two)
-    assert (np.abs(ab - ref) <= 1e-4 * (1.0 + np.abs(ref))).all(), np.abs((ab - ref) / (1.0 + np.abs(ref))).max(0)
-    dets, counts = detect_batch(net, x.to(dev), conf)
-    assert dets.shape == (B, conf.nms_topN_post, 14) and counts.shape == (B,)
-    k = int(counts[0])
-    assert k == min(len(ref), conf.nms_topN_post)
-    assert (np.abs(dets[0, :k].cpu().numpy() - ref[:k]) <= 1e-4 * (1.0 + np.abs(ref[:k]))).all()
-    assert dets[0, k:].abs().max().item() == 0 if k < conf.nms_topN_post else True
+    _detect_vs_oracle((128, 320), 2, pre)
 
 
 def test_pipelined_detector_matches_detect_batch():

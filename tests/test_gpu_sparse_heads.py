@@ -177,12 +177,14 @@ def _batches():
     return [synth.synth_frames(B, CROP, s).to(_dev()) for s in (1234, 3, 4, 5)]
 
 
-def _run_detectors(net, conf, xs):
-    """Detections of the four batches from PipelinedDetector and FrameDetector with sparse heads, and the n_rows each left."""
+def _run_detectors(net, conf, xs, crop=CROP, sparse_heads=True):
+    """Detections of the batches xs from PipelinedDetector and FrameDetector with sparse heads (sparse_heads=False: dense), and
+    the n_rows each left."""
     from m3dssd_amd.pipeline import FrameDetector, PipelinedDetector
-    plan = net.engine().plan_for(B, *CROP)
-    pipe = PipelinedDetector(net, conf, B, *CROP, sparse_heads=True)
-    assert pipe.sparse_heads
+    nb = xs[0].shape[0]
+    plan = net.engine().plan_for(nb, *crop)
+    pipe = PipelinedDetector(net, conf, nb, *crop, sparse_heads=sparse_heads)
+    assert pipe.sparse_heads == sparse_heads
     got_p = []
     for x in xs:
         r = pipe.step(x)
@@ -191,8 +193,8 @@ def _run_detectors(net, conf, xs):
     r = pipe.flush()
     got_p.append((r[0].clone(), r[1].clone()))
     n_p = int(plan.named["n_rows"].item())
-    fd = FrameDetector(net, conf, *CROP, batch=B, sparse_heads=True)
-    assert fd.sparse_heads
+    fd = FrameDetector(net, conf, *crop, batch=nb, sparse_heads=sparse_heads)
+    assert fd.sparse_heads == sparse_heads
     got_f = []
     for x in xs:
         r = fd.detect(x)
