@@ -87,7 +87,8 @@ const char *m3d_last_error(void);
  *                  m3d_anab_attend_f32_rows (additive);
  *                  m3d_head_mlp2_bf16_forward_rows, m3d_anab_attend_bf16_rows (additive);
  *                  m3d_dcn_v2_psroi_pooling_forward, m3d_dcn_v2_psroi_pooling_backward,
- *                  m3d_dcn_v2_psroi_pooling_workspace_bytes (additive). */
+ *                  m3d_dcn_v2_psroi_pooling_workspace_bytes (additive);
+ *                  m3d_anab_attention_forward, m3d_anab_attention_backward, m3d_anab_attention_workspace_bytes (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -770,6 +771,37 @@ int m3d_anab_attend_f32_rows(const float *q, int q_cs, const float *khat, int k_
                              int keys, int keys_pad, int Cv, const float *res, int res_cs, int res_mode, const float *scale,
                              const float *shift, int act, float *out, int out_cs, const int *rows, const int *n_rows,
                              m3d_stream_t stream);
+/* The ANAB attention core for TRAINING (csrc/anab_train.hip; attention.py:136-147 + 207-211, no residual / affine / activation: those
+ * stay with the caller).  Per image, fp32, row views with a channel stride each: q [B*HW][q_cs] (first Ck channels), k (Ck), v (Cv),
+ * g (the 4 gates behind their sigmoid, scale order), bins b = the AdaptiveAvgPool2d windows of sizes (1, 4, 8, 16) in scale-major
+ * order (337 keys; start = floor(i*H/s), end = ceil((i+1)*H/s)):
+ *     khat[b][c] = (1 / area_b) * sum_{p in win_b} g[p][scale(b)] * k[p][c],   vhat likewise from v,
+ *     S = q . khat^T,   P = softmax_keys(S),   out = P . vhat               (out [B*HW][out_cs], first Cv channels).
+ * Forward: the pooling launches of the engine (m3d_anab_pool_nested where H % 16 == 0 and W % 16 == 0, m3d_anab_pool_partial +
+ * _finish otherwise; K and V pooled one after the other) and m3d_anab_attend_f32 without its epilogue, so it has that kernel's
+ * support set: (Ck, Cv) in {(64, 128), (128, 128), (168, 128), (168, 256)}, H * W % 128 == 0, any H, W >= 1 otherwise; anything else is
+ * M3D_E_ARG and m3d_anab_attention_workspace_bytes returns -1.  khat [B][352][round_up(Ck, 32)] and vhat^T [B][Cv][352] are the
+ * first two blocks of the workspace.
+ * Backward, with dO = grad_out and O = P . vhat:
+ *     dvhat = P^T dO,  dP = dO vhat^T,  D = rowsum(dO * O),  dS = P * (dP - D),  dq = dS khat,  dkhat = dS^T q,
+ *     and with w_b(p) = [p in win_b] / area_b:   dk[p][c] = sum_b w_b(p) g[p][scale(b)] dkhat[b][c],   dv the same with dvhat,
+ *     dg[p][s] = sum_{b: scale(b) = s} w_b(p) (sum_c k[p][c] dkhat[b][c] + sum_c v[p][c] dvhat[b][c]).
+ * A pixel is taken with EVERY bin that contains it (one per scale where the windows nest, up to two per dimension where H or W is
+ * not a multiple of the scale, more where H < scale).  The backward pools again into its own workspace (it needs nothing of the
+ * forward's); S, P, dP and dS live in registers only; the products run on fp32 MFMA.
+ * Semantics: every non-NULL gradient is OVERWRITTEN (channels past Ck / Cv / 4 inside its stride are neither read nor written); a
+ * NULL gradient is "not wanted" and skips the work only it needs; a result is the same bits whichever other gradients were asked
+ * for and from run to run (no atomics; the sums over the pixels of an image are taken in a fixed order); nothing depends on what
+ * the workspace held.  q and grad_out: 16-byte aligned views, row strides multiples of 4 floats; workspace 256-byte aligned,
+ * m3d_anab_attention_workspace_bytes(B, H, W, Ck, Cv, backward) bytes. */
+long long m3d_anab_attention_workspace_bytes(int B, int H, int W, int Ck, int Cv, int backward);
+int m3d_anab_attention_forward(const float *q, const float *k, const float *v, const float *g, float *out, int B, int H, int W, int Ck,
+                               int Cv, int q_cs, int k_cs, int v_cs, int g_cs, int out_cs, void *workspace, long long workspace_bytes,
+                               m3d_stream_t stream);
+int m3d_anab_attention_backward(const float *q, const float *k, const float *v, const float *g, const float *grad_out, float *grad_q,
+                                float *grad_k, float *grad_v, float *grad_g, int B, int H, int W, int Ck, int Cv, int q_cs, int k_cs,
+                                int v_cs, int g_cs, int go_cs, int gq_cs, int gk_cs, int gv_cs, int gg_cs, void *workspace,
+                                long long workspace_bytes, m3d_stream_t stream);
 /* In-place softmax over the first `valid` columns of each row; columns [valid, cs) are zeroed. */
 int m3d_softmax_rows(float *x, int rows, int valid, int cs, m3d_stream_t stream);
 

@@ -216,6 +216,9 @@ SIGNATURES = {
                                          P, P, P]),
     "m3d_anab_pool_nested_bf16": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, c_int, P]),
     "m3d_anab_pool_nested_bf16_ex": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, c_int, P, P, P]),
+    "m3d_anab_attention_workspace_bytes": (c_ll, [c_int] * 6),
+    "m3d_anab_attention_forward": (c_int, [P] * 5 + [c_int] * 10 + [P, c_ll, P]),
+    "m3d_anab_attention_backward": (c_int, [P] * 9 + [c_int] * 14 + [P, c_ll, P]),
     "m3d_softmax_rows": (c_int, [P, c_int, c_int, c_int, P]),
     "m3d_bundle_outputs": (c_int, [P] * 7 + [c_int] * 3 + [P]),
     "m3d_decode_rows": (c_int, [P] * 9 + [c_int] * 3 + [P]),

@@ -22,6 +22,9 @@ class center_align(nn.Module):
         self.align = DCNv2(ch, ch, self.kernel_size, 1, kernel_size // 2, dilation=1, deformable_groups=1)
 
     def forward(self, x, bbox_x, bbox_y, prob):
+        from . import train
+        if train.wants_grad(self, x, bbox_x, bbox_y, prob):
+            return train.center_align_forward(self, x, bbox_x, bbox_y, prob)
         from .standalone import center_align_forward
         return center_align_forward(self, x, bbox_x, bbox_y, prob)
 
@@ -49,5 +52,8 @@ class shape_align(nn.Module):
         self.proj = nn.Conv2d(ch * 2, ch, 1, bias=False)   # present in the state_dict, unused by forward (:145,205-208)
 
     def forward(self, x, prob):
+        from . import train
+        if train.wants_grad(self, x, prob):
+            return train.shape_align_forward(self, x, prob)
         from .standalone import shape_align_forward
         return shape_align_forward(self, x, prob)

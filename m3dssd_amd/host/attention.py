@@ -1,4 +1,7 @@
-"""ANAB asymmetric non-local block with the reference's interface (model/module/attention.py:120-216)."""
+"""ANAB asymmetric non-local block with the reference's interface (model/module/attention.py:120-216).
+
+Eval mode and no-grad calls run the fused inference launches; training mode with grad enabled on a device tensor runs the
+differentiable form of host/train.py (m3d_anab_attention_forward / _backward)."""
 from torch import nn
 
 
@@ -29,5 +32,9 @@ class ANAB(nn.Module):
         self.value_papa = PAPAModule(sizes=psp_size)
 
     def forward(self, x):
+        from . import train
+        if train.wants_grad(self, x):
+            # training form: torch projections, the differentiable attention core (ops.anab_attention), the residual
+            return train.anab_forward(self, x)
         from .standalone import anab_forward
         return anab_forward(self, x)

@@ -2,9 +2,11 @@
 (model/pose_dla_dcn.py: BasicBlock :93-121, Bottleneck :162-200, Root :251-269, Tree :272-327, DLA :330-397,
 dla34 :419-425, dla102 :435-441, DeformConv :471-485, IDAUp :519-552, DLAUp :556-578, DLASeg :641-696).
 
-The modules are parameter containers; the arithmetic runs in the HIP engine
+In eval mode the modules are parameter containers and the arithmetic runs in the HIP engine
 (m3dssd_amd/engine.py) -- ``DLASeg.forward`` executes the backbone part of the engine plan,
-``DeformConv.forward`` the fused offset-conv + DCN + BN + LeakyReLU launches."""
+``DeformConv.forward`` the fused offset-conv + DCN + BN + LeakyReLU launches.  In training mode with grad enabled on a device
+tensor ``DLASeg.forward`` walks the sub-modules through their plain torch ``forward``s (host/train.py, the semantics of the
+reference's), with the differentiable DCN inside DeformConv."""
 import math
 import warnings
 
@@ -12,6 +14,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import train
 from .dcn import DCN
 
 BN_MOMENTUM = 0.1
@@ -26,6 +29,9 @@ class BasicBlock(nn.Module):
         self.conv2 = nn.Conv2d(planes, planes, 3, stride=1, padding=1, bias=True, dilation=dilation)
         self.bn2 = nn.BatchNorm2d(planes, momentum=BN_MOMENTUM)
         self.stride = stride
+
+    def forward(self, x, residual=None):
+        return train.basic_block_forward(self, x, residual)
 
 
 class Bottleneck(nn.Module):
@@ -43,6 +49,9 @@ class Bottleneck(nn.Module):
         self.relu = nn.LeakyReLU(inplace=True)
         self.stride = stride
 
+    def forward(self, x, residual=None):
+        return train.bottleneck_forward(self, x, residual)
+
 
 class Root(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size, residual):
@@ -51,6 +60,9 @@ class Root(nn.Module):
         self.bn = nn.BatchNorm2d(out_channels, momentum=BN_MOMENTUM)
         self.relu = nn.LeakyReLU(inplace=True)
         self.residual = residual
+
+    def forward(self, *x):
+        return train.root_forward(self, *x)
 
 
 class Tree(nn.Module):
@@ -77,6 +89,9 @@ class Tree(nn.Module):
             self.project = nn.Sequential(nn.Conv2d(in_channels, out_channels, 1, stride=1, bias=False),
                                          nn.BatchNorm2d(out_channels, momentum=BN_MOMENTUM))
 
+    def forward(self, x, residual=None, children=None):
+        return train.tree_forward(self, x, residual, children)
+
 
 class DLA(nn.Module):
     def __init__(self, levels, channels, block=BasicBlock, residual_root=False):
@@ -99,6 +114,9 @@ class DLA(nn.Module):
                      nn.BatchNorm2d(planes, momentum=BN_MOMENTUM), nn.LeakyReLU(inplace=True)]
             inplanes = planes
         return nn.Sequential(*mods)
+
+    def forward(self, x):
+        return train.dla_forward(self, x)
 
 
 def dla34(pretrained=False, **kwargs):
@@ -159,6 +177,9 @@ class IDAUp(nn.Module):
             setattr(self, "up_%d" % i, up)
             setattr(self, "node_%d" % i, DeformConv(o, o))
 
+    def forward(self, layers, startp, endp):
+        return train.ida_up_forward(self, layers, startp, endp)
+
 
 class DLAUp(nn.Module):
     def __init__(self, startp, channels, scales, in_channels=None, conf=None):
@@ -173,6 +194,9 @@ class DLAUp(nn.Module):
             setattr(self, "ida_%d" % i, IDAUp(channels[j], in_channels[j:], scales[j:] // scales[j], conf=conf))
             scales[j + 1:] = scales[j]
             in_channels[j + 1:] = [channels[j] for _ in channels[j + 1:]]
+
+    def forward(self, layers):
+        return train.dla_up_forward(self, layers)
 
 
 class DLASeg(nn.Module):
@@ -198,5 +222,7 @@ class DLASeg(nn.Module):
         self._engine = None
 
     def forward(self, x):
+        if train.wants_grad(self, x):
+            return train.dlaseg_forward(self, x)
         from .standalone import dlaseg_forward
         return dlaseg_forward(self, x)

@@ -268,6 +268,107 @@ def psroi_pooling(data, rois, offset, no_trans, spatial_scale, output_dim, group
     return (out, count) if return_count else out
 
 
+_ANAB_PAIRS = ((64, 128), (128, 128), (168, 128), (168, 256))
+
+
+def _anab_rows(name, t, what, rows):
+    """A row matrix [rows, C] that may be a column slice of a wider one: unit stride inside a row -> (C, row stride)."""
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s: %s is %s; only float32 is supported" % (name, what, t.dtype))
+    if t.dim() != 2 or t.shape[0] != rows:
+        raise RuntimeError("%s: %s must be a row matrix [B*H*W = %d, C] (got %s)" % (name, what, rows, tuple(t.shape)))
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise RuntimeError("%s: %s must have unit stride inside a row (a column slice of a row-major matrix)" % (name, what))
+    return t.shape[1], t.stride(0)
+
+
+def _anab_prepare(name, q, k, v, gates, B, H, W):
+    _require_cuda(q, k, v, gates)
+    rows = B * H * W
+    (ck, q_cs), (ck2, k_cs), (cv, v_cs), (ng, g_cs) = (_anab_rows(name, t, what, rows) for t, what in
+                                                      ((q, "q"), (k, "k"), (v, "v"), (gates, "gates")))
+    if ck2 != ck or ng != 4:
+        raise RuntimeError("%s: q and k need the same channel count and gates 4 channels (got %d, %d, %d)" % (name, ck, ck2, ng))
+    if (H * W) % 128:
+        raise RuntimeError("%s: H*W must be a multiple of 128 (HW %% 128 == 0; got %dx%d)" % (name, H, W))
+    if (ck, cv) not in _ANAB_PAIRS:
+        raise RuntimeError("%s: (Ck, Cv) must be one of %s (got (%d, %d))" % (name, _ANAB_PAIRS, ck, cv))
+    return ck, cv, (q_cs, k_cs, v_cs, g_cs)
+
+
+def _anab_aligned(t):
+    """q / grad_out go through 16-byte loads: an unaligned view or an odd row stride is copied once."""
+    return t if t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) == 1 else t.contiguous()
+
+
+def anab_attention_forward(q, k, v, gates, B, H, W):
+    """m3d_anab_attention_forward: out [B*H*W, Cv] = softmax_keys(q . khat^T) . vhat with the gated pyramid pooling of ANAB."""
+    name = "anab_attention_forward"
+    ck, cv, (q_cs, k_cs, v_cs, g_cs) = _anab_prepare(name, q, k, v, gates, B, H, W)
+    L = _hip.lib()
+    q = _anab_aligned(q)
+    nbytes = L.m3d_anab_attention_workspace_bytes(B, H, W, ck, cv, 0)
+    if nbytes < 0:
+        raise RuntimeError("%s: unsupported shape" % name)
+    out = torch.empty(B * H * W, cv, device=q.device, dtype=torch.float32)
+    ws, base = _workspace(nbytes, q.device)
+    with torch.cuda.device(q.device):
+        _hip.check(L.m3d_anab_attention_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), out.data_ptr(), B, H, W,
+                                                ck, cv, q.stride(0), k_cs, v_cs, g_cs, cv, base, nbytes, _stream()))
+    return out
+
+
+def anab_attention_backward(q, k, v, gates, grad_out, B, H, W, needs=(True, True, True, True)):
+    """m3d_anab_attention_backward: (grad_q, grad_k, grad_v, grad_gates), freshly written and contiguous; an entry of ``needs`` that
+    is False gives None and skips the work only that gradient needs."""
+    name = "anab_attention_backward"
+    _require_cuda(grad_out)
+    ck, cv, (q_cs, k_cs, v_cs, g_cs) = _anab_prepare(name, q, k, v, gates, B, H, W)
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (B * H * W, cv):
+        raise RuntimeError("%s: grad_out must be float32 [B*H*W, Cv]" % name)
+    L = _hip.lib()
+    q, grad_out = _anab_aligned(q), _anab_aligned(grad_out)
+    nbytes = L.m3d_anab_attention_workspace_bytes(B, H, W, ck, cv, 1)
+    if nbytes < 0:
+        raise RuntimeError("%s: unsupported shape" % name)
+    grads = [torch.empty(B * H * W, c, device=q.device, dtype=torch.float32) if need else None
+             for c, need in zip((ck, ck, cv, 4), needs)]
+    ptrs = [g.data_ptr() if g is not None else None for g in grads]
+    ws, base = _workspace(nbytes, q.device)
+    with torch.cuda.device(q.device):
+        _hip.check(L.m3d_anab_attention_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), grad_out.data_ptr(),
+                                                 *ptrs, B, H, W, ck, cv, q.stride(0), k_cs, v_cs, g_cs, grad_out.stride(0), ck, ck, cv,
+                                                 4, base, nbytes, _stream()))
+    return tuple(grads)
+
+
+class _ANABAttention(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, q, k, v, gates, B, H, W):
+        ctx.dims = (B, H, W)
+        ctx.save_for_backward(q, k, v, gates)
+        return anab_attention_forward(q, k, v, gates, B, H, W)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, gates = ctx.saved_tensors
+        grads = anab_attention_backward(q, k, v, gates, grad_out, *ctx.dims, needs=tuple(ctx.needs_input_grad[:4]))
+        return grads + (None, None, None)
+
+
+def anab_attention(q, k, v, gates, B, H, W):
+    """The ANAB attention core (gated pyramid pooling of k / v into 337 keys, softmax(q . khat^T) . vhat), differentiable in its four
+    tensor arguments: m3d_anab_attention_forward with m3d_anab_attention_backward behind it.  Row matrices [B*H*W, C], float32;
+    column slices of one wider matrix are taken as they are (their row stride is handed to the kernels).  ``gates`` are the four
+    spatial gates behind their sigmoid.  No torch fallback: an unsupported shape raises RuntimeError."""
+    _require_cuda(q, k, v, gates)
+    # (the shape and type rules are checked by anab_attention_forward, behind the float32 cast of custom_fwd under autocast)
+    return _ANABAttention.apply(q, k, v, gates, B, H, W)
+
+
 def rpn_targets(cls, prob, anchors, conf_vec, gt_table, feat_size):
     """compute_targets (lib/rpn_util.py:430-532) for a whole batch on the device: m3d_rpn_targets.  ``anchors`` float64 device
     [A, 9], ``conf_vec`` from ``host.loss.pack_conf``, ``gt_table`` from ``host.loss.pack_gts``; see host/loss.py."""

@@ -2,7 +2,15 @@
 
 ``RPN.forward(x)`` returns exactly what the reference does in eval mode --
 ``(cls [B,N,4], prob [B,N,4], bbox_2d [B,N,4], bbox_3d [B,N,7], feat_size [2], rois [N,5])`` --
-computed by the HIP engine.  Training (phase='train') is out of scope for this path."""
+computed by the HIP engine.
+
+In training mode (``build(conf, 'train')`` / ``.train()``) with grad enabled ``RPN.forward(x)`` returns the reference's training
+5-tuple ``(cls, prob, bbox_2d, bbox_3d, feat_size)`` from a differentiable forward (host/train.py): the backbone, the heads and
+BatchNorm with batch statistics are torch layers, DCNv2 (DeformConv, shape_align, center_align) and the ANAB attention core are
+HIP operators with hand-written backwards (``ops.dcn_v2``, ``ops.anab_attention``).  ``net(x)`` -> ``RPN_3D_loss`` ->
+``loss.backward()`` -> ``optimizer.step()`` -> ``net.eval()`` runs on the device; ``train()`` drops the packed engine, so the
+next eval forward packs the stepped parameters.  Single device: ``nn.DataParallel`` replicas in training mode are not part of it,
+and ``compute_dtype`` selects the eval engine only."""
 import os
 
 import numpy as np
@@ -211,13 +219,26 @@ class RPN(nn.Module):
         return self._engine
 
     def forward(self, x):
-        """Eval-mode forward of the reference (M3d_inference_align.py:303-313).  The four big outputs are FRESH tensors, as the
+        """Training mode with grad enabled on a device tensor: the differentiable forward of host/train.py, which returns the
+        reference's training 5-tuple (cls, prob, bbox_2d, bbox_3d, feat_size) (M3d_inference_align.py:215-304); it does not depend
+        on ``compute_dtype``.  Training mode under ``torch.no_grad()`` raises.
+        Eval-mode forward of the reference (M3d_inference_align.py:303-313).  The four big outputs are FRESH tensors, as the
         reference's are: a caller may keep them across iterations.  ``conf.reuse_outputs = True`` (or ``net.reuse_outputs = True``)
         returns views of the engine's plan-owned buffers instead, which the next forward of the same shape overwrites -- the form
         the device detection stage (lib.rpn_util.detect_batch / im_detect_3d, PipelinedDetector) uses internally: it consumes the
         outputs before the next forward.  Fresh outputs cost nothing but their allocation: `m3d_bundle_outputs` writes them in place
         (round 6; no copies)."""
+        if self.training and torch.is_grad_enabled() and x.is_cuda and not getattr(self, "_is_replica", False):
+            from .train import rpn_forward
+            return rpn_forward(self, x)
         return self._forward_views(x, fresh=not self.reuse_outputs)
+
+    def train(self, mode=True):
+        """Entering training mode drops the packed engine: a train-mode forward changes BatchNorm buffers and an optimizer step
+        changes parameters in place, so the next eval forward packs again.  ``train(False)`` / ``.eval()`` drop nothing."""
+        if mode:
+            self.refresh_engine()
+        return super().train(mode)
 
     def _forward_views(self, x, fresh=False):
         if self.training:
