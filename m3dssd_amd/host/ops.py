@@ -297,8 +297,11 @@ def _anab_prepare(name, q, k, v, gates, B, H, W):
 
 
 def _anab_aligned(t):
-    """q / grad_out go through 16-byte loads: an unaligned view or an odd row stride is copied once."""
-    return t if t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) == 1 else t.contiguous()
+    """q / grad_out go through 16-byte loads: an unaligned view or an odd row stride is copied once, and so is a view whose rows
+    overlap (row stride below the channel count: the expanded grad_out that autograd hands over behind ``.sum(0)``)."""
+    if t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.stride(1) == 1:
+        return t
+    return t.contiguous()
 
 
 def anab_attention_forward(q, k, v, gates, B, H, W):

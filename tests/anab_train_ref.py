@@ -4,7 +4,8 @@
 AdaptiveAvgPool2d pyramids of the keys and the values, model/module/attention.py:136-147) + bmm + softmax + bmm (:207-211) -- on
 row matrices [B*H*W, C] in whatever dtype and on whatever device they come (float64 on the CPU: the yardstick; float32 on the
 device: the error a float32 evaluation in another summation order makes).  ``anab_module`` wraps it with the projections and the
-residual of ANAB.forward.  tests/test_anab_train_host.py pins both against oracle.model_cpu.anab and with gradcheck.
+residual of ANAB.forward; ``anab_logits`` gives the logits in front of its softmax and ``peak_rows_`` scales rows of q so that they
+pass ln(FLT_MAX).  tests/test_anab_train_host.py pins both against oracle.model_cpu.anab and with gradcheck.
 
 ``dcn_ref``: the gather-form DCNv2 of tests/dcn_grad_ref.py, device-aware (the index vectors are made on the input's device), so
 that a whole network can run with it in place of the HIP operator."""
@@ -14,16 +15,25 @@ import torch.nn.functional as F
 PSP = (1, 4, 8, 16)
 
 
+def _planes(t, B, H, W):
+    return t.reshape(B, H, W, t.shape[-1]).permute(0, 3, 1, 2)
+
+
+def _pooled(t, g, B, H, W):
+    """The gated pyramid of a row matrix: [B, C, 337], bins scale-major (1 + 16 + 64 + 256)."""
+    tt, gg = _planes(t, B, H, W), _planes(g, B, H, W)
+    return torch.cat([F.adaptive_avg_pool2d(tt * gg[:, i:i + 1], (z, z)).flatten(2) for i, z in enumerate(PSP)], -1)
+
+
+def anab_logits(q, k, g, B, H, W):
+    """The logits [B, H*W, 337] that ``anab_core`` hands to its softmax."""
+    return torch.bmm(q.reshape(B, H * W, -1), _pooled(k, g, B, H, W))
+
+
 def anab_core(q, k, v, g, B, H, W):
     hw = H * W
-
-    def planes(t):
-        return t.reshape(B, H, W, t.shape[-1]).permute(0, 3, 1, 2)
-
-    kk, vv, gg = planes(k), planes(v), planes(g)
-    kp = torch.cat([F.adaptive_avg_pool2d(kk * gg[:, i:i + 1], (z, z)).flatten(2) for i, z in enumerate(PSP)], -1)   # [B, Ck, 337]
-    vp = torch.cat([F.adaptive_avg_pool2d(vv * gg[:, i:i + 1], (z, z)).flatten(2) for i, z in enumerate(PSP)], -1)   # [B, Cv, 337]
-    att = torch.softmax(torch.bmm(q.reshape(B, hw, -1), kp), dim=-1)
+    vp = _pooled(v, g, B, H, W)                                                                                       # [B, Cv, 337]
+    att = torch.softmax(anab_logits(q, k, g, B, H, W), dim=-1)
     return torch.bmm(att, vp.transpose(1, 2)).reshape(B * hw, -1)
 
 
@@ -98,3 +108,11 @@ def make_core_case(B, H, W, Ck, Cv, seed):
     gwide = torch.full((n, Cv + 8), 1e30)
     gwide[:, 4:4 + Cv] = torch.randn(n, Cv, generator=g)
     return wide, views, gwide
+
+
+def peak_rows_(wide, views, every=37, factor=40.0):
+    """Every ``every``-th row of q (rows 0, every, 2 every, ...) times ``factor``, in place: with q ~ 0.3 N(0, 1) and factor 40 the
+    largest logit of such a row passes ln(FLT_MAX) = 88.72, so exp(s) overflows float32 where exp(s - max) does not."""
+    o, c = views[0]
+    wide[::every, o:o + c] *= factor
+    return wide

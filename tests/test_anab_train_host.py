@@ -43,7 +43,7 @@ def test_workspace_rule_follows_the_support_set():
     assert f(0, 8, 16, 168, 128, 0) == -1
 
 
-@pytest.mark.parametrize("B,H,W", [(2, 8, 16), (1, 5, 7)])
+@pytest.mark.parametrize("B,H,W", [(2, 8, 16), (1, 5, 7), (1, 32, 4), (1, 16, 8), (1, 128, 1), (2, 64, 2)])     # and the narrow maps
 def test_composition_equals_the_forward_oracle(B, H, W):
     g = torch.Generator().manual_seed(3)
     C = 16
@@ -58,7 +58,7 @@ def test_composition_equals_the_forward_oracle(B, H, W):
     assert (got64 - want.double()).abs().max().item() <= 1e-5 * want.abs().max().item()
 
 
-@pytest.mark.parametrize("B,H,W", [(1, 5, 7), (1, 8, 16)])
+@pytest.mark.parametrize("B,H,W", [(1, 5, 7), (1, 8, 16), (1, 8, 2), (1, 20, 1)])
 def test_gradcheck_of_the_composition(B, H, W):
     g = torch.Generator().manual_seed(7)
     n = B * H * W
@@ -91,6 +91,31 @@ def test_host_operator_refusals():
     with pytest.raises(RuntimeError, match=r"\(Ck, Cv\)"):
         ops._anab_prepare("anab_attention", fake(q[:, :64]), fake(k[:, :64]), fake(torch.zeros(n, 256)), fake(g), 1, 8, 16)
     assert ops._anab_prepare("anab_attention", fake(q), fake(k), fake(v), fake(g), 1, 8, 16)[:2] == (168, 128)
+
+
+def test_aligned_copies_what_the_kernels_cannot_read():
+    """ops._anab_aligned hands q / grad_out on as they are only where 16-byte row loads are possible AND the rows do not overlap:
+    autograd's grad_out behind ``.sum(0)`` has strides (0, 1), behind ``.sum()`` (0, 0), and the C ABI refuses go_cs < Cv."""
+    from m3dssd_amd.host import ops
+    n, c = 640, 128
+    g = torch.Generator().manual_seed(5)
+    dense = torch.randn(n, c, generator=g)
+    assert dense.data_ptr() % 16 == 0
+    assert ops._anab_aligned(dense) is dense
+    wide = torch.randn(n, c + 8, generator=g)
+    assert ops._anab_aligned(wide[:, 4:4 + c]).data_ptr() == wide.data_ptr() + 16            # an aligned column slice: as it is
+    row = torch.randn(c, generator=g)
+    for view in (row.expand(n, c), torch.randn((), generator=g).expand(n, c), row[:1].expand(n, c), wide[:, 3:3 + c],
+                 torch.randn(n, c + 2, generator=g)[:, :c], dense.t().contiguous().t()):
+        got = ops._anab_aligned(view)
+        assert got.stride() == (c, 1) and got.data_ptr() % 16 == 0, view.stride()
+        assert torch.equal(got, view)
+    x = torch.randn(n, c, generator=g, requires_grad=True)                 # the strides autograd really hands over
+    seen = []
+    x.register_hook(lambda t: seen.append(t.stride()))
+    x.sum(0).backward(row)
+    x.sum().backward()
+    assert seen == [(0, 1), (0, 0)]
 
 
 @pytest.mark.parametrize("config", ["anab_fullalign", "base"])

@@ -4,7 +4,12 @@ tests/anab_train_ref.py, reproducibility, NULL gradients, and the differentiable
 Bound of the comparisons: per tensor err = max|got - ref64| / max|ref64|, and err_op <= 4 * err_torch32 + 2^-20, where
 err_torch32 is the error of the float32 torch composition computed in the same test on the device: both are float32 evaluations
 of the same sums in different orders (on the CPU two such orders differed by at most 1.9x on the operator cases, errors 0.4e-6 to
-2.6e-6); a dropped bin or a wrong term shows at 1e-3 and above."""
+2.6e-6); a dropped bin or a wrong term shows at 1e-3 and above.
+
+The operator cases also cover B > 1 together with several 512-pixel chunks of the key-major kernel, the nested pooling at Ck = 168,
+Cv = 256 with several images, maps narrower than 16, rows whose logits pass ln(FLT_MAX), each image alone against the batch (bit
+for bit), a canary behind the workspace, and the autograd layer with the grad_out layouts autograd produces (measured margins:
+docs/LAB_NOTES.md section 15)."""
 import functools
 
 import pytest
@@ -24,8 +29,23 @@ CASES = [(2, 8, 16, 168, 128),      # H < 16: two bins per pixel at scale 16
          (1, 12, 32, 128, 128),     # uneven windows
          (1, 4, 32, 168, 128),      # H below two scales
          (1, 16, 40, 168, 128),     # the 128x320 map
-         (1, 8, 16, 168, 256)]      # value-channel split
+         (1, 8, 16, 168, 256),      # value-channel split
+         # batch x pixel chunks of the key-major kernel (512 pixels per chunk: partial row (img * nch + ch) * 352 + key) and narrow maps
+         (2, 16, 72, 168, 128),     # 6: HW 1152 = 36 tiles, nch = 3 with a ragged last chunk of 4 tiles; windows overlap along x
+         (2, 32, 48, 168, 128),     # 7: nested windows at Ck = 168 (the branch of the 48x160 training map), nch = 3, full chunks
+         (2, 16, 40, 168, 256),     # 8: value-channel split with B = 2, nch = 2
+         (3, 16, 40, 128, 128),     # 9: Ck = 128 with B = 3, nch = 2
+         (1, 32, 4, 168, 128),      # 10: W < 8: 2 bins along x at scale 8, 4 at scale 16
+         (1, 16, 8, 64, 128),       # 11: W = 8 < 16
+         (1, 128, 1, 168, 128),     # 12: W = 1: a pixel lies in all 16 x-bins of scale 16
+         (2, 64, 2, 168, 128)]      # 13: B = 2 on a narrow map
+NEW0 = 6                            # the cases from here on are seeded 200 + (i - NEW0), the ones in front 100 + i
+IDS = ["%dx%dx%d_ck%d_cv%d" % c for c in CASES]
+PEAKED = [NEW0, NEW0 + 1, NEW0 + 2, NEW0 + 4]           # run again with every 37th row of q times 40 (logits past ln(FLT_MAX))
+BATCHED = [NEW0, NEW0 + 1, NEW0 + 2]
+LN_FLT_MAX = 88.73
 GUARD = 7.25
+CANARY = 4096                       # bytes behind the workspace size the library asks for, watched by every _run
 NAMES = ("out", "grad_q", "grad_k", "grad_v", "grad_gates")
 
 
@@ -38,10 +58,19 @@ def _bound(e32):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(i):
+def _inputs(i, peaked=False):
+    """The CPU inputs of case ``i`` (tests/anab_train_ref.py::make_core_case), ``peaked``: every 37th row of q times 40."""
+    wide, views, gwide = R.make_core_case(*CASES[i], seed=100 + i if i < NEW0 else 200 + i - NEW0)
+    if peaked:
+        R.peak_rows_(wide, views, 37, 40.0)
+    return wide, views, gwide
+
+
+@functools.lru_cache(maxsize=None)
+def _case(i, peaked=False):
     """Inputs on the device (slices of wider matrices), the float64 yardstick and the float32 torch composition's errors."""
     B, H, W, Ck, Cv = CASES[i]
-    wide, views, gwide = R.make_core_case(B, H, W, Ck, Cv, seed=100 + i)
+    wide, views, gwide = _inputs(i, peaked)
     ts = [wide[:, o:o + c] for o, c in views]
     go = gwide[:, 4:4 + Cv]
     ref64 = R.core_grads(ts, go, B, H, W, torch.float64, "cpu")
@@ -50,14 +79,28 @@ def _case(i):
     return wide.to(_dev()), views, gwide.to(_dev()), ref64, e32
 
 
-def _run(i, needs=(True, True, True, True), fill=None, forward=True, ws_fill=None):
+@functools.lru_cache(maxsize=None)
+def _canary():
+    return (torch.arange(CANARY, device=_dev()) % 251).to(torch.uint8)
+
+
+def _run(i, needs=(True, True, True, True), fill=None, forward=True, ws_fill=None, peaked=False, img=None):
     """The C ABI on strided views: outputs are slices (columns 4 .. 4 + C) of wider matrices pre-filled with GUARD (or poisoned with
-    ``fill``), the workspace is poisoned with ``fill`` (or with ``ws_fill`` alone, which leaves the guard columns checkable).  Returns [out, grad_q, grad_k, grad_v, grad_gates] as the WIDE matrices."""
+    ``fill``), the workspace is poisoned with ``fill`` (or with ``ws_fill`` alone, which leaves the guard columns checkable).  Returns [out, grad_q, grad_k, grad_v, grad_gates] as the WIDE matrices.
+    ``img``: that image of the batch alone (B = 1, every pointer moved to the image's rows).
+    The workspace has exactly the size m3d_anab_attention_workspace_bytes gives; CANARY bytes behind it hold a pattern that must
+    stand after the forward and after the backward."""
     B, H, W, Ck, Cv = CASES[i]
-    wide, views, gwide, _, _ = _case(i)
-    L, dev, n = _hip.lib(), _dev(), B * H * W
-    ptr = [wide.data_ptr() + 4 * o for o, _ in views]
+    wide, views, gwide, _, _ = _case(i, peaked)
+    L, dev = _hip.lib(), _dev()
+    row0 = 0
+    if img is not None:
+        assert 0 <= img < B
+        row0, B = img * H * W, 1
+    n = B * H * W
     cs = wide.stride(0)
+    ptr = [wide.data_ptr() + 4 * (row0 * cs + o) for o, _ in views]
+    go_ptr = gwide.data_ptr() + 4 * (row0 * gwide.stride(0) + 4)
 
     def fresh(c):
         t = torch.full((n, c + 8), GUARD, device=dev)
@@ -68,43 +111,86 @@ def _run(i, needs=(True, True, True, True), fill=None, forward=True, ws_fill=Non
     def workspace(backward):
         nbytes = L.m3d_anab_attention_workspace_bytes(B, H, W, Ck, Cv, backward)
         assert nbytes > 0
-        ws = torch.zeros(nbytes + 256, device=dev, dtype=torch.uint8)
+        ws = torch.zeros(nbytes + 256 + CANARY, device=dev, dtype=torch.uint8)
         if (fill or ws_fill) is not None:
             ws.fill_({"nan": 0xFF, "huge": 0x7F}[fill or ws_fill])        # (a byte tensor: the float pattern, not the small-integer one)
-        return ws, (ws.data_ptr() + 255) // 256 * 256, nbytes
+        base = (ws.data_ptr() + 255) // 256 * 256
+        end = base - ws.data_ptr() + nbytes
+        ws[end:end + CANARY] = _canary()
+        return ws, base, nbytes, end
+
+    def canary_stands(ws, end, what):
+        assert torch.equal(ws[end:end + CANARY], _canary()), "%s wrote behind the workspace size it asks for" % what
 
     res = [None] * 5
     if forward:
         res[0] = fresh(Cv)
-        ws, base, nbytes = workspace(0)
+        ws, base, nbytes, end = workspace(0)
         _hip.check(L.m3d_anab_attention_forward(*ptr, res[0].data_ptr() + 16, B, H, W, Ck, Cv, cs, cs, cs, cs, res[0].stride(0), base,
                                                 nbytes, _stream()))
+        canary_stands(ws, end, "m3d_anab_attention_forward")
     for j, c in enumerate((Ck, Ck, Cv, 4)):
         if needs[j]:
             res[1 + j] = fresh(c)
-    ws, base, nbytes = workspace(1)
+    ws, base, nbytes, end = workspace(1)
     gp = [t.data_ptr() + 16 if t is not None else None for t in res[1:]]
     gcs = [t.stride(0) if t is not None else 0 for t in res[1:]]
-    _hip.check(L.m3d_anab_attention_backward(*ptr, gwide.data_ptr() + 16, *gp, B, H, W, Ck, Cv, cs, cs, cs, cs, gwide.stride(0), *gcs,
+    _hip.check(L.m3d_anab_attention_backward(*ptr, go_ptr, *gp, B, H, W, Ck, Cv, cs, cs, cs, cs, gwide.stride(0), *gcs,
                                              base, nbytes, _stream()))
     torch.cuda.synchronize()
+    canary_stands(ws, end, "m3d_anab_attention_backward")
     return res
 
 
-@pytest.mark.parametrize("i", range(len(CASES)), ids=["%dx%dx%d_ck%d_cv%d" % c for c in CASES])
-def test_operator_matches_float64(i):
-    _, _, _, ref64, e32 = _case(i)
-    res = _run(i, ws_fill=("nan", "huge")[i % 2])          # forward and backward on a poisoned workspace
+def _compare(tag, i, peaked):
+    """Forward and backward of case ``i`` on a poisoned workspace against float64: guard columns, finite values, the bound."""
+    _, _, _, ref64, e32 = _case(i, peaked)
+    res = _run(i, ws_fill=("nan", "huge")[i % 2], peaked=peaked)
     errs = {}
     for name, wide_out, ref, e in zip(NAMES, res, ref64, e32):
         c = ref.shape[1]
         assert torch.equal(wide_out[:, :4], torch.full_like(wide_out[:, :4], GUARD)), name + ": guard columns in front were written"
         assert torch.equal(wide_out[:, 4 + c:], torch.full_like(wide_out[:, 4 + c:], GUARD)), name + ": guard columns behind were written"
+        assert torch.isfinite(wide_out[:, 4:4 + c]).all(), name + " is not finite"
         errs[name] = (_err(wide_out[:, 4:4 + c], ref), e)
-    print("anab_train operator", CASES[i], errs)
-    _log("anab_train_operator", {"case": list(CASES[i]), "errs": {k: list(v) for k, v in errs.items()}})
+    print("anab_train " + tag, CASES[i], errs)
+    _log("anab_train_" + tag, {"case": list(CASES[i]), "errs": {k: list(v) for k, v in errs.items()}})
     for name, (e_op, e) in errs.items():
         assert e_op <= _bound(e), "%s: err %.3e > 4 * %.3e + 2^-20" % (name, e_op, e)
+
+
+@pytest.mark.parametrize("i", range(len(CASES)), ids=IDS)
+def test_operator_matches_float64(i):
+    _compare("operator", i, False)
+
+
+@pytest.mark.parametrize("i", PEAKED, ids=[IDS[i] for i in PEAKED])
+def test_operator_matches_float64_on_peaked_rows(i):
+    """Every 37th row of q times 40: the largest logit of such a row passes ln(FLT_MAX), so the running maximum and the alpha rescale
+    of the pixel-major kernel (and of m3d_anab_attend_f32 in the forward), and exp(s - m) recomputed by the key-major kernel from the
+    stored statistics, carry the result.  Same bound as the mild cases: the float32 composition loses the same digits in dP - D."""
+    B, H, W, Ck, Cv = CASES[i]
+    wide, views, _ = _inputs(i, True)
+    q, k, _, g = (wide[:, o:o + c].double() for o, c in views)
+    top = R.anab_logits(q, k, g, B, H, W).amax(-1).flatten()
+    nbig = int((top > LN_FLT_MAX).sum())
+    print("anab_train peaked", CASES[i], "rows past ln(FLT_MAX):", nbig, "largest logit: %.1f" % top.max().item())
+    assert nbig >= 4, "only %d rows have a logit above %.2f: the case tests nothing" % (nbig, LN_FLT_MAX)
+    _compare("peaked", i, True)
+
+
+@pytest.mark.parametrize("i", BATCHED, ids=[IDS[i] for i in BATCHED])
+def test_batch_equals_its_images_bitwise(i):
+    """Every sum's order depends only on the position inside the image, so an image run alone (B = 1, pointers at its rows) gives
+    the bits the batch gives for it; a difference means a launch mixes images (a wrong image or chunk stride)."""
+    B, H, W, Ck, Cv = CASES[i]
+    hw = H * W
+    full = _run(i, ws_fill="nan")
+    for b in range(B):
+        one = _run(i, ws_fill="huge", img=b)
+        for name, wide_full, wide_one, c in zip(NAMES, full, one, (Cv, Ck, Ck, Cv, 4)):
+            assert wide_one.shape == (hw, c + 8)
+            assert torch.equal(wide_one[:, 4:4 + c], wide_full[b * hw:(b + 1) * hw, 4:4 + c]), "%s of image %d alone differs from the batch" % (name, b)
 
 
 @pytest.mark.parametrize("i", [0, 4], ids=["8x16", "16x40"])
@@ -121,13 +207,85 @@ def test_backward_is_reproducible_on_poisoned_memory(i):
                 assert torch.equal(a, b), "%s differs between launch 0 and launch %d" % (name, rep)
 
 
-def test_single_gradient_calls_equal_the_full_call():
-    ref = _run(0, forward=False)
+def _single_gradient_calls(i):
+    ref = _run(i, forward=False)
     for j in range(4):
         needs = tuple(k == j for k in range(4))
-        res = _run(0, needs=needs, fill="nan", forward=False)
-        c = _case(0)[3][1 + j].shape[1]
+        res = _run(i, needs=needs, fill="nan", forward=False)
+        c = _case(i)[3][1 + j].shape[1]
+        assert torch.isfinite(ref[1 + j][:, 4:4 + c]).all(), NAMES[1 + j]
         assert torch.equal(res[1 + j][:, 4:4 + c], ref[1 + j][:, 4:4 + c]), NAMES[1 + j]
+
+
+def test_single_gradient_calls_equal_the_full_call():
+    _single_gradient_calls(0)
+
+
+def test_single_gradient_calls_equal_the_full_call_on_the_split_value_path():
+    _single_gradient_calls(NEW0 + 2)                 # Cv = 256: two value slices per key block, B = 2, nch = 2
+
+
+# ------------------------------------------------------------------------------------ the autograd layer
+AUTOGRAD_DIMS = (2, 16, 40, 168, 128)
+# columns of the wide leaf: q at an odd float offset (not 16-byte aligned: ops copies it), k, v and gates at odd offsets too (taken
+# as they are, with the leaf's row stride of 490 floats)
+AUTOGRAD_VIEWS = ((3, 168), (177, 168), (351, 128), (483, 4))
+AUTOGRAD_WIDTH = 490
+
+
+@functools.lru_cache(maxsize=None)
+def _autograd_leaf():
+    B, H, W, Ck, Cv = AUTOGRAD_DIMS
+    g = torch.Generator().manual_seed(300)
+    n = B * H * W
+    wide = torch.randn(n, AUTOGRAD_WIDTH, generator=g)                     # guard columns: ordinary numbers nobody may use
+    for (o, c), scale in zip(AUTOGRAD_VIEWS, (0.3, 1.0, 1.0, 1.0)):
+        wide[:, o:o + c] *= scale
+    o, c = AUTOGRAD_VIEWS[3]
+    wide[:, o:o + c] = torch.sigmoid(wide[:, o:o + c])
+    return wide, torch.randn(n, Cv, generator=g), torch.randn(Cv, generator=g)
+
+
+def _autograd_grads(fn, kind, dtype, device):
+    """[out, grad of the wide leaf] of ``fn`` (ops.anab_attention or the composition) on column slices of one leaf, for one of the
+    three forms of grad_out; also the strides of the grad_out that reached ``out``."""
+    B, H, W, _, _ = AUTOGRAD_DIMS
+    wide, go, vec = (t.to(device=device, dtype=dtype) for t in _autograd_leaf())
+    wide.requires_grad_(True)
+    out = fn(*(wide[:, o:o + c] for o, c in AUTOGRAD_VIEWS), B, H, W)
+    seen = []
+    out.register_hook(lambda t: seen.append(t.stride()))
+    if kind == "contiguous":
+        out.backward(go)
+    elif kind == "sum0":
+        out.sum(0).backward(vec)
+    else:
+        out.sum().backward()
+    return [out.detach(), wide.grad], seen[0]
+
+
+@pytest.mark.parametrize("kind,strides", [("contiguous", (128, 1)), ("sum0", (0, 1)), ("sum", (0, 0))], ids=["contiguous", "sum0", "sum"])
+def test_autograd_layer_on_slices_of_one_leaf(kind, strides):
+    """ops.anab_attention on column slices of one wide leaf (q unaligned and copied, k / v / gates as they are) with the three
+    forms of grad_out autograd hands over: contiguous, (0, 1) behind .sum(0), (0, 0) behind .sum()."""
+    from m3dssd_amd.host import ops
+    got, seen = _autograd_grads(ops.anab_attention, kind, torch.float32, _dev())
+    assert seen == strides, "grad_out arrived with strides %s" % (seen,)
+    ref64, _ = _autograd_grads(R.anab_core, kind, torch.float64, "cpu")
+    t32, _ = _autograd_grads(R.anab_core, kind, torch.float32, _dev())
+    keep = torch.zeros(AUTOGRAD_WIDTH, dtype=torch.bool)
+    for o, c in AUTOGRAD_VIEWS:
+        keep[o:o + c] = True
+    assert torch.equal(got[1][:, ~keep], torch.zeros_like(got[1][:, ~keep])), "the guard columns of the leaf got a gradient"
+    pieces = lambda pair: [pair[0]] + [pair[1][:, o:o + c] for o, c in AUTOGRAD_VIEWS]
+    errs = {}
+    for name, a, r, t in zip(NAMES, pieces(got), pieces(ref64), pieces(t32)):
+        assert torch.isfinite(a).all(), name
+        errs[name] = (_err(a, r), _err(t, r))
+    print("anab_train autograd", kind, errs)
+    _log("anab_train_autograd", {"grad_out": kind, "errs": {k: list(v) for k, v in errs.items()}})
+    for name, (e_op, e) in errs.items():
+        assert e_op <= _bound(e), "%s: err %.3e > 4 * %.3e + 2^-20" % (name, e_op, e)
 
 
 # ------------------------------------------------------------------------------------ the modules in training mode
