@@ -88,7 +88,9 @@ const char *m3d_last_error(void);
  *                  m3d_head_mlp2_bf16_forward_rows, m3d_anab_attend_bf16_rows (additive);
  *                  m3d_dcn_v2_psroi_pooling_forward, m3d_dcn_v2_psroi_pooling_backward,
  *                  m3d_dcn_v2_psroi_pooling_workspace_bytes (additive);
- *                  m3d_anab_attention_forward, m3d_anab_attention_backward, m3d_anab_attention_workspace_bytes (additive). */
+ *                  m3d_anab_attention_forward, m3d_anab_attention_backward, m3d_anab_attention_workspace_bytes (additive);
+ *                  m3d_anab_attention_forward_bf16, m3d_anab_attention_backward_bf16,
+ *                  m3d_anab_attention_workspace_bytes_bf16 (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -802,6 +804,31 @@ int m3d_anab_attention_backward(const float *q, const float *k, const float *v, 
                                 float *grad_k, float *grad_v, float *grad_g, int B, int H, int W, int Ck, int Cv, int q_cs, int k_cs,
                                 int v_cs, int g_cs, int go_cs, int gq_cs, int gk_cs, int gv_cs, int gg_cs, void *workspace,
                                 long long workspace_bytes, m3d_stream_t stream);
+/* The same operator with bf16 tensors (csrc/anab_train_bf16.hip; the compute type of torch.autocast(bfloat16)): the mathematics, the
+ * bin rule, the support set, the semantics of NULL gradients, overwriting, reproducibility (no atomics, fixed summation order, the
+ * same bits whichever gradients were asked for) and independence of the workspace's contents are those of the fp32 functions above.
+ * All nine tensors are bf16 (grad_g too), strides in elements; the products run on v_mfma_f32_32x32x16_bf16 with Ck = 168 padded
+ * with zeros to 176.  Rounding points, part of the contract:
+ *   - pooling sums (a fixed order that depends only on the window), softmax statistics (m, l, D) and all accumulators are fp32;
+ *   - khat / vhat are rounded once to bf16, as MFMA operands; S and dP are never rounded;
+ *   - P is rounded once as an MFMA operand: the unnormalised exp(S - m) in the forward's P . vhat, with 1 / l applied to the fp32
+ *     accumulator, and the normalised exp(S - m) / l in the backward's P^T . dO;
+ *   - dS = P * (dP - D) (P in fp32) is rounded once, as the operand of dq and dkhat;
+ *   - dkhat / dvhat, their sums over the pixel chunks and the gather stay fp32; every output is rounded once to bf16.
+ * 1 / l is an IEEE division (correctly rounded: exactly 1/2 for l = 2); exp is expf.
+ * Alignment: q and grad_out are 16-byte aligned views with row strides that are multiples of 8 elements; k, v and g are 4-byte
+ * aligned with even row strides; outputs have no alignment rule.  Anything else is M3D_E_ARG, a workspace below
+ * m3d_anab_attention_workspace_bytes_bf16(B, H, W, Ck, Cv, backward) bytes included (-1 for an unsupported shape); the workspace is
+ * 256-byte aligned.  The forward is one pooling launch (bf16 khat, khat^T, vhat, vhat^T into the zeroed workspace) and one
+ * attention launch; the backward pools again and needs nothing of the forward's. */
+long long m3d_anab_attention_workspace_bytes_bf16(int B, int H, int W, int Ck, int Cv, int backward);
+int m3d_anab_attention_forward_bf16(const void *q, const void *k, const void *v, const void *g, void *out, int B, int H, int W, int Ck,
+                                    int Cv, int q_cs, int k_cs, int v_cs, int g_cs, int out_cs, void *workspace,
+                                    long long workspace_bytes, m3d_stream_t stream);
+int m3d_anab_attention_backward_bf16(const void *q, const void *k, const void *v, const void *g, const void *grad_out, void *grad_q,
+                                     void *grad_k, void *grad_v, void *grad_g, int B, int H, int W, int Ck, int Cv, int q_cs, int k_cs,
+                                     int v_cs, int g_cs, int go_cs, int gq_cs, int gk_cs, int gv_cs, int gg_cs, void *workspace,
+                                     long long workspace_bytes, m3d_stream_t stream);
 /* In-place softmax over the first `valid` columns of each row; columns [valid, cs) are zeroed. */
 int m3d_softmax_rows(float *x, int rows, int valid, int cs, m3d_stream_t stream);
 

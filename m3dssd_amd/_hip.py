@@ -219,6 +219,9 @@ SIGNATURES = {
     "m3d_anab_attention_workspace_bytes": (c_ll, [c_int] * 6),
     "m3d_anab_attention_forward": (c_int, [P] * 5 + [c_int] * 10 + [P, c_ll, P]),
     "m3d_anab_attention_backward": (c_int, [P] * 9 + [c_int] * 14 + [P, c_ll, P]),
+    "m3d_anab_attention_workspace_bytes_bf16": (c_ll, [c_int] * 6),
+    "m3d_anab_attention_forward_bf16": (c_int, [P] * 5 + [c_int] * 10 + [P, c_ll, P]),
+    "m3d_anab_attention_backward_bf16": (c_int, [P] * 9 + [c_int] * 14 + [P, c_ll, P]),
     "m3d_softmax_rows": (c_int, [P, c_int, c_int, c_int, P]),
     "m3d_bundle_outputs": (c_int, [P] * 7 + [c_int] * 3 + [P]),
     "m3d_decode_rows": (c_int, [P] * 9 + [c_int] * 3 + [P]),

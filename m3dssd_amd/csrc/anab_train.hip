@@ -27,10 +27,8 @@
 // overlap (load -> barrier -> multiply).
 #include <stdlib.h>
 
-#include "common.h"
+#include "anab_bins.h"
 
-#define AT_KEYS 337
-#define AT_KPAD 352                      // keys padded to the tile of 32
 #define AT_TROW (32 * 4 + 16)            // bytes per row of a transposed tile in LDS (32 tile rows + 16 pad)
 #define AT_CHUNK_TILES 16                // pixel tiles of 32 per key-major workgroup
 
@@ -288,20 +286,6 @@ __global__ __launch_bounds__(256) void anab_bwd_key_kernel(const AnabBwdArgs a)
 }
 
 // ---- the small kernels --------------------------------------------------------------------------------------------------------------
-// bin -> its scale index, grid size and position (scale-major: 1 + 16 + 64 + 256)
-__device__ __forceinline__ void at_bin_pos(const int bin, int &si, int &sz, int &bi, int &bj)
-{
-    int local;
-    if (bin < 1) { si = 0; sz = 1; local = bin; }
-    else if (bin < 17) { si = 1; sz = 4; local = bin - 1; }
-    else if (bin < 81) { si = 2; sz = 8; local = bin - 17; }
-    else { si = 3; sz = 16; local = bin - 81; }
-    bi = local / sz;
-    bj = local - bi * sz;
-}
-__host__ __device__ __forceinline__ int at_win_lo(int i, int n, int s) { return (i * n) / s; }
-__host__ __device__ __forceinline__ int at_win_hi(int i, int n, int s) { return ((i + 1) * n + s - 1) / s; }
-
 // The work items of m3d_anab_pool_partial for an H x W map, built on the device (what Engine._anab_items builds on the host): windows
 // split into chunks of ceil(H / 16) rows x ceil(W / 4) columns.  One workgroup of 384 threads, thread = bin.
 __global__ void anab_items_kernel(int *__restrict__ items, int *__restrict__ bin_scale, int *__restrict__ bin_slots,
@@ -346,30 +330,6 @@ __global__ void anab_vhat_rows_kernel(const float *__restrict__ vhatT, float *__
     const int key = (int)(bk % AT_KPAD);
     const long long b = bk / AT_KPAD;
     vhat[i] = key < AT_KEYS ? vhatT[(b * Cv + cv) * AT_KPAD + key] : 0.f;
-}
-
-// dkv [B][337][Ck + Cv] = (1 / area_bin) * sum over the pixel chunks, in chunk order, of the partials of step 3
-__global__ void anab_bwd_reduce_kernel(const float *__restrict__ partK, const float *__restrict__ partV, float *__restrict__ dkv, int nch,
-                                       int CAP, int Ck, int Cv, int H, int W, int do_k, int do_v, long long total)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int C = Ck + Cv;
-    const int c = (int)(i % C);
-    const long long bb = i / C;
-    const int bin = (int)(bb % AT_KEYS);
-    const long long b = bb / AT_KEYS;
-    const bool isk = c < Ck;
-    if (isk ? !do_k : !do_v) return;
-    float acc = 0.f;
-    for (int ch = 0; ch < nch; ++ch) {
-        const size_t row = ((size_t)b * nch + ch) * AT_KPAD + bin;
-        acc += isk ? partK[row * CAP + c] : partV[row * Cv + (c - Ck)];
-    }
-    int si, sz, bi, bj;
-    at_bin_pos(bin, si, sz, bi, bj);
-    const int area = (at_win_hi(bi, H, sz) - at_win_lo(bi, H, sz)) * (at_win_hi(bj, W, sz) - at_win_lo(bj, W, sz));
-    dkv[i] = acc * (1.0f / (float)area);
 }
 
 struct AnabGatherArgs {

@@ -16,6 +16,10 @@ class PAPAModule(nn.Module):
 
 
 class ANAB(nn.Module):
+    # opt-in (train.set_bf16_attention): under torch.autocast("cuda", dtype=torch.bfloat16) the training form runs the bf16 attention
+    # operator (ops.anab_attention_bf16) and returns bfloat16; off, it is the float32 operator whatever autocast says
+    bf16_attention = False
+
     def __init__(self, ch, num_psp, psp_size=[1, 4, 8, 16], with_atten=True):
         super().__init__()
         if not with_atten or tuple(psp_size) != (1, 4, 8, 16):

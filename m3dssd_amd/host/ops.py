@@ -372,6 +372,107 @@ def anab_attention(q, k, v, gates, B, H, W):
     return _ANABAttention.apply(q, k, v, gates, B, H, W)
 
 
+def _anab_rows_bf16(name, t, what, rows):
+    if t.dtype != torch.bfloat16:
+        raise RuntimeError("%s: %s is %s; only bfloat16 is supported" % (name, what, t.dtype))
+    if t.dim() != 2 or t.shape[0] != rows:
+        raise RuntimeError("%s: %s must be a row matrix [B*H*W = %d, C] (got %s)" % (name, what, rows, tuple(t.shape)))
+    return t
+
+
+def _anab_prepare_bf16(name, q, k, v, gates, B, H, W):
+    """The rules of _anab_prepare for bfloat16 rows, then the alignment contract of the bf16 kernels: q through 16-byte loads (row
+    stride a multiple of 8 elements), k / v / gates through 4-byte loads (even offset and row stride); what does not fit is copied
+    once."""
+    _require_cuda(q, k, v, gates)
+    rows = B * H * W
+    q, k, v, gates = (_anab_rows_bf16(name, t, what, rows) for t, what in ((q, "q"), (k, "k"), (v, "v"), (gates, "gates")))
+    ck, cv = q.shape[1], v.shape[1]
+    if k.shape[1] != ck or gates.shape[1] != 4:
+        raise RuntimeError("%s: q and k need the same channel count and gates 4 channels (got %d, %d, %d)"
+                           % (name, ck, k.shape[1], gates.shape[1]))
+    if (H * W) % 128:
+        raise RuntimeError("%s: H*W must be a multiple of 128 (HW %% 128 == 0; got %dx%d)" % (name, H, W))
+    if (ck, cv) not in _ANAB_PAIRS:
+        raise RuntimeError("%s: (Ck, Cv) must be one of %s (got (%d, %d))" % (name, _ANAB_PAIRS, ck, cv))
+    return ck, cv, _anab_aligned_bf16(q, 16, 8), tuple(_anab_aligned_bf16(t, 4, 2) for t in (k, v, gates))
+
+
+def _anab_aligned_bf16(t, align, stride_of):
+    if t.data_ptr() % align == 0 and t.stride(0) % stride_of == 0 and t.stride(0) >= t.shape[1] and t.stride(1) == 1:
+        return t
+    return t.contiguous()
+
+
+def anab_attention_forward_bf16(q, k, v, gates, B, H, W):
+    """m3d_anab_attention_forward_bf16: anab_attention_forward on bfloat16 rows, bfloat16 out [B*H*W, Cv]."""
+    name = "anab_attention_forward_bf16"
+    ck, cv, q, (k, v, gates) = _anab_prepare_bf16(name, q, k, v, gates, B, H, W)
+    L = _hip.lib()
+    nbytes = L.m3d_anab_attention_workspace_bytes_bf16(B, H, W, ck, cv, 0)
+    if nbytes < 0:
+        raise RuntimeError("%s: unsupported shape" % name)
+    out = torch.empty(B * H * W, cv, device=q.device, dtype=torch.bfloat16)
+    ws, base = _workspace(nbytes, q.device)
+    with torch.cuda.device(q.device):
+        _hip.check(L.m3d_anab_attention_forward_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), out.data_ptr(), B, H,
+                                                     W, ck, cv, q.stride(0), k.stride(0), v.stride(0), gates.stride(0), cv, base,
+                                                     nbytes, _stream()))
+    return out
+
+
+def anab_attention_backward_bf16(q, k, v, gates, grad_out, B, H, W, needs=(True, True, True, True)):
+    """m3d_anab_attention_backward_bf16: (grad_q, grad_k, grad_v, grad_gates) in bfloat16, freshly written and contiguous; an entry
+    of ``needs`` that is False gives None and skips the work only that gradient needs."""
+    name = "anab_attention_backward_bf16"
+    _require_cuda(grad_out)
+    ck, cv, q, (k, v, gates) = _anab_prepare_bf16(name, q, k, v, gates, B, H, W)
+    if grad_out.dtype != torch.bfloat16 or tuple(grad_out.shape) != (B * H * W, cv):
+        raise RuntimeError("%s: grad_out must be bfloat16 [B*H*W, Cv]" % name)
+    L = _hip.lib()
+    grad_out = _anab_aligned_bf16(grad_out, 16, 8)
+    nbytes = L.m3d_anab_attention_workspace_bytes_bf16(B, H, W, ck, cv, 1)
+    if nbytes < 0:
+        raise RuntimeError("%s: unsupported shape" % name)
+    grads = [torch.empty(B * H * W, c, device=q.device, dtype=torch.bfloat16) if need else None
+             for c, need in zip((ck, ck, cv, 4), needs)]
+    ptrs = [g.data_ptr() if g is not None else None for g in grads]
+    ws, base = _workspace(nbytes, q.device)
+    with torch.cuda.device(q.device):
+        _hip.check(L.m3d_anab_attention_backward_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), grad_out.data_ptr(),
+                                                      *ptrs, B, H, W, ck, cv, q.stride(0), k.stride(0), v.stride(0), gates.stride(0),
+                                                      grad_out.stride(0), ck, ck, cv, 4, base, nbytes, _stream()))
+    return tuple(grads)
+
+
+class _ANABAttentionBf16(torch.autograd.Function):
+    # (no custom_fwd cast: the operands are bfloat16 already, inside an autocast region or outside one)
+    @staticmethod
+    def forward(ctx, q, k, v, gates, B, H, W):
+        ctx.dims = (B, H, W)
+        ctx.save_for_backward(q, k, v, gates)
+        return anab_attention_forward_bf16(q, k, v, gates, B, H, W)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, gates = ctx.saved_tensors
+        grads = anab_attention_backward_bf16(q, k, v, gates, grad_out, *ctx.dims, needs=tuple(ctx.needs_input_grad[:4]))
+        return grads + (None, None, None)
+
+
+def anab_attention_bf16(q, k, v, gates, B, H, W):
+    """``anab_attention`` in bfloat16: bfloat16 row matrices in (column slices are taken as they are where they meet the alignment
+    of the kernels, else copied once), bfloat16 out, bfloat16 gradients; m3d_anab_attention_forward_bf16 with
+    m3d_anab_attention_backward_bf16 behind it, inside or outside an autocast region, never through float32.  Any operand that is not
+    bfloat16 raises RuntimeError; no torch fallback."""
+    _require_cuda(q, k, v, gates)
+    for t, what in ((q, "q"), (k, "k"), (v, "v"), (gates, "gates")):
+        if t.dtype != torch.bfloat16:
+            raise RuntimeError("anab_attention_bf16: %s is %s; only bfloat16 is supported" % (what, t.dtype))
+    return _ANABAttentionBf16.apply(q, k, v, gates, B, H, W)
+
+
 def rpn_targets(cls, prob, anchors, conf_vec, gt_table, feat_size):
     """compute_targets (lib/rpn_util.py:430-532) for a whole batch on the device: m3d_rpn_targets.  ``anchors`` float64 device
     [A, 9], ``conf_vec`` from ``host.loss.pack_conf``, ``gt_table`` from ``host.loss.pack_gts``; see host/loss.py."""

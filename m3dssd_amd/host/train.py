@@ -19,12 +19,33 @@ def anab_forward(mod, x):
     ck = mod.key_ch
     rows = x.permute(0, 2, 3, 1).reshape(B * H * W, C)
     # one matmul with the stacked query | key | value | spatial weights: the projection gradients are autograd's
-    wall = torch.cat([mod.query_conv.weight, mod.key_conv.weight, mod.value_conv.weight, mod.spatial_conv.weight], 0)
+    ws = [mod.query_conv.weight, mod.key_conv.weight, mod.value_conv.weight, mod.spatial_conv.weight]
+    # opt-in (set_bf16_attention) and only under bfloat16 autocast on the device: the bf16 operator on the bf16 rows of the matmul
+    bf16 = mod.bf16_attention and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+    if bf16:
+        # zero rows behind the stacked weights: the row stride of qkvs becomes a multiple of 8 elements, so q is taken as it is
+        ws.append(ws[0].new_zeros((-(2 * ck + C + 4)) % 8, C, 1, 1))
+    wall = torch.cat(ws, 0)
     qkvs = rows @ wall.reshape(wall.shape[0], C).t()
     q, k, v = qkvs[:, :ck], qkvs[:, ck:2 * ck], qkvs[:, 2 * ck:2 * ck + C]
-    gates = torch.sigmoid(qkvs[:, 2 * ck + C:])
-    out = ops.anab_attention(q, k, v, gates, B, H, W) + rows
+    gates = torch.sigmoid(qkvs[:, 2 * ck + C:2 * ck + C + 4])
+    if bf16 and qkvs.dtype == torch.bfloat16:
+        out = (ops.anab_attention_bf16(q, k, v, gates, B, H, W) + rows).to(torch.bfloat16)
+    else:
+        out = ops.anab_attention(q, k, v, gates, B, H, W) + rows
     return out.reshape(B, H, W, C).permute(0, 3, 1, 2).contiguous()
+
+
+def set_bf16_attention(net, flag=True):
+    """Turns the bf16 attention operator (``ops.anab_attention_bf16``) on or off for every ANAB below ``net``; it is taken only under
+    ``torch.autocast("cuda", dtype=torch.bfloat16)``.  Returns the number of blocks set."""
+    from .attention import ANAB
+    n = 0
+    for m in net.modules():
+        if isinstance(m, ANAB):
+            m.bf16_attention = bool(flag)
+            n += 1
+    return n
 
 
 # ---- shape_align / center_align (model/module/feturealign_mgpu.py:48-99, 153-208 with k = 1) ------------------------------------------

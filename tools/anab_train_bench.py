@@ -9,7 +9,12 @@ HIP events around one forward + backward, `--warmup` untimed iterations, `--reps
 times one full training iteration (anab_fullalign, DLA-34, B = 2 at 384x1280: forward, RPN_3D_loss, backward, SGD step) for the
 record.
 
-usage: python tools/anab_train_bench.py [--reps 50] [--warmup 5] [--batch 8] [--iteration]     (one JSON line per measurement)"""
+With `--dtype bf16` the operator leg is ``ops.anab_attention_bf16`` against the parent path on the same bf16 tensors
+(``ops.anab_attention`` under torch.autocast(bfloat16)), with the interquartile range of each leg, and `--iteration` runs under
+autocast with ``ANAB.bf16_attention`` off and on.
+
+usage: python tools/anab_train_bench.py [--reps 50] [--warmup 5] [--batch 8] [--dtype f32|bf16] [--iteration]
+(one JSON line per measurement)"""
 import argparse
 import json
 import os
@@ -49,7 +54,7 @@ def timed(fn, warmup, reps):
         e1.synchronize()
         ts.append(e0.elapsed_time(e1))
     ts.sort()
-    return {"median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4)}
+    return {"median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4), "iqr": round(ts[(3 * len(ts)) // 4] - ts[len(ts) // 4], 4)}
 
 
 def peak_mb(fn):
@@ -85,7 +90,40 @@ def bench_operator(a, dev, ck, cv, H=48, W=160):
     print(json.dumps(res), flush=True)
 
 
-def bench_iteration(a, dev):
+def bench_operator_bf16(a, dev, ck, cv, H=48, W=160):
+    """``ops.anab_attention_bf16`` against the parent path on the same bf16 tensors in the same process: ``ops.anab_attention`` under
+    torch.autocast(bfloat16), whose custom_fwd casts the four slices to float32 and hands a float32 activation back.  The rows are
+    the module's: q | k | v | gates as column slices of one bf16 matrix padded to a row stride that is a multiple of 8."""
+    B, n = a.batch, a.batch * H * W
+    g = torch.Generator().manual_seed(1)
+    width = (2 * ck + cv + 4 + 7) // 8 * 8
+    wide = torch.randn(n, width, generator=g)
+    wide[:, :ck] *= 0.3
+    wide[:, 2 * ck + cv:] = torch.sigmoid(wide[:, 2 * ck + cv:])
+    wide = wide.to(dev).bfloat16()
+    go = torch.randn(n, cv, generator=g).to(dev)
+    go16 = go.bfloat16()
+    leaves = [wide[:, :ck], wide[:, ck:2 * ck], wide[:, 2 * ck:2 * ck + cv], wide[:, 2 * ck + cv:2 * ck + cv + 4]]
+
+    def step16():
+        ts = [t.detach().requires_grad_(True) for t in leaves]
+        ops.anab_attention_bf16(*ts, B, H, W).backward(go16)
+
+    def step_parent():
+        ts = [t.detach().requires_grad_(True) for t in leaves]
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            out = ops.anab_attention(*ts, B, H, W)
+        out.backward(go)
+
+    res = {"op": "anab_attention_bf16 forward+backward", "batch": B, "H": H, "W": W, "Ck": ck, "Cv": cv, "reps": a.reps}
+    res["hip_bf16_ms"] = timed(step16, a.warmup, a.reps)
+    res["parent_autocast_ms"] = timed(step_parent, a.warmup, a.reps)
+    res["hip_bf16_peak_mb"] = peak_mb(step16)
+    res["parent_autocast_peak_mb"] = peak_mb(step_parent)
+    print(json.dumps(res), flush=True)
+
+
+def bench_iteration(a, dev, autocast=False):
     from m3dssd_amd import synth
     from m3dssd_amd.config import Conf
     from model.M3d_inference_align import build
@@ -116,16 +154,22 @@ def bench_iteration(a, dev):
     opt = torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9)
 
     def step():
-        cls, prob, b2, b3, fs = net(x)
-        loss, _ = crit(cls, prob, b2, b3, imobjs, fs)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            cls, prob, b2, b3, fs = net(x)
+        loss, _ = crit(cls.float(), prob.float(), b2.float(), b3.float(), imobjs, fs)
         opt.zero_grad()
         loss.backward()
         opt.step()
 
-    res = {"op": "training iteration anab_fullalign dla34", "batch": B, "crop": list(crop), "reps": min(a.reps, 10)}
-    res["iteration_ms"] = timed(step, 2, min(a.reps, 10))
-    res["peak_mb"] = peak_mb(step)
-    print(json.dumps(res), flush=True)
+    from m3dssd_amd.host import train
+    for flag in ((False, True) if autocast else (False,)):
+        train.set_bf16_attention(net, flag)
+        res = {"op": "training iteration anab_fullalign dla34", "batch": B, "crop": list(crop), "reps": min(a.reps, 10)}
+        if autocast:
+            res.update(autocast="bfloat16", bf16_attention=flag)
+        res["iteration_ms"] = timed(step, 2, min(a.reps, 10))
+        res["peak_mb"] = peak_mb(step)
+        print(json.dumps(res), flush=True)
 
 
 def main():
@@ -134,14 +178,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iteration", action="store_true", help="also time one full training iteration (B = 2, 384x1280)")
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
+                    help="bf16: ops.anab_attention_bf16 against ops.anab_attention under autocast; --iteration then runs under autocast "
+                         "with ANAB.bf16_attention off and on")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("anab_train_bench: no ROCm device")
     dev = torch.device("cuda:0")
     for ck, cv in ((168, 128), (168, 256)):
-        bench_operator(a, dev, ck, cv)
+        (bench_operator_bf16 if a.dtype == "bf16" else bench_operator)(a, dev, ck, cv)
     if a.iteration:
-        bench_iteration(a, dev)
+        bench_iteration(a, dev, autocast=a.dtype == "bf16")
 
 
 if __name__ == "__main__":
