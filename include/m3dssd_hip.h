@@ -804,7 +804,7 @@ int m3d_anab_attention_backward(const float *q, const float *k, const float *v, 
                                 float *grad_k, float *grad_v, float *grad_g, int B, int H, int W, int Ck, int Cv, int q_cs, int k_cs,
                                 int v_cs, int g_cs, int go_cs, int gq_cs, int gk_cs, int gv_cs, int gg_cs, void *workspace,
                                 long long workspace_bytes, m3d_stream_t stream);
-/* The same operator with bf16 tensors (csrc/anab_train_bf16.hip; the compute type of torch.autocast(bfloat16)): the mathematics, the
+/* The same operator with bf16 tensors (csrc/anab_train.hip on its bf16 element traits; the compute type of torch.autocast(bfloat16)): the mathematics, the
  * bin rule, the support set, the semantics of NULL gradients, overwriting, reproducibility (no atomics, fixed summation order, the
  * same bits whichever gradients were asked for) and independence of the workspace's contents are those of the fp32 functions above.
  * All nine tensors are bf16 (grad_g too), strides in elements; the products run on v_mfma_f32_32x32x16_bf16 with Ck = 168 padded

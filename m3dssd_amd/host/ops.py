@@ -3,6 +3,7 @@
 These are what the standalone modules (DCNv2, DCN, ...) call.  The whole-network path
 (``RPN.forward``) does not go through here -- it runs the NHWC engine (m3dssd_amd/engine.py).
 """
+import collections
 import ctypes
 
 import torch
@@ -270,96 +271,142 @@ def psroi_pooling(data, rois, offset, no_trans, spatial_scale, output_dim, group
 
 _ANAB_PAIRS = ((64, 128), (128, 128), (168, 128), (168, 256))
 
-
-def _anab_rows(name, t, what, rows):
-    """A row matrix [rows, C] that may be a column slice of a wider one: unit stride inside a row -> (C, row stride)."""
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s: %s is %s; only float32 is supported" % (name, what, t.dtype))
-    if t.dim() != 2 or t.shape[0] != rows:
-        raise RuntimeError("%s: %s must be a row matrix [B*H*W = %d, C] (got %s)" % (name, what, rows, tuple(t.shape)))
-    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        raise RuntimeError("%s: %s must have unit stride inside a row (a column slice of a row-major matrix)" % (name, what))
-    return t.shape[1], t.stride(0)
+# What differs between the two compute types of the ANAB training operator.  ``q_align`` / ``kvg_align``: (bytes, row-stride multiple
+# in elements) that a view must meet to be handed over as it is, else it is copied once.  ``kvg_align`` None: k / v / gates are
+# handed over untouched with whatever row stride they have, and a non-unit inner stride of any operand raises.
+_AnabType = collections.namedtuple("_AnabType", "dtype dtype_name query forward backward q_align kvg_align")
+_ANAB_F32 = _AnabType(torch.float32, "float32", "m3d_anab_attention_workspace_bytes", "m3d_anab_attention_forward",
+                      "m3d_anab_attention_backward", (16, 4), None)
+_ANAB_BF16 = _AnabType(torch.bfloat16, "bfloat16", "m3d_anab_attention_workspace_bytes_bf16", "m3d_anab_attention_forward_bf16",
+                       "m3d_anab_attention_backward_bf16", (16, 8), (4, 2))
 
 
-def _anab_prepare(name, q, k, v, gates, B, H, W):
-    _require_cuda(q, k, v, gates)
-    rows = B * H * W
-    (ck, q_cs), (ck2, k_cs), (cv, v_cs), (ng, g_cs) = (_anab_rows(name, t, what, rows) for t, what in
-                                                      ((q, "q"), (k, "k"), (v, "v"), (gates, "gates")))
-    if ck2 != ck or ng != 4:
-        raise RuntimeError("%s: q and k need the same channel count and gates 4 channels (got %d, %d, %d)" % (name, ck, ck2, ng))
-    if (H * W) % 128:
-        raise RuntimeError("%s: H*W must be a multiple of 128 (HW %% 128 == 0; got %dx%d)" % (name, H, W))
-    if (ck, cv) not in _ANAB_PAIRS:
-        raise RuntimeError("%s: (Ck, Cv) must be one of %s (got (%d, %d))" % (name, _ANAB_PAIRS, ck, cv))
-    return ck, cv, (q_cs, k_cs, v_cs, g_cs)
-
-
-def _anab_aligned(t):
-    """q / grad_out go through 16-byte loads: an unaligned view or an odd row stride is copied once, and so is a view whose rows
-    overlap (row stride below the channel count: the expanded grad_out that autograd hands over behind ``.sum(0)``)."""
-    if t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.stride(1) == 1:
+def _anab_aligned(t, align=_ANAB_F32.q_align):
+    """q / grad_out go through 16-byte loads (bf16 k / v / gates through 4-byte loads): an unaligned view or an odd row stride is
+    copied once, and so is a view whose rows overlap (row stride below the channel count: the expanded grad_out that autograd hands
+    over behind ``.sum(0)``)."""
+    nbytes, stride_of = align
+    if t.data_ptr() % nbytes == 0 and t.stride(0) % stride_of == 0 and t.stride(0) >= t.shape[1] and t.stride(1) == 1:
         return t
     return t.contiguous()
 
 
-def anab_attention_forward(q, k, v, gates, B, H, W):
-    """m3d_anab_attention_forward: out [B*H*W, Cv] = softmax_keys(q . khat^T) . vhat with the gated pyramid pooling of ANAB."""
-    name = "anab_attention_forward"
-    ck, cv, (q_cs, k_cs, v_cs, g_cs) = _anab_prepare(name, q, k, v, gates, B, H, W)
+def _anab_prepare(name, q, k, v, gates, B, H, W, ty=_ANAB_F32):
+    """The shape and type rules of both calls, then the alignment contract of the kernels -> (Ck, Cv, q, k, v, gates).  The operands
+    are row matrices [rows, C] that may be column slices of a wider one."""
+    _require_cuda(q, k, v, gates)
+    rows = B * H * W
+    for t, what in ((q, "q"), (k, "k"), (v, "v"), (gates, "gates")):
+        if t.dtype != ty.dtype:
+            raise RuntimeError("%s: %s is %s; only %s is supported" % (name, what, t.dtype, ty.dtype_name))
+        if t.dim() != 2 or t.shape[0] != rows:
+            raise RuntimeError("%s: %s must be a row matrix [B*H*W = %d, C] (got %s)" % (name, what, rows, tuple(t.shape)))
+        if ty.kvg_align is None and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+            raise RuntimeError("%s: %s must have unit stride inside a row (a column slice of a row-major matrix)" % (name, what))
+    ck, cv = q.shape[1], v.shape[1]
+    if k.shape[1] != ck or gates.shape[1] != 4:
+        raise RuntimeError("%s: q and k need the same channel count and gates 4 channels (got %d, %d, %d)"
+                           % (name, ck, k.shape[1], gates.shape[1]))
+    if (H * W) % 128:
+        raise RuntimeError("%s: H*W must be a multiple of 128 (HW %% 128 == 0; got %dx%d)" % (name, H, W))
+    if (ck, cv) not in _ANAB_PAIRS:
+        raise RuntimeError("%s: (Ck, Cv) must be one of %s (got (%d, %d))" % (name, _ANAB_PAIRS, ck, cv))
+    if ty.kvg_align is not None:
+        k, v, gates = (_anab_aligned(t, ty.kvg_align) for t in (k, v, gates))
+    return ck, cv, _anab_aligned(q, ty.q_align), k, v, gates
+
+
+def _anab_forward(ty, q, k, v, gates, B, H, W):
+    name = ty.forward[4:]
+    ck, cv, q, k, v, gates = _anab_prepare(name, q, k, v, gates, B, H, W, ty)
     L = _hip.lib()
-    q = _anab_aligned(q)
-    nbytes = L.m3d_anab_attention_workspace_bytes(B, H, W, ck, cv, 0)
+    nbytes = getattr(L, ty.query)(B, H, W, ck, cv, 0)
     if nbytes < 0:
         raise RuntimeError("%s: unsupported shape" % name)
-    out = torch.empty(B * H * W, cv, device=q.device, dtype=torch.float32)
+    out = torch.empty(B * H * W, cv, device=q.device, dtype=ty.dtype)
     ws, base = _workspace(nbytes, q.device)
     with torch.cuda.device(q.device):
-        _hip.check(L.m3d_anab_attention_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), out.data_ptr(), B, H, W,
-                                                ck, cv, q.stride(0), k_cs, v_cs, g_cs, cv, base, nbytes, _stream()))
+        _hip.check(getattr(L, ty.forward)(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), out.data_ptr(), B, H, W, ck, cv,
+                                          q.stride(0), k.stride(0), v.stride(0), gates.stride(0), cv, base, nbytes, _stream()))
     return out
+
+
+def _anab_backward(ty, q, k, v, gates, grad_out, B, H, W, needs):
+    name = ty.backward[4:]
+    _require_cuda(grad_out)
+    ck, cv, q, k, v, gates = _anab_prepare(name, q, k, v, gates, B, H, W, ty)
+    if grad_out.dtype != ty.dtype or tuple(grad_out.shape) != (B * H * W, cv):
+        raise RuntimeError("%s: grad_out must be %s [B*H*W, Cv]" % (name, ty.dtype_name))
+    L = _hip.lib()
+    grad_out = _anab_aligned(grad_out, ty.q_align)
+    nbytes = getattr(L, ty.query)(B, H, W, ck, cv, 1)
+    if nbytes < 0:
+        raise RuntimeError("%s: unsupported shape" % name)
+    grads = [torch.empty(B * H * W, c, device=q.device, dtype=ty.dtype) if need else None for c, need in zip((ck, ck, cv, 4), needs)]
+    ptrs = [g.data_ptr() if g is not None else None for g in grads]
+    ws, base = _workspace(nbytes, q.device)
+    with torch.cuda.device(q.device):
+        _hip.check(getattr(L, ty.backward)(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), grad_out.data_ptr(), *ptrs, B, H,
+                                           W, ck, cv, q.stride(0), k.stride(0), v.stride(0), gates.stride(0), grad_out.stride(0), ck,
+                                           ck, cv, 4, base, nbytes, _stream()))
+    return tuple(grads)
+
+
+def anab_attention_forward(q, k, v, gates, B, H, W):
+    """m3d_anab_attention_forward: out [B*H*W, Cv] = softmax_keys(q . khat^T) . vhat with the gated pyramid pooling of ANAB."""
+    return _anab_forward(_ANAB_F32, q, k, v, gates, B, H, W)
 
 
 def anab_attention_backward(q, k, v, gates, grad_out, B, H, W, needs=(True, True, True, True)):
     """m3d_anab_attention_backward: (grad_q, grad_k, grad_v, grad_gates), freshly written and contiguous; an entry of ``needs`` that
     is False gives None and skips the work only that gradient needs."""
-    name = "anab_attention_backward"
-    _require_cuda(grad_out)
-    ck, cv, (q_cs, k_cs, v_cs, g_cs) = _anab_prepare(name, q, k, v, gates, B, H, W)
-    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (B * H * W, cv):
-        raise RuntimeError("%s: grad_out must be float32 [B*H*W, Cv]" % name)
-    L = _hip.lib()
-    q, grad_out = _anab_aligned(q), _anab_aligned(grad_out)
-    nbytes = L.m3d_anab_attention_workspace_bytes(B, H, W, ck, cv, 1)
-    if nbytes < 0:
-        raise RuntimeError("%s: unsupported shape" % name)
-    grads = [torch.empty(B * H * W, c, device=q.device, dtype=torch.float32) if need else None
-             for c, need in zip((ck, ck, cv, 4), needs)]
-    ptrs = [g.data_ptr() if g is not None else None for g in grads]
-    ws, base = _workspace(nbytes, q.device)
-    with torch.cuda.device(q.device):
-        _hip.check(L.m3d_anab_attention_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), grad_out.data_ptr(),
-                                                 *ptrs, B, H, W, ck, cv, q.stride(0), k_cs, v_cs, g_cs, grad_out.stride(0), ck, ck, cv,
-                                                 4, base, nbytes, _stream()))
-    return tuple(grads)
+    return _anab_backward(_ANAB_F32, q, k, v, gates, grad_out, B, H, W, needs)
+
+
+def anab_attention_forward_bf16(q, k, v, gates, B, H, W):
+    """m3d_anab_attention_forward_bf16: anab_attention_forward on bfloat16 rows, bfloat16 out [B*H*W, Cv]."""
+    return _anab_forward(_ANAB_BF16, q, k, v, gates, B, H, W)
+
+
+def anab_attention_backward_bf16(q, k, v, gates, grad_out, B, H, W, needs=(True, True, True, True)):
+    """m3d_anab_attention_backward_bf16: (grad_q, grad_k, grad_v, grad_gates) in bfloat16, freshly written and contiguous; an entry
+    of ``needs`` that is False gives None and skips the work only that gradient needs."""
+    return _anab_backward(_ANAB_BF16, q, k, v, gates, grad_out, B, H, W, needs)
+
+
+def _anab_fn_forward(ctx, ty, q, k, v, gates, B, H, W):
+    ctx.dims = (B, H, W)
+    ctx.save_for_backward(q, k, v, gates)
+    return _anab_forward(ty, q, k, v, gates, B, H, W)
+
+
+def _anab_fn_backward(ctx, ty, grad_out):
+    return _anab_backward(ty, *ctx.saved_tensors, grad_out, *ctx.dims, needs=tuple(ctx.needs_input_grad[:4])) + (None, None, None)
 
 
 class _ANABAttention(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, q, k, v, gates, B, H, W):
-        ctx.dims = (B, H, W)
-        ctx.save_for_backward(q, k, v, gates)
-        return anab_attention_forward(q, k, v, gates, B, H, W)
+        return _anab_fn_forward(ctx, _ANAB_F32, q, k, v, gates, B, H, W)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        q, k, v, gates = ctx.saved_tensors
-        grads = anab_attention_backward(q, k, v, gates, grad_out, *ctx.dims, needs=tuple(ctx.needs_input_grad[:4]))
-        return grads + (None, None, None)
+        return _anab_fn_backward(ctx, _ANAB_F32, grad_out)
+
+
+class _ANABAttentionBf16(torch.autograd.Function):
+    # (no custom_fwd cast: the operands are bfloat16 already, inside an autocast region or outside one)
+    @staticmethod
+    def forward(ctx, q, k, v, gates, B, H, W):
+        return _anab_fn_forward(ctx, _ANAB_BF16, q, k, v, gates, B, H, W)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        return _anab_fn_backward(ctx, _ANAB_BF16, grad_out)
 
 
 def anab_attention(q, k, v, gates, B, H, W):
@@ -370,95 +417,6 @@ def anab_attention(q, k, v, gates, B, H, W):
     _require_cuda(q, k, v, gates)
     # (the shape and type rules are checked by anab_attention_forward, behind the float32 cast of custom_fwd under autocast)
     return _ANABAttention.apply(q, k, v, gates, B, H, W)
-
-
-def _anab_rows_bf16(name, t, what, rows):
-    if t.dtype != torch.bfloat16:
-        raise RuntimeError("%s: %s is %s; only bfloat16 is supported" % (name, what, t.dtype))
-    if t.dim() != 2 or t.shape[0] != rows:
-        raise RuntimeError("%s: %s must be a row matrix [B*H*W = %d, C] (got %s)" % (name, what, rows, tuple(t.shape)))
-    return t
-
-
-def _anab_prepare_bf16(name, q, k, v, gates, B, H, W):
-    """The rules of _anab_prepare for bfloat16 rows, then the alignment contract of the bf16 kernels: q through 16-byte loads (row
-    stride a multiple of 8 elements), k / v / gates through 4-byte loads (even offset and row stride); what does not fit is copied
-    once."""
-    _require_cuda(q, k, v, gates)
-    rows = B * H * W
-    q, k, v, gates = (_anab_rows_bf16(name, t, what, rows) for t, what in ((q, "q"), (k, "k"), (v, "v"), (gates, "gates")))
-    ck, cv = q.shape[1], v.shape[1]
-    if k.shape[1] != ck or gates.shape[1] != 4:
-        raise RuntimeError("%s: q and k need the same channel count and gates 4 channels (got %d, %d, %d)"
-                           % (name, ck, k.shape[1], gates.shape[1]))
-    if (H * W) % 128:
-        raise RuntimeError("%s: H*W must be a multiple of 128 (HW %% 128 == 0; got %dx%d)" % (name, H, W))
-    if (ck, cv) not in _ANAB_PAIRS:
-        raise RuntimeError("%s: (Ck, Cv) must be one of %s (got (%d, %d))" % (name, _ANAB_PAIRS, ck, cv))
-    return ck, cv, _anab_aligned_bf16(q, 16, 8), tuple(_anab_aligned_bf16(t, 4, 2) for t in (k, v, gates))
-
-
-def _anab_aligned_bf16(t, align, stride_of):
-    if t.data_ptr() % align == 0 and t.stride(0) % stride_of == 0 and t.stride(0) >= t.shape[1] and t.stride(1) == 1:
-        return t
-    return t.contiguous()
-
-
-def anab_attention_forward_bf16(q, k, v, gates, B, H, W):
-    """m3d_anab_attention_forward_bf16: anab_attention_forward on bfloat16 rows, bfloat16 out [B*H*W, Cv]."""
-    name = "anab_attention_forward_bf16"
-    ck, cv, q, (k, v, gates) = _anab_prepare_bf16(name, q, k, v, gates, B, H, W)
-    L = _hip.lib()
-    nbytes = L.m3d_anab_attention_workspace_bytes_bf16(B, H, W, ck, cv, 0)
-    if nbytes < 0:
-        raise RuntimeError("%s: unsupported shape" % name)
-    out = torch.empty(B * H * W, cv, device=q.device, dtype=torch.bfloat16)
-    ws, base = _workspace(nbytes, q.device)
-    with torch.cuda.device(q.device):
-        _hip.check(L.m3d_anab_attention_forward_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), out.data_ptr(), B, H,
-                                                     W, ck, cv, q.stride(0), k.stride(0), v.stride(0), gates.stride(0), cv, base,
-                                                     nbytes, _stream()))
-    return out
-
-
-def anab_attention_backward_bf16(q, k, v, gates, grad_out, B, H, W, needs=(True, True, True, True)):
-    """m3d_anab_attention_backward_bf16: (grad_q, grad_k, grad_v, grad_gates) in bfloat16, freshly written and contiguous; an entry
-    of ``needs`` that is False gives None and skips the work only that gradient needs."""
-    name = "anab_attention_backward_bf16"
-    _require_cuda(grad_out)
-    ck, cv, q, (k, v, gates) = _anab_prepare_bf16(name, q, k, v, gates, B, H, W)
-    if grad_out.dtype != torch.bfloat16 or tuple(grad_out.shape) != (B * H * W, cv):
-        raise RuntimeError("%s: grad_out must be bfloat16 [B*H*W, Cv]" % name)
-    L = _hip.lib()
-    grad_out = _anab_aligned_bf16(grad_out, 16, 8)
-    nbytes = L.m3d_anab_attention_workspace_bytes_bf16(B, H, W, ck, cv, 1)
-    if nbytes < 0:
-        raise RuntimeError("%s: unsupported shape" % name)
-    grads = [torch.empty(B * H * W, c, device=q.device, dtype=torch.bfloat16) if need else None
-             for c, need in zip((ck, ck, cv, 4), needs)]
-    ptrs = [g.data_ptr() if g is not None else None for g in grads]
-    ws, base = _workspace(nbytes, q.device)
-    with torch.cuda.device(q.device):
-        _hip.check(L.m3d_anab_attention_backward_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), gates.data_ptr(), grad_out.data_ptr(),
-                                                      *ptrs, B, H, W, ck, cv, q.stride(0), k.stride(0), v.stride(0), gates.stride(0),
-                                                      grad_out.stride(0), ck, ck, cv, 4, base, nbytes, _stream()))
-    return tuple(grads)
-
-
-class _ANABAttentionBf16(torch.autograd.Function):
-    # (no custom_fwd cast: the operands are bfloat16 already, inside an autocast region or outside one)
-    @staticmethod
-    def forward(ctx, q, k, v, gates, B, H, W):
-        ctx.dims = (B, H, W)
-        ctx.save_for_backward(q, k, v, gates)
-        return anab_attention_forward_bf16(q, k, v, gates, B, H, W)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        q, k, v, gates = ctx.saved_tensors
-        grads = anab_attention_backward_bf16(q, k, v, gates, grad_out, *ctx.dims, needs=tuple(ctx.needs_input_grad[:4]))
-        return grads + (None, None, None)
 
 
 def anab_attention_bf16(q, k, v, gates, B, H, W):

@@ -414,3 +414,39 @@ def test_public_operator_refusals_on_device_tensors():
     with torch.autocast("cuda", dtype=torch.bfloat16):           # autocast operands go back to float32
         out = ops.anab_attention(q.bfloat16(), k.bfloat16(), v.bfloat16(), g.bfloat16(), 1, 8, 16)
     assert out.dtype == torch.float32
+
+
+def test_c_abi_refusals():
+    """What the fp32 C ABI refuses, and with which code: a short workspace is M3D_E_WORKSPACE here (M3D_E_ARG in the bf16 entries,
+    tests/test_gpu_anab_bf16.py), everything else M3D_E_ARG.  The workspace is 16 MiB: the fp32 operator asks for 7.4 / 8.3 MiB at this
+    shape (the pooling scratch of a map whose windows do not nest), where the bf16 one stays below 2 MiB."""
+    L, dev = _hip.lib(), _dev()
+    E_ARG, E_WORKSPACE = -1, -3                                  # M3D_E_ARG, M3D_E_WORKSPACE
+    t = torch.zeros(128, 512, device=dev)
+    o = torch.zeros(128, 512, device=dev)
+    size = 1 << 24
+    ws = torch.zeros(2 * size, device=dev, dtype=torch.uint8)
+    base = (ws.data_ptr() + 255) // 256 * 256
+    p, po = t.data_ptr(), o.data_ptr()
+    need = [L.m3d_anab_attention_workspace_bytes(1, 8, 16, 168, 128, b) for b in (0, 1)]
+    assert 0 < need[0] < need[1] < size
+
+    def fwd(Ck=168, Cv=128, H=8, W=16, nbytes=size, ws_ptr=base):
+        return L.m3d_anab_attention_forward(p, p, p, p, po, 1, H, W, Ck, Cv, 512, 512, 512, 512, 512, ws_ptr, nbytes, _stream())
+
+    def bwd(go=p, nbytes=size, go_cs=512):
+        return L.m3d_anab_attention_backward(p, p, p, p, go, po, po, po, po, 1, 8, 16, 168, 128, 512, 512, 512, 512, go_cs, 512, 512, 512,
+                                             512, base, nbytes, _stream())
+
+    assert fwd() == 0 and bwd() == 0, L.m3d_last_error().decode()
+    torch.cuda.synchronize()
+    for code, word, call in ((E_ARG, "(Ck, Cv)", lambda: fwd(Ck=160)), (E_ARG, "(Ck, Cv)", lambda: fwd(Ck=64, Cv=256)),
+                             (E_ARG, "HW % 128", lambda: fwd(H=5, W=7)),
+                             (E_ARG, "256-byte aligned", lambda: fwd(ws_ptr=base + 16)),
+                             (E_ARG, "16-byte aligned", lambda: bwd(go=p + 4)), (E_ARG, "16-byte aligned", lambda: bwd(go_cs=510)),
+                             (E_WORKSPACE, "workspace", lambda: fwd(nbytes=need[0] - 1)),
+                             (E_WORKSPACE, "workspace", lambda: bwd(nbytes=need[1] - 1))):
+        assert call() == code, word
+        assert word in L.m3d_last_error().decode(), (word, L.m3d_last_error().decode())
+    assert L.m3d_anab_attention_workspace_bytes(1, 5, 7, 168, 128, 0) == -1
+    torch.cuda.synchronize()

@@ -9,7 +9,7 @@ HIP events around one forward + backward, `--warmup` untimed iterations, `--reps
 times one full training iteration (anab_fullalign, DLA-34, B = 2 at 384x1280: forward, RPN_3D_loss, backward, SGD step) for the
 record.
 
-With `--dtype bf16` the operator leg is ``ops.anab_attention_bf16`` against the parent path on the same bf16 tensors
+With `--dtype bf16` the operator leg is ``ops.anab_attention_bf16`` (the bf16 instantiation of the same csrc/anab_train.hip) against the parent path on the same bf16 tensors
 (``ops.anab_attention`` under torch.autocast(bfloat16)), with the interquartile range of each leg, and `--iteration` runs under
 autocast with ``ANAB.bf16_attention`` off and on.
 
