@@ -22,6 +22,8 @@
  *   m3d_dcn_v2_backward_workspace_bytes .. the `ones` / `columns` scratch tensors of that call (dcn_v2_func.py:41-48)
  *   m3d_rpn_targets / m3d_rpn_loss .. RPN_3D_loss.forward, lib/loss/rpn_3d.py:54-657, with compute_targets,
  *                                 lib/rpn_util.py:430-532 (host numpy in the reference) and the backward autograd derives
+ *   m3d_rpn_loss_smp ........... RPN_3D_loss_smp.forward, lib/loss/rpn_3d.py:705-1360 (targets pre-computed by the loader)
+ *   m3d_rpn_precompute_targets . Kitti_Dataset_torch._targets, lib/dataloader.py:1014-1144, for a whole batch
  *   _nms / m3d_nms_sorted_dev .. void _nms(int* keep_out, int* num_out, const float* boxes_host,
  *                                 int boxes_num, int boxes_dim, float nms_overlap_thresh, int device_id)
  *                                 lib/nms/gpu_nms.hpp:1-2, lib/nms/nms_kernel.cu:91-144 (kernel :34-78)
@@ -90,7 +92,8 @@ const char *m3d_last_error(void);
  *                  m3d_dcn_v2_psroi_pooling_workspace_bytes (additive);
  *                  m3d_anab_attention_forward, m3d_anab_attention_backward, m3d_anab_attention_workspace_bytes (additive);
  *                  m3d_anab_attention_forward_bf16, m3d_anab_attention_backward_bf16,
- *                  m3d_anab_attention_workspace_bytes_bf16 (additive). */
+ *                  m3d_anab_attention_workspace_bytes_bf16 (additive);
+ *                  m3d_rpn_loss_smp, m3d_rpn_precompute_targets (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -653,6 +656,37 @@ int m3d_rpn_loss(const double *anchors, int A, int H, int W, const double *conf,
                  const float *targets, const float *scores, unsigned char *sampled, float *grad_cls, float *grad_bbox_2d,
                  float *grad_bbox_3d, float *loss, double *stats, void *workspace, long long workspace_bytes,
                  m3d_stream_t stream);
+
+/* RPN_3D_loss_smp on the device (lib/loss/rpn_3d.py:659-1360): the same loss over targets that were assigned ahead of the
+ * forward, by the data loader (Kitti_Dataset_torch._targets, lib/dataloader.py:1014-1160) or by m3d_rpn_precompute_targets.
+ *
+ * m3d_rpn_precompute_targets is m3d_rpn_targets without cls / prob (launches 1-3, no scores, no accuracy counts): labels and
+ * gt_index as there, the targets in the loader's layout -- bbox_2d_tar float32 [B, R, 4] and bbox_3d_tar float32 [B, R, 7], the
+ * same bits as columns 0-3 and 4-10 of m3d_rpn_targets' `targets` ((0 - mean) / std where a row is not fg, 0 in an image
+ * without a valid gt) -- and any_val int32 [B]: 1 where the image has a valid gt.
+ *
+ * m3d_rpn_loss_smp has no gt table.  labels_in is device [B, R], int64 (label_bytes = 8: what the loader collates) or int16
+ * (label_bytes = 2: what m3d_rpn_targets / m3d_rpn_precompute_targets write), each 0 (bg), 1 .. C-1 (fg) or 3000 (ignored);
+ * any other value is counted in stats[M3D_RPN_SMP_STAT_BAD_LABELS] and the row treated as ignored.  bbox_2d_tar / bbox_3d_tar /
+ * any_val as above, on the device.  One ingest launch writes labels (int16), targets (float32 [B, R, 11], packed) and scores
+ * (prob[label]; 0 for an ignored row and in an image with any_val = 0) -- caller buffers like those of m3d_rpn_targets -- and
+ * leaves the per-image counts in the workspace; launches 4-6 of m3d_rpn_loss follow unchanged.  An image with any_val = 0
+ * selects nothing; its labels still enter the fg / bg accuracy.  Outputs as m3d_rpn_loss; `stats` holds
+ * M3D_RPN_SMP_STAT_COUNT doubles.  Fed the labels and targets m3d_rpn_targets wrote, every output equals m3d_rpn_loss' bit for
+ * bit.  Workspace: m3d_rpn_loss_workspace_bytes(B, R), contents irrelevant on entry. */
+enum {
+    M3D_RPN_SMP_STAT_BAD_LABELS = 16,   /* after the M3D_RPN_STAT_* slots */
+    M3D_RPN_SMP_STAT_COUNT = 17
+};
+int m3d_rpn_precompute_targets(const double *anchors, int A, int H, int W, const double *conf, int n_conf,
+                               const double *gt_table, int B, int Gmax, short *labels, short *gt_index, float *bbox_2d_tar,
+                               float *bbox_3d_tar, int *any_val, void *workspace, long long workspace_bytes,
+                               m3d_stream_t stream);
+int m3d_rpn_loss_smp(const double *anchors, int A, int H, int W, const double *conf, int n_conf, int B, const void *labels_in,
+                     int label_bytes, const float *bbox_2d_tar, const float *bbox_3d_tar, const int *any_val, const float *cls,
+                     const float *prob, const float *bbox_2d, const float *bbox_3d, int C, short *labels, float *targets,
+                     float *scores, unsigned char *sampled, float *grad_cls, float *grad_bbox_2d, float *grad_bbox_3d,
+                     float *loss, double *stats, void *workspace, long long workspace_bytes, m3d_stream_t stream);
 
 /* Weight packing: [Cout, Cin, kh, kw] (torch layout) -> [Cout_pad, kh*kw*Cin_pad] (tap-major, zero pad). */
 int m3d_pack_conv_weight(const float *w, float *packed, int Cout, int Cout_pad, int Cin, int Cin_pad, int kh,

@@ -15,11 +15,15 @@
 // unsigned 32-bit vector atomic min), launch 3 recomputes the same bits once more and assigns.  Integer max / min / add only:
 // the result does not depend on arrival order.
 //
-// Launches (m3d_rpn_targets: 1-3, m3d_rpn_loss: 4-6):
+// Launches (m3d_rpn_targets: 1-3, m3d_rpn_loss: 4-6; m3d_rpn_precompute_targets: 1-3 without cls / prob; m3d_rpn_loss_smp: the
+// ingest launch, then 4-6):
 //   1 rpn_gt_max_kernel     per anchor x valid gt: overlap -> max of its bits over 1 024 anchors on chip, one atomic max per gt
 //   2 rpn_gt_row_kernel     per anchor x valid gt: overlap == max -> atomic min of the row per gt
 //   3 rpn_assign_kernel     per anchor: row max / arg-max, ignore overlap, label, gt index, the 11 normalised regression targets,
 //                           the score prob[label] the sampling sorts by, and the fg / bg counts + arg-max accuracy counts
+//   I rpn_ingest_kernel     (RPN_3D_loss_smp, lib/loss/rpn_3d.py:659-1360: targets arrive pre-computed) per anchor: the label as the
+//                           data loader collates it (int64) or as launch 3 writes it (int16) -> checked int16 label, the score
+//                           prob[label], the packed targets and the same per-image counts launch 3 leaves, + a bad-label count
 //   4 rpn_select_kernel     per (image, fg | bg): the k lowest (score, row) keys by radix select (8-bit digits over the sortable
 //                           score bits, then over the row among the scores equal to the threshold) -> a threshold key
 //   5 rpn_loss_kernel       per anchor (at most 2 048 workgroups stride over the rows): sampled iff key <= threshold; weighted
@@ -50,7 +54,7 @@ struct RpnConf {
 struct RpnWs {
     unsigned long long *gtmax;   // [B][M3D_RPN_MAX_GT] bits of the best overlap per valid gt
     unsigned *bestrow;           // [B][M3D_RPN_MAX_GT] lowest row with that overlap
-    int *counts;                 // [B][8]: 0 fg, 1 bg, 2 fg arg-max correct, 3 bg arg-max correct
+    int *counts;                 // [B][8]: 0 fg, 1 bg, 2 fg arg-max correct, 3 bg arg-max correct, 4 labels outside the allowed set (ingest)
     unsigned *sel;               // [B][2][8]: 0 mode (0 none, 1 all, 2 threshold), 1 score key, 2 row, 3 selected, 4 selected with score 1
     double *partials;            // [workgroups of launch 5][RPN_NQ]
     long long total;
@@ -235,6 +239,8 @@ struct RpnAssignArgs {
     float *targets, *scores;
     int *counts;
     int Gmax, R, H, W, C;
+    float *tar_2d, *tar_3d;      // PRE only: the targets as [B, R, 4] and [B, R, 7] (the data loader's layout) instead of `targets`
+    int *any_val;                // PRE only: [B], 1 where the image has a valid gt
 };
 
 __device__ __forceinline__ float rpn_norm(double t, double mean, double stdv)
@@ -245,6 +251,8 @@ __device__ __forceinline__ float rpn_norm(double t, double mean, double stdv)
     return (float)((double)s / stdv);
 }
 
+// PRE (m3d_rpn_precompute_targets): no cls / prob, so no score, no accuracy count; labels, gt index and target bits as without
+template <bool PRE>
 __global__ __launch_bounds__(RPN_TPB) void rpn_assign_kernel(RpnAssignArgs A, RpnConf cf)
 {
     __shared__ double sg[M3D_RPN_MAX_GT][5];
@@ -313,6 +321,19 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_assign_kernel(RpnAssignArgs A, Rp
     } else {
         is_bg = true;      // an image without a valid gt keeps label 0 everywhere (and is never sampled)
     }
+    if (PRE) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) A.any_val[b] = nv > 0 ? 1 : 0;
+        if (live) {
+            A.labels[row] = (short)label;
+            A.gt_index[row] = (short)gidx;
+            float *o2 = A.tar_2d + row * 4, *o3 = A.tar_3d + row * 7;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o2[i] = tar[i];
+#pragma unroll
+            for (int i = 0; i < 7; ++i) o3[i] = tar[4 + i];
+        }
+        return;
+    }
     int pred = 0;
     float score = 0.f;
     if (live) {
@@ -338,6 +359,96 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_assign_kernel(RpnAssignArgs A, Rp
     }
     __syncthreads();
     if (threadIdx.x < 4 && sc[threadIdx.x]) atomicAdd(&A.counts[b * 8 + threadIdx.x], sc[threadIdx.x]);
+}
+
+// ---- ingest (RPN_3D_loss_smp) ---------------------------------------------------------------------------------------------
+struct RpnIngestArgs {
+    const void *labels_in;       // [B, R] int64 (the data loader's collated labels) or int16 (launch 3's)
+    const float *tar_2d, *tar_3d, *cls, *prob;
+    const int *any_val;
+    short *labels;
+    float *targets, *scores;
+    int *counts;
+    int R, C;
+};
+
+template <typename T> struct RpnLabelPair;
+template <> struct RpnLabelPair<long long> { typedef longlong2 type; };     // one 16-byte load
+template <> struct RpnLabelPair<short> { typedef short2 type; };            // one 4-byte load
+
+// Two consecutive rows per thread.  A label outside {0, 1 .. C-1, 3000} is counted and treated as ignored.  The score follows
+// launch 3: prob[label] where the image has a valid gt and the row is not ignored, else 0.  The counts are launch 3's (every
+// image, with or without a valid gt, enters the accuracy stats), integer atomics only.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(RPN_TPB) void rpn_ingest_kernel(RpnIngestArgs A)
+{
+    __shared__ int sc[5];
+    const int b = blockIdx.y;
+    if (threadIdx.x < 5) sc[threadIdx.x] = 0;
+    __syncthreads();
+    const int r0 = (blockIdx.x * RPN_TPB + threadIdx.x) * 2;
+    const T *lin = (const T *)A.labels_in + (size_t)b * A.R;
+    const bool has_gt = A.any_val[b] != 0;
+    const bool live[2] = {r0 < A.R, r0 + 1 < A.R};
+    long long lv[2] = {0, 0};
+    if (VEC) {
+        if (live[1]) {
+            const typename RpnLabelPair<T>::type p = *reinterpret_cast<const typename RpnLabelPair<T>::type *>(lin + r0);
+            lv[0] = (long long)p.x;
+            lv[1] = (long long)p.y;
+        }
+    } else {
+        if (live[0]) lv[0] = (long long)lin[r0];
+        if (live[1]) lv[1] = (long long)lin[r0 + 1];
+    }
+    bool f_fg[2], f_bg[2], f_okfg[2], f_okbg[2], f_bad[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const bool ok = lv[u] == 0 || (lv[u] > 0 && lv[u] < (long long)A.C) || lv[u] == RPN_IGN_LABEL;
+        const int label = ok ? (int)lv[u] : RPN_IGN_LABEL;
+        const bool is_fg = label > 0 && label != RPN_IGN_LABEL, is_bg = label == 0;
+        int pred = 0;
+        if (live[u]) {
+            const size_t row = (size_t)b * A.R + r0 + u;
+            const float *c = A.cls + row * A.C;
+            float mx = c[0];
+            for (int k = 1; k < A.C; ++k)
+                if (c[k] > mx) { mx = c[k]; pred = k; }
+            float score = 0.f;
+            if (has_gt && label < A.C) score = A.prob[row * A.C + label];
+            A.labels[row] = (short)label;
+            A.scores[row] = score;
+        }
+        f_fg[u] = live[u] && is_fg;
+        f_bg[u] = live[u] && is_bg;
+        f_okfg[u] = f_fg[u] && pred == label;
+        f_okbg[u] = f_bg[u] && pred == 0;
+        f_bad[u] = live[u] && !ok;
+    }
+    // the packed targets of this workgroup's rows: consecutive threads write consecutive floats
+    {
+        const int base = blockIdx.x * RPN_TPB * 2, nrows = min(RPN_TPB * 2, A.R - base);
+        const size_t row0 = (size_t)b * A.R + base;
+        const float *i2 = A.tar_2d + row0 * 4, *i3 = A.tar_3d + row0 * 7;
+        float *o = A.targets + row0 * 11;
+        for (int e = threadIdx.x; e < nrows * 11; e += RPN_TPB) {
+            const int rr = e / 11, c = e - rr * 11;
+            o[e] = c < 4 ? i2[rr * 4 + c] : i3[rr * 7 + (c - 4)];
+        }
+    }
+    int n[5];
+    n[0] = __popcll(__ballot(f_fg[0])) + __popcll(__ballot(f_fg[1]));
+    n[1] = __popcll(__ballot(f_bg[0])) + __popcll(__ballot(f_bg[1]));
+    n[2] = __popcll(__ballot(f_okfg[0])) + __popcll(__ballot(f_okfg[1]));
+    n[3] = __popcll(__ballot(f_okbg[0])) + __popcll(__ballot(f_okbg[1]));
+    n[4] = __popcll(__ballot(f_bad[0])) + __popcll(__ballot(f_bad[1]));
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if (n[k]) atomicAdd(&sc[k], n[k]);
+    }
+    __syncthreads();
+    if (threadIdx.x < 5 && sc[threadIdx.x]) atomicAdd(&A.counts[b * 8 + threadIdx.x], sc[threadIdx.x]);
 }
 
 // ---- launch 4 ----------------------------------------------------------------------------------------------------------
@@ -414,8 +525,9 @@ __device__ __forceinline__ unsigned rpn_select_pass(unsigned *hist, unsigned *bc
 
 template <bool VEC>
 __global__ __launch_bounds__(RPN_SEL_TPB) void rpn_select_kernel(const short *__restrict__ labels, const float *__restrict__ scores,
-                                                                 const double *__restrict__ gt, int Gmax, const int *__restrict__ counts,
-                                                                 unsigned *__restrict__ sel, int R, RpnConf cf)
+                                                                 const double *__restrict__ gt, int Gmax, const int *__restrict__ any_val,
+                                                                 const int *__restrict__ counts, unsigned *__restrict__ sel, int R,
+                                                                 RpnConf cf)
 {
     __shared__ unsigned hist[256];
     __shared__ unsigned bc[4];
@@ -423,7 +535,8 @@ __global__ __launch_bounds__(RPN_SEL_TPB) void rpn_select_kernel(const short *__
     const short *lb = labels + (size_t)b * R;
     const float *sc = scores + (size_t)b * R;
     unsigned *out = sel + (b * 2 + kind) * 8;
-    const int nv = (int)gt[(size_t)b * (Gmax + 1) * M3D_RPN_GT_COLS];
+    // whether the image has a valid gt: from its table, or (pre-computed targets: no table) from the loader's any_val
+    const int nv = gt ? (int)gt[(size_t)b * (Gmax + 1) * M3D_RPN_GT_COLS] : any_val[b];
     const int n_fg = counts[b * 8 + 0], n_bg = counts[b * 8 + 1];
     long long fg_num, bg_num;
     if (isinf(cf.box_samples)) {
@@ -711,7 +824,7 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_loss_kernel(RpnLossArgs A, RpnCon
 #define RPN_FIN_TPB 1024
 __global__ __launch_bounds__(RPN_FIN_TPB) void rpn_finish_kernel(const double *__restrict__ partials, int nblk, const unsigned *__restrict__ sel,
                                                                  const int *__restrict__ counts, int B, RpnConf cf, float *__restrict__ loss_out,
-                                                                 double *__restrict__ stats)
+                                                                 double *__restrict__ stats, int smp)
 {
     // thread (l, k) adds the partials of quantity k of the workgroups l, l + 64, ...; then a tree over l: fixed order
     __shared__ double red[RPN_FIN_TPB / RPN_NQ][RPN_NQ];
@@ -761,6 +874,11 @@ __global__ __launch_bounds__(RPN_FIN_TPB) void rpn_finish_kernel(const double *_
     s[M3D_RPN_STAT_N_ACTIVE] = T.n_active;
     s[M3D_RPN_STAT_FG_WEIGHT] = T.fg_weight;
     for (int k = 0; k < M3D_RPN_STAT_COUNT; ++k) stats[k] = s[k];
+    if (smp) {
+        long long bad = 0;
+        for (int b = 0; b < B; ++b) bad += counts[b * 8 + 4];
+        stats[M3D_RPN_SMP_STAT_BAD_LABELS] = (double)bad;
+    }
     loss_out[0] = (float)loss;
 }
 
@@ -812,8 +930,37 @@ extern "C" int m3d_rpn_targets(const double *anchors, int A, int H, int W, const
     RpnAssignArgs a;
     a.anchors = anchors; a.gt = gt_table; a.cls = cls; a.prob = prob; a.gtmax = ws.gtmax; a.bestrow = ws.bestrow;
     a.labels = labels; a.gt_index = gt_index; a.targets = targets; a.scores = scores; a.counts = ws.counts;
-    a.Gmax = Gmax; a.R = (int)R; a.H = H; a.W = W; a.C = C;
-    hipLaunchKernelGGL(rpn_assign_kernel, grid, dim3(RPN_TPB), 0, s, a, cf);
+    a.Gmax = Gmax; a.R = (int)R; a.H = H; a.W = W; a.C = C; a.tar_2d = a.tar_3d = nullptr; a.any_val = nullptr;
+    hipLaunchKernelGGL(rpn_assign_kernel<false>, grid, dim3(RPN_TPB), 0, s, a, cf);
+    M3D_LAUNCH_CHECK();
+    return M3D_OK;
+}
+
+// launches 4-6 behind m3d_rpn_loss (gt_table) and m3d_rpn_loss_smp (any_val, one more stat slot)
+static int rpn_launch_loss(const char *who, const double *anchors, int H, int W, const RpnConf &cf, const double *gt_table, int Gmax,
+                           const int *any_val, int B, long long R, const float *cls, const float *bbox_2d, const float *bbox_3d, int C,
+                           const short *labels, const float *targets, const float *scores, unsigned char *sampled, float *grad_cls,
+                           float *grad_bbox_2d, float *grad_bbox_3d, float *loss, double *stats, const RpnWs &ws, hipStream_t s)
+{
+    if (!isinf(cf.box_samples)) {
+        // with a rounded count of 0 the reference keeps EVERY candidate instead of none (its `num > 0 and ...` guards)
+        const double want = (double)R * cf.box_samples, fg_cap = rint(want * cf.fg_fraction);
+        M3D_REQUIRE(fg_cap >= 1 && rint(want - fg_cap) >= 1, "%s: box_samples %g x fg_fraction %g of %lld anchors rounds to no fg or no bg sample",
+                    who, cf.box_samples, cf.fg_fraction, R);
+    }
+    if (R % 4 == 0 && (uintptr_t)labels % 8 == 0 && (uintptr_t)scores % 16 == 0)
+        hipLaunchKernelGGL(rpn_select_kernel<true>, dim3(2, B), dim3(RPN_SEL_TPB), 0, s, labels, scores, gt_table, Gmax, any_val, ws.counts, ws.sel, (int)R, cf);
+    else
+        hipLaunchKernelGGL(rpn_select_kernel<false>, dim3(2, B), dim3(RPN_SEL_TPB), 0, s, labels, scores, gt_table, Gmax, any_val, ws.counts, ws.sel, (int)R, cf);
+    M3D_LAUNCH_CHECK();
+    RpnLossArgs a;
+    a.anchors = anchors; a.cls = cls; a.bbox_2d = bbox_2d; a.bbox_3d = bbox_3d; a.labels = labels; a.targets = targets; a.scores = scores;
+    a.sel = ws.sel; a.sampled = sampled; a.g_cls = grad_cls; a.g_2d = grad_bbox_2d; a.g_3d = grad_bbox_3d; a.partials = ws.partials;
+    a.B = B; a.R = (int)R; a.H = H; a.W = W; a.C = C;
+    const int nblk = imin(cdiv((long long)B * R, RPN_TPB), RPN_LOSS_MAX_WG);
+    hipLaunchKernelGGL(rpn_loss_kernel, dim3(nblk), dim3(RPN_TPB), 0, s, a, cf);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rpn_finish_kernel, dim3(1), dim3(RPN_FIN_TPB), 0, s, ws.partials, nblk, ws.sel, ws.counts, B, cf, loss, stats, gt_table ? 0 : 1);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
 }
@@ -837,26 +984,82 @@ extern "C" int m3d_rpn_loss(const double *anchors, int A, int H, int W, const do
         m3d_set_error("rpn_loss: workspace %lld < %lld bytes (m3d_rpn_loss_workspace_bytes)", workspace_bytes, ws.total);
         return M3D_E_WORKSPACE;
     }
-    if (!isinf(cf.box_samples)) {
-        // with a rounded count of 0 the reference keeps EVERY candidate instead of none (its `num > 0 and ...` guards)
-        const double want = (double)R * cf.box_samples, fg_cap = rint(want * cf.fg_fraction);
-        M3D_REQUIRE(fg_cap >= 1 && rint(want - fg_cap) >= 1, "rpn_loss: box_samples %g x fg_fraction %g of %lld anchors rounds to no fg or no bg sample",
-                    cf.box_samples, cf.fg_fraction, R);
+    return rpn_launch_loss("rpn_loss", anchors, H, W, cf, gt_table, Gmax, nullptr, B, R, cls, bbox_2d, bbox_3d, C, labels, targets, scores,
+                           sampled, grad_cls, grad_bbox_2d, grad_bbox_3d, loss, stats, ws, (hipStream_t)stream);
+}
+
+extern "C" int m3d_rpn_precompute_targets(const double *anchors, int A, int H, int W, const double *conf, int n_conf,
+                                          const double *gt_table, int B, int Gmax, short *labels, short *gt_index, float *bbox_2d_tar,
+                                          float *bbox_3d_tar, int *any_val, void *workspace, long long workspace_bytes,
+                                          m3d_stream_t stream)
+{
+    long long R;
+    RpnConf cf;
+    int st = rpn_check_shape("rpn_precompute_targets", A, H, W, B, 2, Gmax, &R);
+    if (st) return st;
+    if ((st = rpn_conf_from(conf, n_conf, &cf, "rpn_precompute_targets"))) return st;
+    M3D_REQUIRE(anchors && gt_table && labels && gt_index && bbox_2d_tar && bbox_3d_tar && any_val && workspace,
+                "rpn_precompute_targets: NULL pointer");
+    const RpnWs ws = rpn_ws_layout(workspace, B, R);
+    if (workspace_bytes < ws.total) {
+        m3d_set_error("rpn_precompute_targets: workspace %lld < %lld bytes (m3d_rpn_loss_workspace_bytes)", workspace_bytes, ws.total);
+        return M3D_E_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (R % 4 == 0 && (uintptr_t)labels % 8 == 0 && (uintptr_t)scores % 16 == 0)
-        hipLaunchKernelGGL(rpn_select_kernel<true>, dim3(2, B), dim3(RPN_SEL_TPB), 0, s, labels, scores, gt_table, Gmax, ws.counts, ws.sel, (int)R, cf);
-    else
-        hipLaunchKernelGGL(rpn_select_kernel<false>, dim3(2, B), dim3(RPN_SEL_TPB), 0, s, labels, scores, gt_table, Gmax, ws.counts, ws.sel, (int)R, cf);
+    M3D_HIP(hipMemsetAsync(ws.gtmax, 0, (size_t)B * M3D_RPN_MAX_GT * 8, s));
+    M3D_HIP(hipMemsetAsync(ws.bestrow, 0xff, (size_t)B * M3D_RPN_MAX_GT * 4, s));
+    const dim3 grid(cdiv(R, RPN_TPB), B);
+    hipLaunchKernelGGL(rpn_gt_max_kernel, dim3(cdiv(R, RPN_TPB * RPN_MAX_ROWS), B), dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax);
     M3D_LAUNCH_CHECK();
-    RpnLossArgs a;
-    a.anchors = anchors; a.cls = cls; a.bbox_2d = bbox_2d; a.bbox_3d = bbox_3d; a.labels = labels; a.targets = targets; a.scores = scores;
-    a.sel = ws.sel; a.sampled = sampled; a.g_cls = grad_cls; a.g_2d = grad_bbox_2d; a.g_3d = grad_bbox_3d; a.partials = ws.partials;
-    a.B = B; a.R = (int)R; a.H = H; a.W = W; a.C = C;
-    const int nblk = imin(cdiv((long long)B * R, RPN_TPB), RPN_LOSS_MAX_WG);
-    hipLaunchKernelGGL(rpn_loss_kernel, dim3(nblk), dim3(RPN_TPB), 0, s, a, cf);
+    hipLaunchKernelGGL(rpn_gt_row_kernel, grid, dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax, ws.bestrow);
     M3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rpn_finish_kernel, dim3(1), dim3(RPN_FIN_TPB), 0, s, ws.partials, nblk, ws.sel, ws.counts, B, cf, loss, stats);
+    RpnAssignArgs a;
+    a.anchors = anchors; a.gt = gt_table; a.cls = nullptr; a.prob = nullptr; a.gtmax = ws.gtmax; a.bestrow = ws.bestrow;
+    a.labels = labels; a.gt_index = gt_index; a.targets = nullptr; a.scores = nullptr; a.counts = nullptr;
+    a.Gmax = Gmax; a.R = (int)R; a.H = H; a.W = W; a.C = 0; a.tar_2d = bbox_2d_tar; a.tar_3d = bbox_3d_tar; a.any_val = any_val;
+    hipLaunchKernelGGL(rpn_assign_kernel<true>, grid, dim3(RPN_TPB), 0, s, a, cf);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
+}
+
+extern "C" int m3d_rpn_loss_smp(const double *anchors, int A, int H, int W, const double *conf, int n_conf, int B, const void *labels_in,
+                                int label_bytes, const float *bbox_2d_tar, const float *bbox_3d_tar, const int *any_val, const float *cls,
+                                const float *prob, const float *bbox_2d, const float *bbox_3d, int C, short *labels, float *targets,
+                                float *scores, unsigned char *sampled, float *grad_cls, float *grad_bbox_2d, float *grad_bbox_3d,
+                                float *loss, double *stats, void *workspace, long long workspace_bytes, m3d_stream_t stream)
+{
+    long long R;
+    RpnConf cf;
+    int st = rpn_check_shape("rpn_loss_smp", A, H, W, B, C, 0, &R);
+    if (st) return st;
+    if ((st = rpn_conf_from(conf, n_conf, &cf, "rpn_loss_smp"))) return st;
+    M3D_REQUIRE(label_bytes == 8 || label_bytes == 2, "rpn_loss_smp: labels are int64 (label_bytes 8) or int16 (2), got %d", label_bytes);
+    M3D_REQUIRE(anchors && labels_in && bbox_2d_tar && bbox_3d_tar && any_val && cls && prob && bbox_2d && bbox_3d && labels && targets &&
+                    scores && sampled && grad_cls && grad_bbox_2d && grad_bbox_3d && loss && stats && workspace,
+                "rpn_loss_smp: NULL pointer");
+    M3D_REQUIRE((uintptr_t)labels_in % label_bytes == 0, "rpn_loss_smp: labels are not aligned to their own size");
+    M3D_REQUIRE(labels_in != (const void *)labels, "rpn_loss_smp: the int16 label output must not alias the label input");
+    const RpnWs ws = rpn_ws_layout(workspace, B, R);
+    if (workspace_bytes < ws.total) {
+        m3d_set_error("rpn_loss_smp: workspace %lld < %lld bytes (m3d_rpn_loss_workspace_bytes)", workspace_bytes, ws.total);
+        return M3D_E_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    M3D_HIP(hipMemsetAsync(ws.counts, 0, (size_t)B * 8 * 4, s));
+    RpnIngestArgs g;
+    g.labels_in = labels_in; g.tar_2d = bbox_2d_tar; g.tar_3d = bbox_3d_tar; g.any_val = any_val; g.cls = cls; g.prob = prob;
+    g.labels = labels; g.targets = targets; g.scores = scores; g.counts = ws.counts; g.R = (int)R; g.C = C;
+    // two labels per load: every image's first row is then aligned iff R is even
+    const bool vec = R % 2 == 0 && (uintptr_t)labels_in % (2 * label_bytes) == 0;
+    const dim3 grid(cdiv(R, RPN_TPB * 2), B);
+    if (label_bytes == 8) {
+        if (vec) hipLaunchKernelGGL((rpn_ingest_kernel<long long, true>), grid, dim3(RPN_TPB), 0, s, g);
+        else hipLaunchKernelGGL((rpn_ingest_kernel<long long, false>), grid, dim3(RPN_TPB), 0, s, g);
+    } else {
+        if (vec) hipLaunchKernelGGL((rpn_ingest_kernel<short, true>), grid, dim3(RPN_TPB), 0, s, g);
+        else hipLaunchKernelGGL((rpn_ingest_kernel<short, false>), grid, dim3(RPN_TPB), 0, s, g);
+    }
+    M3D_LAUNCH_CHECK();
+    return rpn_launch_loss("rpn_loss_smp", anchors, H, W, cf, nullptr, 0, any_val, B, R, cls, bbox_2d, bbox_3d, C, labels, targets, scores,
+                           sampled, grad_cls, grad_bbox_2d, grad_bbox_3d, loss, stats, ws, s);
 }

@@ -1,4 +1,4 @@
-"""RPN_3D_loss (lib/loss/rpn_3d.py:14-657) on the HIP library.
+"""RPN_3D_loss (lib/loss/rpn_3d.py:14-657) and RPN_3D_loss_smp (lib/loss/rpn_3d.py:659-1360) on the HIP library.
 
 The reference copies ``prob`` to the host, assigns targets and samples in numpy one image at a time and uploads sixteen
 ``[B, R]`` arrays again.  Here the host part is what concerns a few dozen ground-truth boxes -- ``determine_ignores``, the class
@@ -8,9 +8,18 @@ m3d_rpn_targets / m3d_rpn_loss (csrc/rpn_loss.hip); one small stat block is down
 list.  ``loss`` stays on the device and carries a ``grad_fn``: the gradients with respect to ``cls``, ``bbox_2d`` and ``bbox_3d``
 were written by the same launch and are handed to autograd in ``backward`` (scaled when ``grad_output`` is not 1).
 
-Not supported (NotImplementedError): ``bbox_3d_proj_lambda != 0`` (the reference's branch mixes host and device tensors),
-random sampling (``hard_negatives=False`` with a finite ``box_samples``: it draws from numpy's global RNG stream) and
-``RPN_3D_loss_smp`` (it consumes targets the data loader pre-computes).  Host tensors: NotImplementedError, no CPU fallback.
+RPN_3D_loss_smp is the criterion the training script binds when ``conf.pre_compute_target`` is set (all shipped
+configurations): its fifth argument is the collated ``batch['target']`` dict the data loader assigned per image
+(``Kitti_Dataset_torch._targets``, lib/dataloader.py:1014-1160), not a list of imobjs.  Here it reads ``labels`` (int64 or
+int16), ``bbox_2d``, ``bbox_3d`` and ``meta['any_val']`` from that dict -- host tensors are uploaded through pinned staging --
+and m3d_rpn_loss_smp validates the labels, gathers the sampling scores and counts on the device, then runs the select / loss /
+finish launches of m3d_rpn_loss unchanged.  ``rpn_precompute_targets`` (m3d_rpn_precompute_targets) is the device form of
+``_targets``: the same dict, made ahead of the forward from the packed gt table.  ``labels_fg`` / ``labels_bg`` /
+``labels_ign`` and ``meta['rois']`` are functions of ``labels`` and ``conf.anchors`` and are not read.
+
+Not supported (NotImplementedError): ``bbox_3d_proj_lambda != 0`` (the reference's branch mixes host and device tensors) and
+random sampling (``hard_negatives=False`` with a finite ``box_samples``: it draws from a global RNG stream).  Host ``cls`` /
+``prob`` / ``bbox_*``: NotImplementedError, no CPU fallback.
 """
 import math
 
@@ -26,6 +35,8 @@ GT_COLS = 12          # M3D_RPN_GT_COLS
 CONF_COUNT = 35       # M3D_RPN_CONF_COUNT
 STAT_NAMES = ("loss", "cls", "bbox_2d", "bbox_3d", "iou_loss", "z", "ry", "iou_acc", "acc_fg", "acc_bg", "n_fg", "n_bg", "fg_num",
               "bg_num", "n_active", "fg_weight")          # M3D_RPN_STAT_*
+SMP_STAT_BAD_LABELS = 16          # M3D_RPN_SMP_STAT_BAD_LABELS: the stat block of m3d_rpn_loss_smp has one more slot
+SMP_STAT_COUNT = 17               # M3D_RPN_SMP_STAT_COUNT
 IGN_FLAG = 3000
 
 
@@ -116,7 +127,7 @@ def _check_inputs(who, cls, prob, bbox_2d, bbox_3d, n_anchors, feat_size):
 
 
 class _Ctx:
-    """Device-side state shared by rpn_targets and rpn_loss: anchors, settings, gt table, workspace."""
+    """Device-side state shared by rpn_targets and rpn_loss: anchors, settings, gt table (None: pre-computed targets), workspace."""
 
     def __init__(self, anchors, conf_vec, gt_table, feat_size, B, R, device):
         L = _hip.lib()
@@ -125,6 +136,15 @@ class _Ctx:
         if self.anchors.dtype != torch.float64 or self.anchors.dim() != 2 or self.anchors.shape[1] != 9 or not self.anchors.is_cuda:
             raise RuntimeError("rpn_loss: anchors must be [A, 9] (x1 y1 x2 y2 z w h l ry)")
         self.conf = np.ascontiguousarray(conf_vec, dtype=np.float64)
+        self.H, self.W = int(feat_size[0]), int(feat_size[1])
+        self.A = int(self.anchors.shape[0])
+        nbytes = L.m3d_rpn_loss_workspace_bytes(B, R)
+        self.ws = torch.empty(nbytes + 256, device=device, dtype=torch.uint8)
+        self.ws_base = (self.ws.data_ptr() + 255) // 256 * 256
+        self.ws_bytes = nbytes
+        if gt_table is None:
+            self.gt, self.Gmax = None, 0
+            return
         gt_table = np.ascontiguousarray(gt_table, dtype=np.float64)
         if gt_table.ndim != 3 or gt_table.shape[0] != B or gt_table.shape[2] != GT_COLS or gt_table.shape[1] < 1:
             raise RuntimeError("rpn_loss: gt table must be [B = %d, Gmax + 1, %d] (got %s)" % (B, GT_COLS, gt_table.shape))
@@ -135,12 +155,6 @@ class _Ctx:
         self.max_label = max([int(gt_table[b, 1:1 + int(gt_table[b, 0, 0]), 4].max()) for b in range(B) if gt_table[b, 0, 0] > 0] + [1])
         self.min_label = min([int(gt_table[b, 1:1 + int(gt_table[b, 0, 0]), 4].min()) for b in range(B) if gt_table[b, 0, 0] > 0] + [1])
         self.gt = torch.from_numpy(gt_table).to(device, non_blocking=False)            # the upload
-        self.H, self.W = int(feat_size[0]), int(feat_size[1])
-        self.A = int(self.anchors.shape[0])
-        nbytes = L.m3d_rpn_loss_workspace_bytes(B, R)
-        self.ws = torch.empty(nbytes + 256, device=device, dtype=torch.uint8)
-        self.ws_base = (self.ws.data_ptr() + 255) // 256 * 256
-        self.ws_bytes = nbytes
 
     def conf_ptr(self):
         return self.conf.ctypes.data
@@ -239,50 +253,66 @@ def stats_list(block, cls_2d_lambda, bbox_2d_lambda, bbox_3d_lambda, iou_2d_lamb
     return out
 
 
+def _conf_fields(self, conf):
+    """The constructor fields both reference classes carry."""
+    self.num_classes = len(conf.lbls) + 1
+    self.num_anchors = conf.anchors.shape[0]
+    self.anchors = conf.anchors
+    self.bbox_means = conf.bbox_means
+    self.bbox_stds = conf.bbox_stds
+    self.feat_stride = conf.feat_stride
+    self.fg_fraction = conf.fg_fraction
+    self.box_samples = conf.box_samples
+    self.ign_thresh = conf.ign_thresh
+    self.nms_thres = conf.nms_thres
+    self.fg_thresh = conf.fg_thresh
+    self.bg_thresh_lo = conf.bg_thresh_lo
+    self.bg_thresh_hi = conf.bg_thresh_hi
+    self.best_thresh = conf.best_thresh
+    self.hard_negatives = conf.hard_negatives
+    self.focal_loss = conf.focal_loss
+    self.crop_size = conf.crop_size
+    self.cls_2d_lambda = conf.cls_2d_lambda
+    self.iou_2d_lambda = conf.iou_2d_lambda
+    self.bbox_2d_lambda = conf.bbox_2d_lambda
+    self.bbox_3d_lambda = conf.bbox_3d_lambda
+    self.bbox_3d_proj_lambda = conf.bbox_3d_proj_lambda
+    self.lbls = conf.lbls
+    self.ilbls = conf.ilbls
+    self.min_gt_vis = conf.min_gt_vis
+    self.min_gt_h = conf.min_gt_h
+    self.max_gt_h = conf.max_gt_h
+    self.device = conf.device
+
+
 class RPN_3D_loss(nn.Module):
     """Drop-in for lib/loss/rpn_3d.py: RPN_3D_loss -- same constructor fields, same ``forward`` signature and return."""
 
     def __init__(self, conf):
         super(RPN_3D_loss, self).__init__()
-        self.num_classes = len(conf.lbls) + 1
-        self.num_anchors = conf.anchors.shape[0]
-        self.anchors = conf.anchors
-        self.bbox_means = conf.bbox_means
-        self.bbox_stds = conf.bbox_stds
-        self.feat_stride = conf.feat_stride
-        self.fg_fraction = conf.fg_fraction
-        self.box_samples = conf.box_samples
-        self.ign_thresh = conf.ign_thresh
-        self.nms_thres = conf.nms_thres
-        self.fg_thresh = conf.fg_thresh
-        self.bg_thresh_lo = conf.bg_thresh_lo
-        self.bg_thresh_hi = conf.bg_thresh_hi
-        self.best_thresh = conf.best_thresh
-        self.hard_negatives = conf.hard_negatives
-        self.focal_loss = conf.focal_loss
-        self.crop_size = conf.crop_size
-        self.cls_2d_lambda = conf.cls_2d_lambda
-        self.iou_2d_lambda = conf.iou_2d_lambda
-        self.bbox_2d_lambda = conf.bbox_2d_lambda
-        self.bbox_3d_lambda = conf.bbox_3d_lambda
-        self.bbox_3d_proj_lambda = conf.bbox_3d_proj_lambda
-        self.lbls = conf.lbls
-        self.ilbls = conf.ilbls
-        self.min_gt_vis = conf.min_gt_vis
-        self.min_gt_h = conf.min_gt_h
-        self.max_gt_h = conf.max_gt_h
-        self.device = conf.device
+        _conf_fields(self, conf)
         self._anchors_dev = None
         self.last = None          # details of the last call (labels, sampled, ...): a dict of device tensors
         self._check_settings()
 
     def _check_settings(self):
+        who = type(self).__name__
         if self.bbox_3d_proj_lambda:
-            raise NotImplementedError("RPN_3D_loss: bbox_3d_proj_lambda != 0 is not supported (the reference's own branch mixes host "
+            raise NotImplementedError(who + ": bbox_3d_proj_lambda != 0 is not supported (the reference's own branch mixes host "
                                       "and device tensors)")
         if not self.hard_negatives and not math.isinf(float(self.box_samples)):
-            raise NotImplementedError("RPN_3D_loss: random sampling (hard_negatives=False with a finite box_samples) is not supported: "
-                                      "it draws from numpy's global RNG stream")
+            raise NotImplementedError(who + ": random sampling (hard_negatives=False with a finite box_samples) is not supported: "
+                                      "it draws from a global RNG stream")
+
+    def _upload_anchors(self, device):
+        if self._anchors_dev is None or self._anchors_dev.device != device:
+            a = self.anchors.detach().cpu().numpy() if torch.is_tensor(self.anchors) else np.asarray(self.anchors)
+            self._anchors_dev = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+
+    def _conf_vec(self):
+        return pack_conf(self.bbox_means, self.bbox_stds, self.fg_thresh, self.ign_thresh, self.bg_thresh_lo, self.bg_thresh_hi,
+                         self.best_thresh, self.box_samples, self.fg_fraction, self.focal_loss, self.cls_2d_lambda, self.iou_2d_lambda,
+                         self.bbox_2d_lambda, self.bbox_3d_lambda, self.feat_stride)
 
     def forward(self, cls, prob, bbox_2d, bbox_3d, imobjs, feat_size):
         self._check_settings()
@@ -291,19 +321,186 @@ class RPN_3D_loss(nn.Module):
             raise RuntimeError("RPN_3D_loss: cls has %d classes, conf.lbls gives %d" % (cls.shape[2], self.num_classes))
         if len(imobjs) != cls.shape[0]:
             raise RuntimeError("RPN_3D_loss: %d imobjs for a batch of %d" % (len(imobjs), cls.shape[0]))
-        if self._anchors_dev is None or self._anchors_dev.device != cls.device:
-            a = self.anchors.detach().cpu().numpy() if torch.is_tensor(self.anchors) else np.asarray(self.anchors)
-            self._anchors_dev = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(cls.device)
+        self._upload_anchors(cls.device)
         table = pack_gts(imobjs, self.lbls, self.ilbls, self.min_gt_vis, self.min_gt_h)
-        vec = pack_conf(self.bbox_means, self.bbox_stds, self.fg_thresh, self.ign_thresh, self.bg_thresh_lo, self.bg_thresh_hi,
-                        self.best_thresh, self.box_samples, self.fg_fraction, self.focal_loss, self.cls_2d_lambda, self.iou_2d_lambda,
-                        self.bbox_2d_lambda, self.bbox_3d_lambda, self.feat_stride)
+        vec = self._conf_vec()
         loss, stats, self.last = rpn_loss(cls, prob, bbox_2d, bbox_3d, self._anchors_dev, vec, table, feat_size, return_details=True)
         block = stats.cpu().numpy()                                            # the one download
         return loss, stats_list(block, self.cls_2d_lambda, self.bbox_2d_lambda, self.bbox_3d_lambda, self.iou_2d_lambda)
 
 
-class RPN_3D_loss_smp(nn.Module):
+# ---- pre-computed targets: rpn_precompute_targets, rpn_loss_smp, RPN_3D_loss_smp ---------------------------------------------
+def rpn_precompute_targets(anchors, conf_vec, gt_table, feat_size, device):
+    """``Kitti_Dataset_torch._targets`` for a whole batch on the device (m3d_rpn_precompute_targets: launches 1-3 without cls /
+    prob).  Returns the target dict of rpn_loss_smp: labels, gt_index int16 [B, R]; bbox_2d float32 [B, R, 4]; bbox_3d float32
+    [B, R, 7]; meta: {any_val int32 [B]}.  The bits are those of rpn_targets; rows that are not fg carry (0 - mean) / std."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise NotImplementedError("rpn_precompute_targets: device=%s: no CPU fallback" % (device,))
+    L = _hip.lib()
+    gt_table = np.asarray(gt_table)
+    B = int(gt_table.shape[0])
+    R = int(anchors.shape[0]) * int(feat_size[0]) * int(feat_size[1])
+    ctx = _Ctx(anchors, conf_vec, gt_table, feat_size, B, R, dev)
+    if ctx.min_label < 1:
+        raise RuntimeError("rpn_precompute_targets: gt class labels must be >= 1 (got %d)" % ctx.min_label)
+    labels = torch.empty(B, R, device=dev, dtype=torch.int16)
+    gt_index = torch.empty(B, R, device=dev, dtype=torch.int16)
+    b2t = torch.empty(B, R, 4, device=dev, dtype=torch.float32)
+    b3t = torch.empty(B, R, 7, device=dev, dtype=torch.float32)
+    any_val = torch.empty(B, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _hip.check(L.m3d_rpn_precompute_targets(ctx.anchors.data_ptr(), ctx.A, ctx.H, ctx.W, ctx.conf_ptr(), CONF_COUNT, ctx.gt.data_ptr(),
+                                                B, ctx.Gmax, labels.data_ptr(), gt_index.data_ptr(), b2t.data_ptr(), b3t.data_ptr(),
+                                                any_val.data_ptr(), ctx.ws_base, ctx.ws_bytes, ops._stream()))
+    return dict(labels=labels, gt_index=gt_index, bbox_2d=b2t, bbox_3d=b3t, meta=dict(any_val=any_val))
+
+
+def _upload(t, device):
+    """A device tensor as it is; a host tensor through pinned memory (staged where it is not pinned already)."""
+    if t.is_cuda:
+        if t.device != device:
+            raise RuntimeError("rpn_loss_smp: a target tensor lives on %s, cls on %s" % (t.device, device))
+        return t
+    return (t if t.is_pinned() else t.pin_memory()).to(device, non_blocking=True)
+
+
+def _target_tensors(target, B, R, device):
+    """(labels int64 | int16 [B, R], bbox_2d [B, R, 4], bbox_3d [B, R, 7], any_val int32 [B]) on ``device`` from the target dict.
+    Checked before anything is uploaded."""
+    who = "rpn_loss_smp"
+    if not isinstance(target, dict):
+        raise RuntimeError("%s: the target must be the dict the data loader collates (labels, bbox_2d, bbox_3d, meta['any_val']), "
+                           "got %s" % (who, type(target).__name__))
+    for k in ("labels", "bbox_2d", "bbox_3d", "meta"):
+        if k not in target:
+            raise RuntimeError("%s: the target dict has no '%s'" % (who, k))
+    if not isinstance(target["meta"], dict) or "any_val" not in target["meta"]:
+        raise RuntimeError("%s: the target dict has no meta['any_val']" % who)
+    want = {"labels": ((B, R), (torch.int64, torch.int16)), "bbox_2d": ((B, R, 4), (torch.float32,)), "bbox_3d": ((B, R, 7), (torch.float32,))}
+    for k, (shape, dtypes) in want.items():
+        t = target[k]
+        if not torch.is_tensor(t):
+            raise RuntimeError("%s: target['%s'] must be a tensor (got %s)" % (who, k, type(t).__name__))
+        if tuple(t.shape) != shape:
+            raise RuntimeError("%s: target['%s'] has shape %s; expected %s" % (who, k, tuple(t.shape), shape))
+        if t.dtype not in dtypes:
+            raise RuntimeError("%s: target['%s'] must be %s (got %s)" % (who, k, " or ".join(str(d) for d in dtypes), t.dtype))
+        if not t.is_contiguous():
+            raise RuntimeError("%s: target['%s'] must be contiguous" % (who, k))
+    # functions of labels / conf.anchors: not read, but a wrong shape means the dict belongs to another batch
+    for k in ("labels_fg", "labels_bg", "labels_ign"):
+        if k in target and tuple(target[k].shape) != (B, R):
+            raise RuntimeError("%s: target['%s'] has shape %s; expected %s" % (who, k, tuple(target[k].shape), (B, R)))
+    rois = target["meta"].get("rois")
+    if rois is not None and (rois.dim() != 3 or rois.shape[0] != B or rois.shape[1] != R):
+        raise RuntimeError("%s: target['meta']['rois'] has shape %s; expected [%d, %d, 5]" % (who, tuple(rois.shape), B, R))
+    any_val = target["meta"]["any_val"]
+    any_val = any_val if torch.is_tensor(any_val) else torch.as_tensor(np.asarray(any_val))
+    if tuple(any_val.shape) != (B,) or any_val.dtype.is_floating_point:
+        raise RuntimeError("%s: target['meta']['any_val'] must hold %d integers (got %s %s)" % (who, B, any_val.dtype, tuple(any_val.shape)))
+    any_val = _upload(any_val.contiguous(), device).to(torch.int32)
+    return _upload(target["labels"], device), _upload(target["bbox_2d"], device), _upload(target["bbox_3d"], device), any_val
+
+
+def _loss_smp(ctx, cls, prob, bbox_2d, bbox_3d, tgt):
+    L = _hip.lib()
+    B, R, C = cls.shape
+    dev = cls.device
+    labels_in, b2t, b3t, any_val = tgt
+    labels = torch.empty(B, R, device=dev, dtype=torch.int16)
+    targets = torch.empty(B, R, 11, device=dev, dtype=torch.float32)
+    scores = torch.empty(B, R, device=dev, dtype=torch.float32)
+    sampled = torch.empty(B, R, device=dev, dtype=torch.uint8)
+    g_cls, g_2d, g_3d = torch.empty_like(cls), torch.empty_like(bbox_2d), torch.empty_like(bbox_3d)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    stats = torch.empty(SMP_STAT_COUNT, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _hip.check(L.m3d_rpn_loss_smp(ctx.anchors.data_ptr(), ctx.A, ctx.H, ctx.W, ctx.conf_ptr(), CONF_COUNT, B, labels_in.data_ptr(),
+                                      labels_in.element_size(), b2t.data_ptr(), b3t.data_ptr(), any_val.data_ptr(), cls.data_ptr(),
+                                      prob.data_ptr(), bbox_2d.data_ptr(), bbox_3d.data_ptr(), C, labels.data_ptr(), targets.data_ptr(),
+                                      scores.data_ptr(), sampled.data_ptr(), g_cls.data_ptr(), g_2d.data_ptr(), g_3d.data_ptr(),
+                                      loss.data_ptr(), stats.data_ptr(), ctx.ws_base, ctx.ws_bytes, ops._stream()))
+    return loss, stats, dict(labels=labels, targets=targets, scores=scores, sampled=sampled, stats=stats, grads=(g_cls, g_2d, g_3d))
+
+
+class _RpnLossSmp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cls, bbox_2d, bbox_3d, prob, state, tgt):
+        loss, stats, state.out = _loss_smp(state, cls, prob, bbox_2d, bbox_3d, tgt)
+        ctx.save_for_backward(*state.out["grads"])
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        out = []
+        for g, need in zip(ctx.saved_tensors, ctx.needs_input_grad[:3]):
+            out.append(g * grad_loss if need else None)
+        return tuple(out) + (None, None, None)
+
+
+def rpn_loss_smp(cls, prob, bbox_2d, bbox_3d, target, anchors, conf_vec, feat_size, return_details=False):
+    """The loss layer below RPN_3D_loss_smp: (loss 0-d float32 device tensor with grad_fn, stats float64 device tensor [17]: the
+    STAT_NAMES slots, then the count of labels outside {0, 1 .. C-1, 3000} -- such rows were treated as ignored; a caller that
+    does not go through the module checks that slot).  ``return_details`` adds a dict with labels (int16), targets (packed
+    [B, R, 11]), scores, sampled and the stored gradients."""
+    n_anchors = anchors.shape[0]
+    B, R, H, W, C = _check_inputs("rpn_loss_smp", cls, prob, bbox_2d, bbox_3d, n_anchors, feat_size)
+    tgt = _target_tensors(target, B, R, cls.device)
+    state = _Ctx(anchors, conf_vec, None, feat_size, B, R, cls.device)
+    loss, stats = _RpnLossSmp.apply(cls, bbox_2d, bbox_3d, prob.detach(), state, tgt)
+    return (loss, stats, state.out) if return_details else (loss, stats)
+
+
+def stats_list_smp(block, cls_2d_lambda, bbox_3d_lambda, iou_2d_lambda):
+    """The stats list of the reference's RPN_3D_loss_smp (entries, order, presence rules: lib/loss/rpn_3d.py:1099-1357) from a
+    downloaded stat block: the 3-D term is named 'bbox3d', the 2-D term has no entry, 'ttloss' (the total) closes the fg branch.
+    'bg' is present whenever the classification term is on (the reference tests the length of a 2-tuple, lib/loss/rpn_3d.py:1103),
+    NaN -- its mean of nothing -- for a batch without a bg anchor."""
+    s = dict(zip(STAT_NAMES, [float(v) for v in block]))
+    out = []
+    if cls_2d_lambda and s["n_fg"] > 0:
+        out.append({'name': 'fg', 'val': s["acc_fg"], 'format': '{:0.2f}', 'group': 'acc'})
+    if cls_2d_lambda:
+        out.append({'name': 'bg', 'val': s["acc_bg"] if s["n_bg"] > 0 else float("nan"), 'format': '{:0.2f}', 'group': 'acc'})
+    if cls_2d_lambda and s["n_active"] > 0:
+        out.append({'name': 'cls', 'val': s["cls"], 'format': '{:0.4f}', 'group': 'loss'})
+    if s["fg_num"] > 0:
+        if bbox_3d_lambda:
+            out.append({'name': 'bbox3d', 'val': s["bbox_3d"], 'format': '{:0.4f}', 'group': 'loss'})
+        out.append({'name': 'z', 'val': s["z"], 'format': '{:0.2f}', 'group': 'misc'})
+        out.append({'name': 'ry', 'val': s["ry"], 'format': '{:0.2f}', 'group': 'misc'})
+        out.append({'name': 'iou', 'val': s["iou_acc"], 'format': '{:0.2f}', 'group': 'acc'})
+        if iou_2d_lambda:
+            out.append({'name': 'iou', 'val': s["iou_loss"], 'format': '{:0.4f}', 'group': 'loss'})
+        out.append({'name': 'ttloss', 'val': s["loss"], 'format': '{:0.4f}', 'group': 'loss'})
+    return out
+
+
+class RPN_3D_loss_smp(RPN_3D_loss):
+    """Drop-in for lib/loss/rpn_3d.py: RPN_3D_loss_smp -- same constructor fields, same ``forward`` signature and return; the
+    fifth argument of ``forward`` is the target dict (the loader's collated batch['target'], host or device, or the dict of
+    rpn_precompute_targets).  Nothing is uploaded before the first ``forward``.  Unlike the reference, the caller's ``bbox_2d``
+    and the dict's ``bbox_2d`` are left as they are (the reference de-normalises both in place), and ``bbox_2d_lambda != 0``
+    works (the reference raises NameError there) with the value RPN_3D_loss gives."""
+
     def __init__(self, conf):
-        super(RPN_3D_loss_smp, self).__init__()
-        raise NotImplementedError("RPN_3D_loss_smp is not supported: it consumes the targets the reference's data loader pre-computes")
+        if torch.device(conf.device).type != "cuda":
+            raise NotImplementedError("RPN_3D_loss_smp: conf.device=%s: no CPU fallback" % (conf.device,))
+        super(RPN_3D_loss_smp, self).__init__(conf)
+
+    def forward(self, cls, prob, bbox_2d, bbox_3d, imobjs, feat_size):
+        self._check_settings()
+        ops._require_cuda(cls, prob, bbox_2d, bbox_3d)
+        if cls.shape[2] != self.num_classes:
+            raise RuntimeError("RPN_3D_loss_smp: cls has %d classes, conf.lbls gives %d" % (cls.shape[2], self.num_classes))
+        self._upload_anchors(cls.device)
+        loss, stats, self.last = rpn_loss_smp(cls, prob, bbox_2d, bbox_3d, imobjs, self._anchors_dev, self._conf_vec(), feat_size,
+                                              return_details=True)
+        block = stats.cpu().numpy()                                            # the one download
+        if block[SMP_STAT_BAD_LABELS]:
+            raise RuntimeError("RPN_3D_loss_smp: %d labels are outside {0, 1 .. %d, %d}" % (int(block[SMP_STAT_BAD_LABELS]),
+                                                                                            self.num_classes - 1, IGN_FLAG))
+        return loss, stats_list_smp(block, self.cls_2d_lambda, self.bbox_3d_lambda, self.iou_2d_lambda)

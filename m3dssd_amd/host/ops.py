@@ -444,6 +444,21 @@ def rpn_loss(cls, prob, bbox_2d, bbox_3d, anchors, conf_vec, gt_table, feat_size
     return loss.rpn_loss(cls, prob, bbox_2d, bbox_3d, anchors, conf_vec, gt_table, feat_size, return_details)
 
 
+def rpn_precompute_targets(anchors, conf_vec, gt_table, feat_size, device):
+    """Kitti_Dataset_torch._targets (lib/dataloader.py:1014-1144) for a whole batch on the device, ahead of the forward:
+    m3d_rpn_precompute_targets.  Returns the dict RPN_3D_loss_smp / rpn_loss_smp take: labels, gt_index (int16 [B, R]), bbox_2d
+    (float32 [B, R, 4]), bbox_3d (float32 [B, R, 7]), meta: {any_val (int32 [B])}, all on ``device``."""
+    from . import loss
+    return loss.rpn_precompute_targets(anchors, conf_vec, gt_table, feat_size, device)
+
+
+def rpn_loss_smp(cls, prob, bbox_2d, bbox_3d, target, anchors, conf_vec, feat_size, return_details=False):
+    """The RPN_3D_loss_smp computation below the module: m3d_rpn_loss_smp over the pre-computed ``target`` dict (the reference's
+    collated batch['target'], host or device, or the dict of rpn_precompute_targets), differentiable in cls, bbox_2d, bbox_3d."""
+    from . import loss
+    return loss.rpn_loss_smp(cls, prob, bbox_2d, bbox_3d, target, anchors, conf_vec, feat_size, return_details)
+
+
 def nms_sorted(boxes_sorted, thresh):
     """Device NMS on score-sorted boxes [B, n, >=4] (or [n, >=4]) -> (keep [B, n] int32, num [B] int32)."""
     _require_cuda(boxes_sorted)

@@ -16,7 +16,17 @@ and latency.  Per-launch TIMES come from a kernel trace in a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o t -- python tools/rpn_loss_bench.py --reps 20 --no-cpu
     python tools/rpn_loss_bench.py --merge BENCH.json --stats-csv DIR/.../t_kernel_stats.csv      (no GPU needed)
 
-usage: python tools/rpn_loss_bench.py [--reps 50] [--warmup 5] [--batches 4 8] [--no-cpu]      (one JSON line per batch size)"""
+`--smp` times RPN_3D_loss_smp (m3d_rpn_loss_smp: ingest launch + launches 4-6) instead, against RPN_3D_loss on the same inputs
+in the same process, median of `--reps` with the interquartile range:
+  full_module      RPN_3D_loss.forward (as above)
+  smp_resident     RPN_3D_loss_smp.forward on the device dict of rpn_precompute_targets (int16 labels): no upload
+  smp_resident_i64 the same targets with int64 labels resident on the device (the loader's dtype)
+  smp_host         RPN_3D_loss_smp.forward on the loader's host dict (int64 labels, pageable tensors): staged through pinned
+                   memory and uploaded in every call
+  smp_host_pinned  the same dict with the three tensors pinned once
+  precompute       rpn_precompute_targets alone (gt packing excluded)
+
+usage: python tools/rpn_loss_bench.py [--reps 50] [--warmup 5] [--batches 4 8] [--no-cpu] [--smp]   (one JSON line per batch size)"""
 import argparse
 import csv
 import json
@@ -60,7 +70,8 @@ def timed(fn, warmup, reps):
         e1.synchronize()
         ts.append(e0.elapsed_time(e1))
     ts.sort()
-    return {"median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4)}
+    return {"median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4), "q1": round(ts[len(ts) // 4], 4),
+            "q3": round(ts[(3 * len(ts)) // 4], 4)}
 
 
 def merge(bench_json, stats_csv):
@@ -80,6 +91,40 @@ def merge(bench_json, stats_csv):
         print(json.dumps(res))
 
 
+def smp(a):
+    import numpy as np
+    import torch
+    from m3dssd_amd.host import loss as hl
+    from m3dssd_amd.host import ops
+    import rpn_loss_ref as RR
+    dev = torch.device("cuda:0")
+    for B in a.batches:
+        conf = RR.loss_conf((384, 1280), 0, device="cuda:0")
+        cls, prob, b2, b3, imobjs, fs = RR.make_case(40 + B, (384, 1280), B, a.gts)
+        ins = [t.to(dev) for t in (cls, prob, b2, b3)]
+        full, crit = hl.RPN_3D_loss(conf), hl.RPN_3D_loss_smp(conf)
+        vec = full._conf_vec()
+        table = hl.pack_gts(imobjs, conf.lbls, conf.ilbls, conf.min_gt_vis, conf.min_gt_h)
+        anchors = np.asarray(conf.anchors, dtype=np.float64)
+        pre = ops.rpn_precompute_targets(anchors, vec, table, fs, dev)
+        pre_i64 = dict(pre, labels=pre["labels"].long())
+        host = dict(labels=pre_i64["labels"].cpu(), bbox_2d=pre["bbox_2d"].cpu(), bbox_3d=pre["bbox_3d"].cpu(),
+                    meta=dict(any_val=pre["meta"]["any_val"].cpu().long()))
+        pinned = dict(host, labels=host["labels"].pin_memory(), bbox_2d=host["bbox_2d"].pin_memory(), bbox_3d=host["bbox_3d"].pin_memory())
+        res = {"tool": "rpn_loss_bench --smp", "B": B, "R": cls.shape[1], "gts_per_image": a.gts, "reps": a.reps, "warmup": a.warmup,
+               "host_dict_mbytes": round(sum(host[k].numel() * host[k].element_size() for k in ("labels", "bbox_2d", "bbox_3d")) / 1e6, 1)}
+        l_full, _ = full(*ins, imobjs, fs)
+        for name, tgt in (("smp_resident", pre), ("smp_resident_i64", pre_i64), ("smp_host", host), ("smp_host_pinned", pinned)):
+            l_smp, _ = crit(*ins, tgt, fs)
+            assert l_smp.cpu().numpy().tobytes() == l_full.cpu().numpy().tobytes(), name          # the same loss, bit for bit
+        res["full_module_ms"] = timed(lambda: full(*ins, imobjs, fs), a.warmup, a.reps)
+        for name, tgt in (("smp_resident", pre), ("smp_resident_i64", pre_i64), ("smp_host", host), ("smp_host_pinned", pinned)):
+            res[name + "_ms"] = timed(lambda: crit(*ins, tgt, fs), a.warmup, a.reps)
+        res["precompute_ms"] = timed(lambda: ops.rpn_precompute_targets(anchors, vec, table, fs, dev), a.warmup, a.reps)
+        res["full_module_again_ms"] = timed(lambda: full(*ins, imobjs, fs), a.warmup, a.reps)          # drift check: same as the first
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
@@ -87,6 +132,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[4, 8])
     ap.add_argument("--gts", type=int, default=3, help="ground truths per image (3: the size the CPU figure of the issue used)")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--smp", action="store_true", help="time RPN_3D_loss_smp against RPN_3D_loss")
     ap.add_argument("--merge")
     ap.add_argument("--stats-csv")
     a = ap.parse_args()
@@ -99,6 +145,8 @@ def main():
     from m3dssd_amd.host import loss as hl
     import rpn_loss_ref as RR
     torch.set_num_threads(min(16, os.cpu_count() or 1))
+    if a.smp:
+        return smp(a)
     dev = torch.device("cuda:0")
     for B in a.batches:
         conf = RR.loss_conf((384, 1280), 0)
