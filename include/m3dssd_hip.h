@@ -93,7 +93,8 @@ const char *m3d_last_error(void);
  *                  m3d_anab_attention_forward, m3d_anab_attention_backward, m3d_anab_attention_workspace_bytes (additive);
  *                  m3d_anab_attention_forward_bf16, m3d_anab_attention_backward_bf16,
  *                  m3d_anab_attention_workspace_bytes_bf16 (additive);
- *                  m3d_rpn_loss_smp, m3d_rpn_precompute_targets (additive). */
+ *                  m3d_rpn_loss_smp, m3d_rpn_precompute_targets (additive);
+ *                  m3d_refine_3d_host (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -970,6 +971,14 @@ int m3d_refine_3d(const float *aboxes, const int *counts, int B, int K, const do
 int m3d_refine_3d_ex(const float *aboxes, const int *counts, int B, int K, const double *p2, const double *p2_inv,
                      const float *scale, const float *clip_wh, double score_thresh, int hill_climbing, double step_r_init,
                      double r_lim, double *out, m3d_stream_t stream);
+/* Host twin of m3d_refine_3d_ex: the same arguments without the stream, every pointer a HOST pointer; synchronous, no device work.
+ * A plain loop over the B*K rows through the row function the kernel calls (like the m3d_eval_* host natives below).
+ * Angles: the reference's `while a > pi: a -= 2 pi` wrap does not terminate for a non-finite angle or |a| above ~1e17; here (kernel
+ * and twin) an angle beyond 64 turns, inf or NaN is reduced once with remainder(a, 2 pi) (inf / NaN -> NaN); within 64 turns the
+ * reference's loops run unchanged. */
+int m3d_refine_3d_host(const float *aboxes, const int *counts, int B, int K, const double *p2, const double *p2_inv,
+                       const float *scale, const float *clip_wh, double score_thresh, int hill_climbing, double step_r_init,
+                       double r_lim, double *out);
 
 /* ------------------------------------------------------------------------------------------
  * KITTI AP evaluator natives (lib/eval/eval.py, lib/eval/rotate_iou.py of the reference, which compiles them

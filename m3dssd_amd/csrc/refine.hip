@@ -10,6 +10,7 @@
 // mirrored: `box = aboxes[i]` holds np.float32 scalars, so x3d*z3d, y3d*z3d (rpn_util.py:1825,1836 and test_projection :2025,
 // where cx, cy, z arrive as np.float32), the box width / height (:1813-1814) and x + w - 1 (:2022-2023) are ROUNDED TO FLOAT32
 // before they widen into the float64 arithmetic; np.float32 + Python float (the angle conversions, ry3d +- step) is float64.
+// The per-row body is a __host__ __device__ function: m3d_refine_3d_host loops over it on the host (tests compare the two).
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -28,8 +29,15 @@ struct RefineArgs {
 
 #define REF_PI 3.141592653589793
 
-__device__ __forceinline__ double wrap_pi(double a)
+// The two loops are the reference's (lib/util.py:516-535) and run as they stand for |a| <= 64 * 2 pi (at most 64 turns; results in
+// that range keep their bits).  DEPARTURE FROM THE REFERENCE: beyond that range, or for a non-finite a, the reference's loops do
+// not terminate (a - 2 pi == a above ~1e17, inf - 2 pi == inf) -- one overflowed alpha would hang the launch.  Such an angle is
+// reduced once with remainder(a, 2 pi), which lands in [-pi, pi]; inf and NaN become NaN, for which both loop tests are false.
+#define REF_WRAP_LOOP_MAX (64 * (REF_PI * 2))
+
+__host__ __device__ __forceinline__ double wrap_pi(double a)
 {
+    if (!(fabs(a) <= REF_WRAP_LOOP_MAX)) a = remainder(a, REF_PI * 2);
     while (a > REF_PI) a -= REF_PI * 2;
     while (a < (-REF_PI)) a += REF_PI * 2;
     return a;
@@ -38,9 +46,9 @@ __device__ __forceinline__ double wrap_pi(double a)
 // test_projection: returns ol, sets *invalid
 // bx, by, bw, bh, cx, cy are float32 values (the row's np.float32 scalars); z_f32: z is still the row's float32 depth (always,
 // for the depth step of 0 the reference passes) -> the products round to float32 like np.float32 * np.float32
-__device__ double test_projection_dev(const double *p2, const double *pi, float bxf, float byf, float bwf, float bhf, float cxf,
-                                      float cyf, double z, bool z_f32, double w3d, double h3d, double l3d, double rot,
-                                      bool *invalid)
+__host__ __device__ double test_projection_dev(const double *p2, const double *pi, float bxf, float byf, float bwf, float bhf,
+                                               float cxf, float cyf, double z, bool z_f32, double w3d, double h3d, double l3d,
+                                               double rot, bool *invalid)
 {
     const double bx = bxf, by = byf;
     const double x2 = (double)((bxf + bwf) - 1.0f), y2 = (double)((byf + bhf) - 1.0f);
@@ -73,10 +81,10 @@ __device__ double test_projection_dev(const double *p2, const double *pi, float 
     return -(fabs(bx - xn) + fabs(by - yn) + fabs(x2 - xm) + fabs(y2 - ym));
 }
 
-__global__ void refine3d_kernel(const RefineArgs a)
+// One row i of [B*K]: shared by the kernel (one thread per row) and by m3d_refine_3d_host (a plain loop), so that the host twin
+// runs the same arithmetic in the same order.
+__host__ __device__ inline void refine3d_row(const RefineArgs &a, int i)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.B * a.K) return;
     const int b = i / a.K, k = i - b * a.K;
     double *o = a.out + (size_t)i * 16;
     const float *r = a.aboxes + (size_t)i * 14;
@@ -149,19 +157,48 @@ __global__ void refine3d_kernel(const RefineArgs a)
     o[7] = h3d; o[8] = w3d; o[9] = l3d; o[10] = X; o[11] = Y + h3d / 2; o[12] = Z; o[13] = ry; o[14] = score; o[15] = 0.0;
 }
 
-extern "C" int m3d_refine_3d_ex(const float *aboxes, const int *counts, int B, int K, const double *p2, const double *p2_inv,
-                                const float *scale, const float *clip_wh, double score_thresh, int hill_climbing,
-                                double step_r_init, double r_lim, double *out, m3d_stream_t stream)
+__global__ void refine3d_kernel(const RefineArgs a)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.B * a.K) return;
+    refine3d_row(a, i);
+}
+
+static int fill_args(RefineArgs &a, const float *aboxes, const int *counts, int B, int K, const double *p2, const double *p2_inv,
+                     const float *scale, const float *clip_wh, double score_thresh, int hill_climbing, double step_r_init,
+                     double r_lim, double *out)
 {
     M3D_REQUIRE(aboxes && counts && p2 && p2_inv && out && B >= 1 && K >= 1, "refine_3d: bad arguments");
     M3D_REQUIRE(step_r_init >= 0 && r_lim >= 0, "refine_3d: negative step / limit");
-    RefineArgs a;
     a.aboxes = aboxes; a.counts = counts; a.p2 = p2; a.p2_inv = p2_inv; a.out = out; a.B = B; a.K = K;
     a.scale = scale; a.clip_wh = clip_wh;
     a.hill_climbing = hill_climbing; a.score_thresh = score_thresh; a.step_r_init = step_r_init; a.r_lim = r_lim;
     a.step_z_init = 0.0; a.z_lim = 0.0; a.min_ol_dif = 0.0;                   // the values test_kitti_3d passes (:1833)
+    return M3D_OK;
+}
+
+extern "C" int m3d_refine_3d_ex(const float *aboxes, const int *counts, int B, int K, const double *p2, const double *p2_inv,
+                                const float *scale, const float *clip_wh, double score_thresh, int hill_climbing,
+                                double step_r_init, double r_lim, double *out, m3d_stream_t stream)
+{
+    RefineArgs a;
+    const int rc = fill_args(a, aboxes, counts, B, K, p2, p2_inv, scale, clip_wh, score_thresh, hill_climbing, step_r_init, r_lim, out);
+    if (rc != M3D_OK) return rc;
     hipLaunchKernelGGL(refine3d_kernel, dim3(cdiv(B * K, 64)), dim3(64), 0, (hipStream_t)stream, a);
     M3D_LAUNCH_CHECK();
+    return M3D_OK;
+}
+
+// Host twin of m3d_refine_3d_ex: every pointer is a HOST pointer, synchronous, no device work -- the same row function in a plain
+// loop (the precedent: the m3d_eval_* host natives).
+extern "C" int m3d_refine_3d_host(const float *aboxes, const int *counts, int B, int K, const double *p2, const double *p2_inv,
+                                  const float *scale, const float *clip_wh, double score_thresh, int hill_climbing,
+                                  double step_r_init, double r_lim, double *out)
+{
+    RefineArgs a;
+    const int rc = fill_args(a, aboxes, counts, B, K, p2, p2_inv, scale, clip_wh, score_thresh, hill_climbing, step_r_init, r_lim, out);
+    if (rc != M3D_OK) return rc;
+    for (int i = 0; i < B * K; ++i) refine3d_row(a, i);
     return M3D_OK;
 }
 
