@@ -713,6 +713,20 @@ int m3d_preprocess_u8(const unsigned char *frames_bgr, int N, int img_h, int img
 int m3d_stem_conv7x7_u8(const unsigned char *frames_bgr, int img_h, int img_w, const float *mean3, const float *stds3,
                         const float *wgt, const float *scale, const float *shift, float *out, int out_cs, int N, int H, int W,
                         m3d_stream_t stream);
+/* Training input path of the reference (lib/augmentations.py:164-234,236-469: photometric distortion, mirror, scale-and-shift warp
+ * to H x W, Normalize; then BGR -> RGB, HWC -> CHW) for N uint8 BGR frames that share one [N][hmax][wmax][3] buffer, in one launch
+ * per 16 images.  The random decisions are the host's: `params` is a HOST pointer to N rows of `param_stride` doubles
+ * (>= M3D_AUGMENT_PARAMS), which travel to the kernel as launch arguments (no upload, no device allocation):
+ *   [0] h  [1] w           the image's own size, <= hmax x wmax
+ *   [2] mode               0 no photometric step, 1 contrast first, 2 contrast last
+ *   [3] delta [4] alpha [5] sat [6] hue     brightness, contrast, saturation, hue shift in degrees (|hue| <= 360); [7] reserved
+ *   [8..13] Minv           row-major 2x3: (x_src, y_src) = Minv . (x, y, 1), evaluated in float64; a mirror is folded in by the host
+ * Bilinear taps at the exact source coordinate; a tap outside h x w is 0 AFTER the photometric step, so the border normalises to
+ * (0 - mean) / std.  mean / stds: HOST pointers to 3 floats, indexed by BGR position.  Everything is validated before the first
+ * launch (M3D_E_ARG: null pointer, N < 1, a size above the buffer's, a non-finite parameter, a singular Minv).  Deterministic. */
+#define M3D_AUGMENT_PARAMS 14
+int m3d_augment_u8(const unsigned char *frames_bgr, int N, int hmax, int wmax, const double *params, int param_stride,
+                   const float *mean3, const float *stds3, float *out_nchw, int H, int W, m3d_stream_t stream);
 /* 3x3, 16 -> 16, stride 1, pad 1 (DLA level0, pose_dla_dcn.py:341-342) as a direct VALU convolution: NHWC in/out,
  * wgt [(i*3+j)*16 + cin][16 cout], fused affine (folded BN) + LeakyReLU. */
 int m3d_conv3x3_c16(const float *in, int in_cs, const float *wgt, const float *scale, const float *shift, float *out,

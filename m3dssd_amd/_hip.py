@@ -199,6 +199,8 @@ SIGNATURES = {
     "m3d_refine_3d_host": (c_int, [P, P, c_int, c_int, P, P, P, P, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, P]),
     "m3d_preprocess_u8": (c_int, [P, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), P, c_int,
                                   c_int, P]),
+    "m3d_augment_u8": (c_int, [P, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int, ctypes.POINTER(ctypes.c_float),
+                               ctypes.POINTER(ctypes.c_float), P, c_int, c_int, P]),
     "m3d_stem_conv7x7_u8": (c_int, [P, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), P, P, P, P,
                                     c_int, c_int, c_int, c_int, P]),
     "m3d_conv3x3_c16": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, P]),
