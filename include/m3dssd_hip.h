@@ -24,6 +24,8 @@
  *                                 lib/rpn_util.py:430-532 (host numpy in the reference) and the backward autograd derives
  *   m3d_rpn_loss_smp ........... RPN_3D_loss_smp.forward, lib/loss/rpn_3d.py:705-1360 (targets pre-computed by the loader)
  *   m3d_rpn_precompute_targets . Kitti_Dataset_torch._targets, lib/dataloader.py:1014-1144, for a whole batch
+ *   m3d_rpn_target_stats ....... the per-image sums of compute_bbox_stats, lib/rpn_util.py:732-889 (it calls the numpy
+ *                                 compute_targets twice per image of the imdb; float64 rois, unlike the loss)
  *   _nms / m3d_nms_sorted_dev .. void _nms(int* keep_out, int* num_out, const float* boxes_host,
  *                                 int boxes_num, int boxes_dim, float nms_overlap_thresh, int device_id)
  *                                 lib/nms/gpu_nms.hpp:1-2, lib/nms/nms_kernel.cu:91-144 (kernel :34-78)
@@ -94,7 +96,8 @@ const char *m3d_last_error(void);
  *                  m3d_anab_attention_forward_bf16, m3d_anab_attention_backward_bf16,
  *                  m3d_anab_attention_workspace_bytes_bf16 (additive);
  *                  m3d_rpn_loss_smp, m3d_rpn_precompute_targets (additive);
- *                  m3d_refine_3d_host (additive). */
+ *                  m3d_refine_3d_host (additive);
+ *                  m3d_rpn_target_stats, m3d_rpn_target_stats_workspace_bytes (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -688,6 +691,25 @@ int m3d_rpn_loss_smp(const double *anchors, int A, int H, int W, const double *c
                      const float *prob, const float *bbox_2d, const float *bbox_3d, int C, short *labels, float *targets,
                      float *scores, unsigned char *sampled, float *grad_cls, float *grad_bbox_2d, float *grad_bbox_3d,
                      float *loss, double *stats, void *workspace, long long workspace_bytes, m3d_stream_t stream);
+
+/* The reduction compute_bbox_stats (lib/rpn_util.py:732-889) makes of compute_targets, per image on the device: launches 1-3 of
+ * m3d_rpn_targets with the reducing form of launch 3, then one finish launch.  anchors, gt_table, Gmax and the thresholds and
+ * stride of `conf` as for m3d_rpn_precompute_targets; the means, stds and loss settings of `conf` are NOT read (nor checked).
+ * Unlike the loss path, the anchor boxes stay FLOAT64 here through the overlaps and the transforms, as the reference's
+ * compute_bbox_stats has them (it does not cast locate_anchors' result; the loss does).
+ *   center  device, float64 [11]: subtracted from every transform (zeros for the pass that finds the means, the means for the
+ *           pass that finds the stds).
+ *   out     device, float64 [B, M3D_RPN_TARGET_STATS_COLS]; per image over its fg rows: n_fg, then sum(t32 - center) for the 11
+ *           columns (2-D dx dy dw dh, 3-D x y z w h l ry), then sum((t32 - center)^2) for the 11 columns.  t32 is the raw
+ *           transform (mean 0, std 1) rounded to float32 like the reference's array; differences, squares and sums are float64.
+ *           An image with n_valid = 0 gives a zero row.
+ * No float atomics, fixed summation order: an image's row holds the same bits whatever batch, batch slot or workspace contents
+ * it is computed with.  Workspace: m3d_rpn_target_stats_workspace_bytes(B, R), contents irrelevant on entry. */
+#define M3D_RPN_TARGET_STATS_COLS 23
+long long m3d_rpn_target_stats_workspace_bytes(int B, long long R);
+int m3d_rpn_target_stats(const double *anchors, int A, int H, int W, const double *conf, int n_conf, const double *gt_table, int B,
+                         int Gmax, const double *center, double *out, void *workspace, long long workspace_bytes,
+                         m3d_stream_t stream);
 
 /* Weight packing: [Cout, Cin, kh, kw] (torch layout) -> [Cout_pad, kh*kw*Cin_pad] (tap-major, zero pad). */
 int m3d_pack_conv_weight(const float *w, float *packed, int Cout, int Cout_pad, int Cin, int Cin_pad, int kh,

@@ -190,6 +190,8 @@ SIGNATURES = {
     "m3d_rpn_loss": (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, c_int, P, P, P, P, P, P, P, P, P, P, c_ll, P]),
     "m3d_rpn_precompute_targets": (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, P, P, P, c_ll, P]),
     "m3d_rpn_loss_smp": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, P, P, P, P, P, P, c_int] + [P] * 10 + [c_ll, P]),
+    "m3d_rpn_target_stats_workspace_bytes": (c_ll, [c_int, c_ll]),
+    "m3d_rpn_target_stats": (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, c_ll, P]),
     "m3d_pack_conv_weight": (c_int, [P, P] + [c_int] * 6 + [P]),
     "m3d_nchw_to_nhwc": (c_int, [P, P] + [c_int] * 5 + [P]),
     "m3d_nhwc_to_nchw": (c_int, [P, c_int, P] + [c_int] * 4 + [P]),

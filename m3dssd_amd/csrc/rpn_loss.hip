@@ -15,8 +15,15 @@
 // unsigned 32-bit vector atomic min), launch 3 recomputes the same bits once more and assigns.  Integer max / min / add only:
 // the result does not depend on arrival order.
 //
+// m3d_rpn_target_stats (compute_bbox_stats, lib/rpn_util.py:732-889: the means and stds of the raw transforms over a dataset) runs
+// launches 1-3 with the roi kept in FLOAT64 -- that function hands locate_anchors' float64 array over without the loss' cast --
+// so the roi arithmetic is generic over its scalar type (RpnRoiT<T>); T = float is the loss path, bit for bit what it was.
+//
 // Launches (m3d_rpn_targets: 1-3, m3d_rpn_loss: 4-6; m3d_rpn_precompute_targets: 1-3 without cls / prob; m3d_rpn_loss_smp: the
-// ingest launch, then 4-6):
+// ingest launch, then 4-6; m3d_rpn_target_stats: 1, 2, 3S, S):
+//   3S rpn_stats_kernel      launch 3's decisions on float64 rois; writes no labels and no targets: per workgroup n_fg and the
+//                            float64 sums of (t32 - center) and its square over the fg rows, t32 the float32-rounded transform
+//   S rpn_stats_finish_kernel per image: adds its workgroups' partials in a fixed order -> out[b][23]
 //   1 rpn_gt_max_kernel     per anchor x valid gt: overlap -> max of its bits over 1 024 anchors on chip, one atomic max per gt
 //   2 rpn_gt_row_kernel     per anchor x valid gt: overlap == max -> atomic min of the row per gt
 //   3 rpn_assign_kernel     per anchor: row max / arg-max, ignore overlap, label, gt index, the 11 normalised regression targets,
@@ -75,7 +82,9 @@ static RpnWs rpn_ws_layout(void *base, int B, long long R)
     return w;
 }
 
-static int rpn_conf_from(const double *c, int n, RpnConf *o, const char *who)
+// assign_only (m3d_rpn_target_stats): only the thresholds and the stride are read; means, stds and the loss settings are not
+// checked (the caller is about to compute the means and stds).
+static int rpn_conf_from(const double *c, int n, RpnConf *o, const char *who, bool assign_only = false)
 {
     M3D_REQUIRE(c && n == M3D_RPN_CONF_COUNT, "%s: conf must hold M3D_RPN_CONF_COUNT = %d doubles (got %d)", who, M3D_RPN_CONF_COUNT, n);
     for (int i = 0; i < 11; ++i) { o->mean[i] = c[M3D_RPN_CONF_MEANS + i]; o->stdv[i] = c[M3D_RPN_CONF_STDS + i]; }
@@ -84,8 +93,9 @@ static int rpn_conf_from(const double *c, int n, RpnConf *o, const char *who)
     o->box_samples = c[M3D_RPN_CONF_BOX_SAMPLES]; o->fg_fraction = c[M3D_RPN_CONF_FG_FRACTION]; o->focal = c[M3D_RPN_CONF_FOCAL];
     o->lam_cls = c[M3D_RPN_CONF_LAMBDA_CLS]; o->lam_iou = c[M3D_RPN_CONF_LAMBDA_IOU];
     o->lam_2d = c[M3D_RPN_CONF_LAMBDA_2D]; o->lam_3d = c[M3D_RPN_CONF_LAMBDA_3D]; o->stride = c[M3D_RPN_CONF_STRIDE];
-    for (int i = 0; i < 11; ++i) M3D_REQUIRE(o->stdv[i] != 0.0 && isfinite(o->stdv[i]) && isfinite(o->mean[i]), "%s: bbox_means / bbox_stds must be finite, stds non-zero", who);
     M3D_REQUIRE(o->stride > 0, "%s: feat_stride must be positive", who);
+    if (assign_only) return M3D_OK;
+    for (int i = 0; i < 11; ++i) M3D_REQUIRE(o->stdv[i] != 0.0 && isfinite(o->stdv[i]) && isfinite(o->mean[i]), "%s: bbox_means / bbox_stds must be finite, stds non-zero", who);
     M3D_REQUIRE(o->box_samples > 0, "%s: box_samples must be positive or inf", who);
     M3D_REQUIRE(isinf(o->box_samples) || (o->fg_fraction >= 0 && o->fg_fraction <= 1),
                 "%s: a finite box_samples needs fg_fraction in [0, 1] (the reference multiplies by it)", who);
@@ -95,44 +105,53 @@ static int rpn_conf_from(const double *c, int n, RpnConf *o, const char *who)
 }
 
 // ---- shared geometry ---------------------------------------------------------------------------------------------------
-struct RpnRoi {
-    float x1, y1, x2, y2;
+// T is the scalar type the roi reaches compute_targets in: float for the loss (locate_anchors(...).float()), double for the
+// dataset statistics (compute_bbox_stats hands the float64 rois of locate_anchors over as they are).  T = float is the
+// arithmetic this file always had; both instantiations evaluate the same expressions in the same order.
+template <typename T>
+struct RpnRoiT {
+    T x1, y1, x2, y2;
     int a;
 };
+typedef RpnRoiT<float> RpnRoi;
 
-__device__ __forceinline__ RpnRoi rpn_roi(const double *__restrict__ anchors, int r, int H, int W, double stride)
+template <typename T>
+__device__ __forceinline__ RpnRoiT<T> rpn_roi(const double *__restrict__ anchors, int r, int H, int W, double stride)
 {
-    RpnRoi o;
+    RpnRoiT<T> o;
     const int hw = H * W;
     o.a = r / hw;
     const int rem = r - o.a * hw;
     const int h = rem / W, w = rem - h * W;
     const double sx = (double)w * stride, sy = (double)h * stride;
     const double *an = anchors + o.a * 9;
-    o.x1 = (float)(sx + an[0]);
-    o.y1 = (float)(sy + an[1]);
-    o.x2 = (float)(sx + an[2]);
-    o.y2 = (float)(sy + an[3]);
+    o.x1 = (T)(sx + an[0]);
+    o.y1 = (T)(sy + an[1]);
+    o.x2 = (T)(sx + an[2]);
+    o.y2 = (T)(sy + an[3]);
     return o;
 }
 
-__device__ __forceinline__ double rpn_inter(const RpnRoi &q, const double *g)
+template <typename T>
+__device__ __forceinline__ double rpn_inter(const RpnRoiT<T> &q, const double *g)
 {
     const double iw = fmax(fmin((double)q.x2, g[2]) - fmax((double)q.x1, g[0]), 0.0);
     const double ih = fmax(fmin((double)q.y2, g[3]) - fmax((double)q.y1, g[1]), 0.0);
     return iw * ih;
 }
 // g: x1 y1 x2 y2 area
-__device__ __forceinline__ double rpn_iou(const RpnRoi &q, double area_a, const double *g)
+template <typename T>
+__device__ __forceinline__ double rpn_iou(const RpnRoiT<T> &q, double area_a, const double *g)
 {
     const double inter = rpn_inter(q, g);
     const double uni = (area_a + g[4]) - inter;
     return inter / uni;
 }
-__device__ __forceinline__ double rpn_roi_area(const RpnRoi &q)
+template <typename T>
+__device__ __forceinline__ double rpn_roi_area(const RpnRoiT<T> &q)
 {
-    const float w = q.x2 - q.x1, h = q.y2 - q.y1;
-    const float a = w * h;
+    const T w = q.x2 - q.x1, h = q.y2 - q.y1;
+    const T a = w * h;
     return (double)a;
 }
 
@@ -163,8 +182,16 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     return v;
 }
 
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // ---- launch 1 ----------------------------------------------------------------------------------------------------------
 #define RPN_MAX_ROWS 4          // rows per thread of launch 1: 1024 anchors share one atomic per gt
+template <typename T>
 __global__ __launch_bounds__(RPN_TPB) void rpn_gt_max_kernel(const double *__restrict__ anchors, const double *__restrict__ gt, int Gmax,
                                                              int R, int H, int W, double stride, unsigned long long *__restrict__ gtmax)
 {
@@ -174,14 +201,14 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_gt_max_kernel(const double *__res
     int nv, ni;
     rpn_load_gts(gt, Gmax, b, sg, nv, ni);
     if (nv == 0) return;
-    RpnRoi q[RPN_MAX_ROWS];
+    RpnRoiT<T> q[RPN_MAX_ROWS];
     double area[RPN_MAX_ROWS];
     bool live[RPN_MAX_ROWS];
 #pragma unroll
     for (int u = 0; u < RPN_MAX_ROWS; ++u) {
         const int r = (blockIdx.x * RPN_MAX_ROWS + u) * RPN_TPB + threadIdx.x;
         live[u] = r < R;
-        q[u] = rpn_roi(anchors, live[u] ? r : 0, H, W, stride);
+        q[u] = rpn_roi<T>(anchors, live[u] ? r : 0, H, W, stride);
         area[u] = rpn_roi_area(q[u]);
     }
     for (int g = 0; g < nv; ++g) {
@@ -205,6 +232,7 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_gt_max_kernel(const double *__res
 }
 
 // ---- launch 2 ----------------------------------------------------------------------------------------------------------
+template <typename T>
 __global__ __launch_bounds__(RPN_TPB) void rpn_gt_row_kernel(const double *__restrict__ anchors, const double *__restrict__ gt, int Gmax,
                                                              int R, int H, int W, double stride,
                                                              const unsigned long long *__restrict__ gtmax, unsigned *__restrict__ bestrow)
@@ -216,7 +244,7 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_gt_row_kernel(const double *__res
     if (nv == 0) return;
     const int r = blockIdx.x * RPN_TPB + threadIdx.x;
     const bool live = r < R;
-    RpnRoi q = rpn_roi(anchors, live ? r : 0, H, W, stride);
+    const RpnRoiT<T> q = rpn_roi<T>(anchors, live ? r : 0, H, W, stride);
     const double area = rpn_roi_area(q);
     for (int g = 0; g < nv; ++g) {
         const double v = rpn_iou(q, area, sg[g]);
@@ -251,6 +279,70 @@ __device__ __forceinline__ float rpn_norm(double t, double mean, double stdv)
     return (float)((double)s / stdv);
 }
 
+struct RpnRow {
+    int label, gidx;
+    bool is_fg, is_bg;
+};
+
+// One row of an image with a valid gt (nv > 0): the label decision and the raw (not normalised) transforms t[0..10], 0 where the
+// row is not fg.  Shared by every form of launch 3; T as in RpnRoiT.
+template <typename T>
+__device__ __forceinline__ RpnRow rpn_assign_row(const double *__restrict__ anchors, const double *__restrict__ gt,
+                                                 const unsigned long long *__restrict__ gtmax, const unsigned *__restrict__ bestrow,
+                                                 int Gmax, int H, int W, int b, int r, bool live, int nv, int ni,
+                                                 const double (*sg)[5], const RpnConf &cf, double *t)
+{
+    RpnRow o;
+    o.label = 0;
+    o.gidx = -1;
+    const RpnRoiT<T> q = rpn_roi<T>(anchors, live ? r : 0, H, W, cf.stride);
+    const double area = rpn_roi_area(q);
+    double ols_max = -1.0;
+    int arg = 0;
+    bool best = false;
+    for (int g = 0; g < nv; ++g) {
+        const double v = rpn_iou(q, area, sg[g]);
+        if (v > ols_max) { ols_max = v; arg = g; }
+        const unsigned long long mx = gtmax[b * M3D_RPN_MAX_GT + g];
+        best = best || (bestrow[b * M3D_RPN_MAX_GT + g] == (unsigned)r && __longlong_as_double((long long)mx) >= cf.best_thresh);
+    }
+    double ign_max = 0.0;      // np.zeros when the image has no ignore region
+    for (int g = nv; g < nv + ni; ++g) {
+        const double v = rpn_inter(q, sg[g]) / area;
+        if (v > ign_max) ign_max = v;
+    }
+    o.is_fg = (ols_max >= cf.fg_thresh) || best;
+    const bool is_ign = ign_max >= cf.ign_thresh;
+    o.is_bg = (ols_max >= cf.bg_lo) && (ols_max < cf.bg_hi) && !is_ign && !o.is_fg;
+    const double *grow = gt + ((size_t)b * (Gmax + 1) + 1 + arg) * M3D_RPN_GT_COLS;
+#pragma unroll
+    for (int i = 0; i < 11; ++i) t[i] = 0.0;
+    if (o.is_fg) {
+        o.gidx = arg;
+        o.label = (int)grow[4];
+        // bbox_transform / bbox_transform_3d: the roi side in T (the dtype of the roi array), the gt side in float64
+        const T ex_w = q.x2 - q.x1 + (T)1.0, ex_h = q.y2 - q.y1 + (T)1.0;
+        const T ex_cx = q.x1 + (T)0.5 * (ex_w - (T)1.0), ex_cy = q.y1 + (T)0.5 * (ex_h - (T)1.0);
+        const double gw = grow[2] - grow[0] + 1.0, gh = grow[3] - grow[1] + 1.0;
+        const double gcx = grow[0] + 0.5 * (gw - 1.0), gcy = grow[1] + 0.5 * (gh - 1.0);
+        t[0] = (gcx - (double)ex_cx) / (double)ex_w;
+        t[1] = (gcy - (double)ex_cy) / (double)ex_h;
+        t[2] = log(gw / (double)ex_w);
+        t[3] = log(gh / (double)ex_h);
+        const double *an = anchors + q.a * 9;
+        t[4] = (grow[5] - (double)ex_cx) / (double)ex_w;
+        t[5] = (grow[6] - (double)ex_cy) / (double)ex_h;
+        t[6] = grow[7] - an[4];
+        t[7] = log(grow[8] / an[5]);
+        t[8] = log(grow[9] / an[6]);
+        t[9] = log(grow[10] / an[7]);
+        t[10] = grow[11] - an[8];
+    } else if (!o.is_bg) {
+        o.label = RPN_IGN_LABEL;
+    }
+    return o;
+}
+
 // PRE (m3d_rpn_precompute_targets): no cls / prob, so no score, no accuracy count; labels, gt index and target bits as without
 template <bool PRE>
 __global__ __launch_bounds__(RPN_TPB) void rpn_assign_kernel(RpnAssignArgs A, RpnConf cf)
@@ -270,52 +362,9 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_assign_kernel(RpnAssignArgs A, Rp
 #pragma unroll
     for (int i = 0; i < 11; ++i) tar[i] = 0.f;
     if (nv > 0) {
-        RpnRoi q = rpn_roi(A.anchors, live ? r : 0, A.H, A.W, cf.stride);
-        const double area = rpn_roi_area(q);
-        double ols_max = -1.0;
-        int arg = 0;
-        bool best = false;
-        for (int g = 0; g < nv; ++g) {
-            const double v = rpn_iou(q, area, sg[g]);
-            if (v > ols_max) { ols_max = v; arg = g; }
-            const unsigned long long mx = A.gtmax[b * M3D_RPN_MAX_GT + g];
-            best = best || (A.bestrow[b * M3D_RPN_MAX_GT + g] == (unsigned)r && __longlong_as_double((long long)mx) >= cf.best_thresh);
-        }
-        double ign_max = 0.0;      // np.zeros when the image has no ignore region
-        for (int g = nv; g < nv + ni; ++g) {
-            const double v = rpn_inter(q, sg[g]) / area;
-            if (v > ign_max) ign_max = v;
-        }
-        is_fg = (ols_max >= cf.fg_thresh) || best;
-        const bool is_ign = ign_max >= cf.ign_thresh;
-        is_bg = (ols_max >= cf.bg_lo) && (ols_max < cf.bg_hi) && !is_ign && !is_fg;
-        const double *grow = A.gt + ((size_t)b * (A.Gmax + 1) + 1 + arg) * M3D_RPN_GT_COLS;
         double t[11];
-#pragma unroll
-        for (int i = 0; i < 11; ++i) t[i] = 0.0;
-        if (is_fg) {
-            gidx = arg;
-            label = (int)grow[4];
-            // bbox_transform / bbox_transform_3d: the roi side in float32 (a float32 array), the gt side in float64
-            const float ex_w = q.x2 - q.x1 + 1.0f, ex_h = q.y2 - q.y1 + 1.0f;
-            const float ex_cx = q.x1 + 0.5f * (ex_w - 1.0f), ex_cy = q.y1 + 0.5f * (ex_h - 1.0f);
-            const double gw = grow[2] - grow[0] + 1.0, gh = grow[3] - grow[1] + 1.0;
-            const double gcx = grow[0] + 0.5 * (gw - 1.0), gcy = grow[1] + 0.5 * (gh - 1.0);
-            t[0] = (gcx - (double)ex_cx) / (double)ex_w;
-            t[1] = (gcy - (double)ex_cy) / (double)ex_h;
-            t[2] = log(gw / (double)ex_w);
-            t[3] = log(gh / (double)ex_h);
-            const double *an = A.anchors + q.a * 9;
-            t[4] = (grow[5] - (double)ex_cx) / (double)ex_w;
-            t[5] = (grow[6] - (double)ex_cy) / (double)ex_h;
-            t[6] = grow[7] - an[4];
-            t[7] = log(grow[8] / an[5]);
-            t[8] = log(grow[9] / an[6]);
-            t[9] = log(grow[10] / an[7]);
-            t[10] = grow[11] - an[8];
-        } else if (!is_bg) {
-            label = RPN_IGN_LABEL;
-        }
+        const RpnRow o = rpn_assign_row<float>(A.anchors, A.gt, A.gtmax, A.bestrow, A.Gmax, A.H, A.W, b, r, live, nv, ni, sg, cf, t);
+        label = o.label; gidx = o.gidx; is_fg = o.is_fg; is_bg = o.is_bg;
 #pragma unroll
         for (int i = 0; i < 11; ++i) tar[i] = rpn_norm(t[i], cf.mean[i], cf.stdv[i]);
     } else {
@@ -359,6 +408,84 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_assign_kernel(RpnAssignArgs A, Rp
     }
     __syncthreads();
     if (threadIdx.x < 4 && sc[threadIdx.x]) atomicAdd(&A.counts[b * 8 + threadIdx.x], sc[threadIdx.x]);
+}
+
+// ---- launch 3, reducing form + its finish launch (m3d_rpn_target_stats) ----------------------------------------------------
+// compute_bbox_stats (lib/rpn_util.py:732-889) needs, per image, the count of the fg rows and the sums of their raw transforms
+// -- not the rows.  Same decisions as launch 3 on float64 rois; the transform is rounded to float32 (the reference's
+// `transforms` array), then (t32 - center) and its square are taken and added in float64: a thread's one row, the lane butterfly,
+// the waves in order -> one partial block per workgroup; the finish launch adds an image's blocks strided, then a tree.  No
+// atomics: an image's sums depend on nothing but its own table, R and the launch shape that R fixes.
+#define RPN_NS M3D_RPN_TARGET_STATS_COLS          // n_fg, 11 sums, 11 sums of squares
+struct RpnStatsArgs {
+    const double *anchors, *gt, *center;
+    const unsigned long long *gtmax;
+    const unsigned *bestrow;
+    double *partials;          // [B][gridDim.x][RPN_NS]
+    int Gmax, R, H, W;
+};
+
+__global__ __launch_bounds__(RPN_TPB) void rpn_stats_kernel(RpnStatsArgs A, RpnConf cf)
+{
+    __shared__ double sg[M3D_RPN_MAX_GT][5];
+    __shared__ double sw[RPN_TPB / 64][RPN_NS];
+    const int b = blockIdx.y;
+    int nv, ni;
+    rpn_load_gts(A.gt, A.Gmax, b, sg, nv, ni);
+    const int r = blockIdx.x * RPN_TPB + threadIdx.x;
+    const bool live = r < A.R;
+    bool is_fg = false;
+    double q[RPN_NS];
+#pragma unroll
+    for (int k = 0; k < RPN_NS; ++k) q[k] = 0.0;
+    if (nv > 0) {
+        double t[11];
+        const RpnRow o = rpn_assign_row<double>(A.anchors, A.gt, A.gtmax, A.bestrow, A.Gmax, A.H, A.W, b, r, live, nv, ni, sg, cf, t);
+        is_fg = live && o.is_fg;
+        if (is_fg) {
+            q[0] = 1.0;
+#pragma unroll
+            for (int i = 0; i < 11; ++i) {
+                const float t32 = (float)t[i];
+                const double d = (double)t32 - A.center[i];
+                q[1 + i] = d;
+                q[12 + i] = d * d;
+            }
+        }
+    }
+    const bool any = __ballot(is_fg) != 0ull;          // most waves hold no fg row: their sums are 0 without the butterfly
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < RPN_NS; ++k) {
+        const double v = any ? wave_sum_f64(q[k]) : 0.0;
+        if ((threadIdx.x & 63) == 0) sw[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < RPN_NS) {
+        double v = sw[0][threadIdx.x];
+        for (int w = 1; w < RPN_TPB / 64; ++w) v += sw[w][threadIdx.x];
+        A.partials[((size_t)b * gridDim.x + blockIdx.x) * RPN_NS + threadIdx.x] = v;
+    }
+}
+
+#define RPN_SFIN_L 32          // thread (l, k): quantity k of the workgroups l, l + 32, ...; then a tree over l
+__global__ __launch_bounds__(RPN_SFIN_L * 32) void rpn_stats_finish_kernel(const double *__restrict__ partials, int nwg, double *__restrict__ out)
+{
+    __shared__ double red[RPN_SFIN_L][RPN_NS];
+    const int k = threadIdx.x & 31, l = threadIdx.x >> 5, b = blockIdx.x;
+    const bool on = k < RPN_NS;
+    if (on) {
+        const double *p = partials + (size_t)b * nwg * RPN_NS;
+        double v = 0.0;
+        for (int j = l; j < nwg; j += RPN_SFIN_L) v += p[(size_t)j * RPN_NS + k];
+        red[l][k] = v;
+    }
+    __syncthreads();
+    for (int s = RPN_SFIN_L / 2; s > 0; s >>= 1) {
+        if (on && l < s) red[l][k] += red[l + s][k];
+        __syncthreads();
+    }
+    if (on && l == 0) out[(size_t)b * RPN_NS + k] = red[0][k];
 }
 
 // ---- ingest (RPN_3D_loss_smp) ---------------------------------------------------------------------------------------------
@@ -641,13 +768,6 @@ __device__ __forceinline__ RpnTotals rpn_totals(const unsigned *sel, int B, cons
     return t;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ double smooth_l1(double d, double &g)
 {
     const double a = fabs(d);
@@ -739,7 +859,7 @@ __global__ __launch_bounds__(RPN_TPB) void rpn_loss_kernel(RpnLossArgs A, RpnCon
             o3[k] = (float)(cf.lam_3d * inv_fg * g);
         }
         // ---- z / ry in absolute units (the anchor's own z / ry cancels in exact arithmetic; kept as the reference has it)
-        RpnRoi roi = rpn_roi(A.anchors, r, A.H, A.W, cf.stride);
+        RpnRoi roi = rpn_roi<float>(A.anchors, r, A.H, A.W, cf.stride);
         const double *an = A.anchors + roi.a * 9;
         const double zt = an[4] + ((double)tr[6] * cf.stdv[6] + cf.mean[6]), zp = an[4] + ((double)p3[2] * cf.stdv[6] + cf.mean[6]);
         const double rt = an[8] + ((double)tr[10] * cf.stdv[10] + cf.mean[10]), rp = an[8] + ((double)p3[6] * cf.stdv[10] + cf.mean[10]);
@@ -923,9 +1043,9 @@ extern "C" int m3d_rpn_targets(const double *anchors, int A, int H, int W, const
     M3D_HIP(hipMemsetAsync(ws.bestrow, 0xff, (size_t)B * M3D_RPN_MAX_GT * 4, s));
     M3D_HIP(hipMemsetAsync(ws.counts, 0, (size_t)B * 8 * 4, s));
     const dim3 grid(cdiv(R, RPN_TPB), B);
-    hipLaunchKernelGGL(rpn_gt_max_kernel, dim3(cdiv(R, RPN_TPB * RPN_MAX_ROWS), B), dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax);
+    hipLaunchKernelGGL(rpn_gt_max_kernel<float>, dim3(cdiv(R, RPN_TPB * RPN_MAX_ROWS), B), dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax);
     M3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rpn_gt_row_kernel, grid, dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax, ws.bestrow);
+    hipLaunchKernelGGL(rpn_gt_row_kernel<float>, grid, dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax, ws.bestrow);
     M3D_LAUNCH_CHECK();
     RpnAssignArgs a;
     a.anchors = anchors; a.gt = gt_table; a.cls = cls; a.prob = prob; a.gtmax = ws.gtmax; a.bestrow = ws.bestrow;
@@ -1009,9 +1129,9 @@ extern "C" int m3d_rpn_precompute_targets(const double *anchors, int A, int H, i
     M3D_HIP(hipMemsetAsync(ws.gtmax, 0, (size_t)B * M3D_RPN_MAX_GT * 8, s));
     M3D_HIP(hipMemsetAsync(ws.bestrow, 0xff, (size_t)B * M3D_RPN_MAX_GT * 4, s));
     const dim3 grid(cdiv(R, RPN_TPB), B);
-    hipLaunchKernelGGL(rpn_gt_max_kernel, dim3(cdiv(R, RPN_TPB * RPN_MAX_ROWS), B), dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax);
+    hipLaunchKernelGGL(rpn_gt_max_kernel<float>, dim3(cdiv(R, RPN_TPB * RPN_MAX_ROWS), B), dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax);
     M3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rpn_gt_row_kernel, grid, dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax, ws.bestrow);
+    hipLaunchKernelGGL(rpn_gt_row_kernel<float>, grid, dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax, ws.bestrow);
     M3D_LAUNCH_CHECK();
     RpnAssignArgs a;
     a.anchors = anchors; a.gt = gt_table; a.cls = nullptr; a.prob = nullptr; a.gtmax = ws.gtmax; a.bestrow = ws.bestrow;
@@ -1062,4 +1182,65 @@ extern "C" int m3d_rpn_loss_smp(const double *anchors, int A, int H, int W, cons
     M3D_LAUNCH_CHECK();
     return rpn_launch_loss("rpn_loss_smp", anchors, H, W, cf, nullptr, 0, any_val, B, R, cls, bbox_2d, bbox_3d, C, labels, targets, scores,
                            sampled, grad_cls, grad_bbox_2d, grad_bbox_3d, loss, stats, ws, s);
+}
+
+// ---- dataset statistics (compute_bbox_stats, lib/rpn_util.py:732-889) ----------------------------------------------------------
+struct RpnStatsWs {
+    unsigned long long *gtmax;   // [B][M3D_RPN_MAX_GT]
+    unsigned *bestrow;           // [B][M3D_RPN_MAX_GT]
+    double *partials;            // [B][cdiv(R, RPN_TPB)][RPN_NS]
+    long long total;
+};
+
+static RpnStatsWs rpn_stats_ws_layout(void *base, int B, long long R)
+{
+    RpnStatsWs w;
+    char *p = (char *)base;
+    long long o = 0;
+    w.gtmax = (unsigned long long *)(p + o); o += (long long)B * M3D_RPN_MAX_GT * 8;
+    w.bestrow = (unsigned *)(p + o); o += (long long)B * M3D_RPN_MAX_GT * 4;
+    o = (o + 255) / 256 * 256;
+    w.partials = (double *)(p + o); o += (long long)B * cdiv(R, RPN_TPB) * RPN_NS * 8;
+    w.total = o;
+    return w;
+}
+
+extern "C" long long m3d_rpn_target_stats_workspace_bytes(int B, long long R)
+{
+    if (B <= 0 || R <= 0) return -1;
+    return rpn_stats_ws_layout(nullptr, B, R).total;
+}
+
+extern "C" int m3d_rpn_target_stats(const double *anchors, int A, int H, int W, const double *conf, int n_conf, const double *gt_table,
+                                    int B, int Gmax, const double *center, double *out, void *workspace, long long workspace_bytes,
+                                    m3d_stream_t stream)
+{
+    long long R;
+    RpnConf cf;
+    int st = rpn_check_shape("rpn_target_stats", A, H, W, B, 2, Gmax, &R);
+    if (st) return st;
+    if ((st = rpn_conf_from(conf, n_conf, &cf, "rpn_target_stats", true))) return st;
+    M3D_REQUIRE(anchors && gt_table && center && out && workspace, "rpn_target_stats: NULL pointer");
+    const RpnStatsWs ws = rpn_stats_ws_layout(workspace, B, R);
+    if (workspace_bytes < ws.total) {
+        m3d_set_error("rpn_target_stats: workspace %lld < %lld bytes (m3d_rpn_target_stats_workspace_bytes)", workspace_bytes, ws.total);
+        return M3D_E_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    M3D_HIP(hipMemsetAsync(ws.gtmax, 0, (size_t)B * M3D_RPN_MAX_GT * 8, s));
+    M3D_HIP(hipMemsetAsync(ws.bestrow, 0xff, (size_t)B * M3D_RPN_MAX_GT * 4, s));
+    const int nwg = cdiv(R, RPN_TPB);
+    const dim3 grid(nwg, B);
+    hipLaunchKernelGGL(rpn_gt_max_kernel<double>, dim3(cdiv(R, RPN_TPB * RPN_MAX_ROWS), B), dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rpn_gt_row_kernel<double>, grid, dim3(RPN_TPB), 0, s, anchors, gt_table, Gmax, (int)R, H, W, cf.stride, ws.gtmax, ws.bestrow);
+    M3D_LAUNCH_CHECK();
+    RpnStatsArgs a;
+    a.anchors = anchors; a.gt = gt_table; a.center = center; a.gtmax = ws.gtmax; a.bestrow = ws.bestrow; a.partials = ws.partials;
+    a.Gmax = Gmax; a.R = (int)R; a.H = H; a.W = W;
+    hipLaunchKernelGGL(rpn_stats_kernel, grid, dim3(RPN_TPB), 0, s, a, cf);
+    M3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rpn_stats_finish_kernel, dim3(B), dim3(RPN_SFIN_L * 32), 0, s, ws.partials, nwg, out);
+    M3D_LAUNCH_CHECK();
+    return M3D_OK;
 }

@@ -356,6 +356,45 @@ def rpn_precompute_targets(anchors, conf_vec, gt_table, feat_size, device):
     return dict(labels=labels, gt_index=gt_index, bbox_2d=b2t, bbox_3d=b3t, meta=dict(any_val=any_val))
 
 
+TARGET_STATS_COLS = 23          # M3D_RPN_TARGET_STATS_COLS: n_fg, 11 sums, 11 sums of squares
+
+
+def rpn_target_stats(anchors, conf_vec, gt_table, feat_size, center=None, device="cuda:0"):
+    """What ``compute_bbox_stats`` (lib/rpn_util.py:732-889) needs of ``compute_targets``, per image, on the device
+    (m3d_rpn_target_stats): float64 [B, 23] = n_fg, sum(t - center) and sum((t - center)^2) of the 11 raw float32 transforms over
+    the fg rows.  The anchor boxes stay float64 (the reference's statistics do not cast them; its loss does).  ``center``:
+    11 values, default zeros.  Of ``conf_vec`` only the thresholds and the stride are read."""
+    dev = anchors.device if torch.is_tensor(anchors) else torch.device(device)
+    if dev.type != "cuda":
+        raise NotImplementedError("rpn_target_stats: device=%s: no CPU fallback" % (dev,))
+    L = _hip.lib()
+    anc = anchors if torch.is_tensor(anchors) else torch.from_numpy(np.ascontiguousarray(np.asarray(anchors, dtype=np.float64))).to(dev)
+    if anc.dtype != torch.float64 or anc.dim() != 2 or anc.shape[1] != 9 or not anc.is_contiguous():
+        raise RuntimeError("rpn_target_stats: anchors must be float64 [A, 9] (x1 y1 x2 y2 z w h l ry)")
+    gt_table = np.ascontiguousarray(gt_table, dtype=np.float64)
+    if gt_table.ndim != 3 or gt_table.shape[2] != GT_COLS or gt_table.shape[1] < 1 or gt_table.shape[0] < 1:
+        raise RuntimeError("rpn_target_stats: gt table must be [B, Gmax + 1, %d] (got %s)" % (GT_COLS, gt_table.shape))
+    if (gt_table[:, 0, :2] < 0).any() or (gt_table[:, 0, 0] + gt_table[:, 0, 1] > gt_table.shape[1] - 1).any():
+        raise RuntimeError("rpn_target_stats: gt table counts exceed its rows")
+    B, Gmax = int(gt_table.shape[0]), int(gt_table.shape[1]) - 1
+    H, W = int(feat_size[0]), int(feat_size[1])
+    A = int(anc.shape[0])
+    vec = np.ascontiguousarray(conf_vec, dtype=np.float64)
+    c = np.zeros(11, dtype=np.float64) if center is None else np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(-1))
+    if c.size != 11:
+        raise RuntimeError("rpn_target_stats: center must hold 11 values (got %d)" % c.size)
+    nbytes = L.m3d_rpn_target_stats_workspace_bytes(B, A * H * W)
+    ws = torch.empty(max(nbytes, 0) + 256, device=dev, dtype=torch.uint8)
+    ws_base = (ws.data_ptr() + 255) // 256 * 256
+    gt = torch.from_numpy(gt_table).to(dev)
+    cen = torch.from_numpy(c).to(dev)
+    out = torch.empty(B, TARGET_STATS_COLS, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _hip.check(L.m3d_rpn_target_stats(anc.data_ptr(), A, H, W, vec.ctypes.data, int(vec.size), gt.data_ptr(), B, Gmax,
+                                          cen.data_ptr(), out.data_ptr(), ws_base, nbytes, ops._stream()))
+    return out
+
+
 def _upload(t, device):
     """A device tensor as it is; a host tensor through pinned memory (staged where it is not pinned already)."""
     if t.is_cuda:

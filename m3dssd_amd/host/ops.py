@@ -459,6 +459,14 @@ def rpn_loss_smp(cls, prob, bbox_2d, bbox_3d, target, anchors, conf_vec, feat_si
     return loss.rpn_loss_smp(cls, prob, bbox_2d, bbox_3d, target, anchors, conf_vec, feat_size, return_details)
 
 
+def rpn_target_stats(anchors, conf_vec, gt_table, feat_size, center=None, device="cuda:0"):
+    """The per-image sums compute_bbox_stats (lib/rpn_util.py:732-889) takes over compute_targets, on the device with float64 anchor
+    boxes: m3d_rpn_target_stats.  Returns float64 [B, 23] on the device: n_fg, sum(t - center) and sum((t - center)^2) of the 11
+    raw float32 transforms over each image's fg rows.  ``gt_table`` from ``host.dataset_stats.pack_gts_scaled``."""
+    from . import loss
+    return loss.rpn_target_stats(anchors, conf_vec, gt_table, feat_size, center, device)
+
+
 def nms_sorted(boxes_sorted, thresh):
     """Device NMS on score-sorted boxes [B, n, >=4] (or [n, >=4]) -> (keep [B, n] int32, num [B] int32)."""
     _require_cuda(boxes_sorted)
