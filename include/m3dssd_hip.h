@@ -97,7 +97,9 @@ const char *m3d_last_error(void);
  *                  m3d_anab_attention_workspace_bytes_bf16 (additive);
  *                  m3d_rpn_loss_smp, m3d_rpn_precompute_targets (additive);
  *                  m3d_refine_3d_host (additive);
- *                  m3d_rpn_target_stats, m3d_rpn_target_stats_workspace_bytes (additive). */
+ *                  m3d_rpn_target_stats, m3d_rpn_target_stats_workspace_bytes (additive);
+ *                  m3d_dcn_v2_backward_det, m3d_dcn_v2_backward_det_bf16, m3d_dcn_v2_backward_det_workspace_bytes,
+ *                  m3d_dcn_v2_backward_det_workspace_bytes_bf16 (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -538,6 +540,41 @@ int m3d_dcn_v2_backward_bf16(const void *input, const void *weight, const void *
                              int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
                              int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
                              int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
+
+/* The two backward calls with a bitwise-reproducible grad_input (csrc/dcn_op.hip): the argument lists, restrictions, error codes
+ * and messages of m3d_dcn_v2_backward / m3d_dcn_v2_backward_bf16, a workspace of m3d_dcn_v2_backward_det_workspace_bytes[_bf16]()
+ * bytes (never smaller than the float form's: the staging buffer of grad_input doubles; -1 where the float queries return -1).
+ * grad_offset, grad_mask, grad_weight and grad_bias take the same path and have the bits of the float form.  grad_input is a
+ * function of the inputs alone: the same bits on every launch, and for an image alone or inside any batch.
+ *   - Every contribution gcol * mask * w_q is the fp32 value the float form adds.  It is scaled by 2^s_n (exact), rounded to the
+ *     nearest integer and added into a 64-bit integer sum (integer atomics: addition is associative); the finished sum is
+ *     converted to fp32 (round to nearest), scaled by 2^-s_n (exact) and, for bf16, rounded once more to bf16.
+ *   - s_n is chosen per image n and deformable group from order-independent maxima: A_n = max |grad_output[n]|, W_g = max over
+ *     (channel of the group, tap) of sum_co |weight[co][c][tap]|, M_n = max |mask[n, group]|.  With 2^E > 2 A_n W_g M_n (one spare
+ *     bit for the rounding of the GEMM) and T = Ho*Wo*kh*kw contributions at most per element, s_n = 62 - E - ceil(log2 T): no
+ *     input can overflow the sum (DESIGN.md has the argument).  Resolution: 2^-s_n = 2^(E + ceil(log2 T) - 62), 45 bits below 2^E
+ *     on a 48x160 map with a 3x3 kernel.
+ *   - Differences from the float form: if A_n, W_g or M_n is not finite (a NaN or infinity in grad_output[n], the weights or the
+ *     masks of image n), or their product reaches 2^126, grad_input of image n (that group's channels) is all NaN; if the product
+ *     is zero that grad_input is zero.  Non-finite offsets are treated as in the float form (outside, zero gradients). */
+long long m3d_dcn_v2_backward_det_workspace_bytes(int batch, int channels, int height, int width, int channels_out,
+                                                  int kernel_h, int kernel_w, int stride, int pad, int dilation,
+                                                  int deformable_group);
+int m3d_dcn_v2_backward_det(const float *input, const float *weight, const float *offset, const float *mask,
+                            const float *grad_output,
+                            float *grad_input, float *grad_offset, float *grad_mask, float *grad_weight, float *grad_bias,
+                            int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
+                            int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
+                            int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
+long long m3d_dcn_v2_backward_det_workspace_bytes_bf16(int batch, int channels, int height, int width, int channels_out,
+                                                       int kernel_h, int kernel_w, int stride, int pad, int dilation,
+                                                       int deformable_group);
+int m3d_dcn_v2_backward_det_bf16(const void *input, const void *weight, const void *offset, int offset_is_bf16, const void *mask,
+                                 int mask_is_bf16, const void *grad_output,
+                                 void *grad_input, float *grad_offset, float *grad_mask, void *grad_weight, float *grad_bias,
+                                 int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
+                                 int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
+                                 int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Deformable position-sensitive RoI pooling (csrc/psroi_pool.hip): the drop-ins for dcn_v2_psroi_pooling_cuda_forward /

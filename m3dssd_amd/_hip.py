@@ -182,6 +182,10 @@ SIGNATURES = {
     "m3d_dcn_v2_forward_bf16": (c_int, [P, P, P, P, c_int, P, c_int, P] + [c_int] * 14 + [P, c_ll, P]),
     "m3d_dcn_v2_backward_workspace_bytes_bf16": (c_ll, [c_int] * 11),
     "m3d_dcn_v2_backward_bf16": (c_int, [P, P, P, c_int, P, c_int, P] + [P] * 5 + [c_int] * 14 + [P, c_ll, P]),
+    "m3d_dcn_v2_backward_det_workspace_bytes": (c_ll, [c_int] * 11),
+    "m3d_dcn_v2_backward_det": (c_int, [P] * 10 + [c_int] * 14 + [P, c_ll, P]),
+    "m3d_dcn_v2_backward_det_workspace_bytes_bf16": (c_ll, [c_int] * 11),
+    "m3d_dcn_v2_backward_det_bf16": (c_int, [P, P, P, c_int, P, c_int, P] + [P] * 5 + [c_int] * 14 + [P, c_ll, P]),
     "m3d_dcn_v2_psroi_pooling_workspace_bytes": (c_ll, [c_int] * 10),
     "m3d_dcn_v2_psroi_pooling_forward": (c_int, [P] * 5 + [c_int] * 8 + [c_float] + [c_int] * 5 + [c_float, P, c_ll, P]),
     "m3d_dcn_v2_psroi_pooling_backward": (c_int, [P] * 6 + [c_int] * 8 + [c_float] + [c_int] * 5 + [c_float, P, c_ll, P]),

@@ -47,6 +47,20 @@
 //
 // Determinism: grad_offset, grad_mask, grad_weight, grad_bias are bitwise reproducible (fixed reduction orders).  grad_input is
 // accumulated with float atomics, as the reference does (dcn_v2_im2col_cuda.cu:234): its last bits depend on arrival order.
+// m3d_dcn_v2_backward_det / _det_bf16 are the same driver and the same sampling code with a compile-time switch (DET) for the one
+// step that differs, and make grad_input a function of the inputs alone -- the same bits on every launch, and for an image alone
+// or inside any batch.  Contract and mechanism: each contribution gcol * mask * w_q, the fp32 value of the float form, is scaled by
+// 2^s_n (exact), rounded to the nearest integer and added into a 64-bit integer staging buffer (integer addition is associative);
+// the finish converts to fp32 (round to nearest), scales by 2^-s_n (exact) and, for bf16, rounds once more.  s_n = 62 - E -
+// ceil(log2(Ho*Wo*kh*kw)) with 2^E > 2 A_n W_g M_n, from the order-independent maxima A_n = max |grad_out[n]|, W_g = max over
+// (channel, tap) of sum_co |W|, M_n = max |mask[n, group]| (three small reduction kernels, read by the sampling kernel from the
+// workspace: the host never sees s_n); DESIGN.md has the argument that no input can overflow the sum.  Resolution: 2^-s_n, 45 bits
+// below 2^E on a 48x160 map with a 3x3 kernel.  Non-finite rule (the difference from the float form): a NaN / infinity in grad_out[n],
+// the weights or the masks of image n (or a bound of 2^126 and more) makes the whole grad_input of that image and group NaN; a zero
+// bound gives zeros; non-finite offsets are dcn_corners' business in both forms.  Measured cost (MI355X, bs 8,
+// profiles/dcn_backward_det_bench.jsonl): the full call takes 1.39x to 1.56x the float form in fp32, 1.66x to 2.04x in bf16; the
+// 64-bit atomics move twice the bytes at the byte rate of the fp32 ones.  With torch.use_deterministic_algorithms set the host
+// layer takes this form (ops.set_dcn_deterministic), and every HIP operator of the training step is then bitwise reproducible.
 // Every non-NULL gradient is OVERWRITTEN (the reference accumulates into grad_weight / grad_bias and adds into a zeroed
 // grad_input); a NULL gradient pointer = not wanted, and the work only it needs is skipped.
 #include <limits.h>
@@ -76,6 +90,7 @@ struct DcnF32 {
     static constexpr int wgrad_rows(int co_pad) { return co_pad % 128 ? 64 : 128; }   // rows (co) of a weight-gradient tile
     static constexpr long long max_in_elems = 1ll << 31, max_go_elems = LLONG_MAX;    // NHWC input / grad_out elements
     static constexpr const char *bwd_name = "dcn_v2_backward", *bwd_query = "m3d_dcn_v2_backward_workspace_bytes";
+    static constexpr const char *det_name = "dcn_v2_backward_det", *det_query = "m3d_dcn_v2_backward_det_workspace_bytes";
     static __device__ __forceinline__ float load(float v) { return v; }
     static __device__ __forceinline__ float store(float v) { return v; }
 };
@@ -87,6 +102,7 @@ struct DcnBf16 {
     static constexpr int wgrad_rows(int) { return 64; }
     static constexpr long long max_in_elems = 1ll << 30, max_go_elems = 1ll << 30;
     static constexpr const char *bwd_name = "dcn_v2_backward_bf16", *bwd_query = "m3d_dcn_v2_backward_workspace_bytes_bf16";
+    static constexpr const char *det_name = "dcn_v2_backward_det_bf16", *det_query = "m3d_dcn_v2_backward_det_workspace_bytes_bf16";
     static __device__ __forceinline__ float load(u16 v) { return bf16_bits_to_f32(v); }
     static __device__ __forceinline__ u16 store(float v) { return f32_to_bf16_bits(v); }
 };
@@ -162,6 +178,108 @@ __global__ void dcn_nhwc_f32_to_nchw_kernel(const float *__restrict__ in, int in
             v = in[i];
             for (int s = 1; s < nsum; ++s) v += in[i + (size_t)s * sum_stride];
         }
+        t[r][tx] = v;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+        const int c = c0 + r, p = p0 + tx;
+        if (c < C && p < HW) out[((size_t)n * Ctot + c0s + c) * HW + p] = E::store(t[tx][r]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The deterministic grad_input (m3d_dcn_v2_backward_det*): 64-bit fixed point with one binary exponent per image.
+//
+// sexp[n] = s_n: a contribution v (fp32) enters the sum as rint(v * 2^s_n), the finished element is fp32(sum) * 2^-s_n.  One value of
+// sexp[n] is no exponent: DCN_SEXP_NAN = the bound of image n is not finite, its grad_input is NaN, nothing is added.
+#define DCN_SEXP_NAN INT_MIN
+
+__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
+__device__ __forceinline__ float dcn_widen(float v) { return v; }
+__device__ __forceinline__ float dcn_widen(u16 v) { return bf16_bits_to_f32(v); }
+
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, off));
+    return v;
+}
+
+// out[n] = max over rows r < rows, channels [c0, c0 + cn) of |src[(n*rows + r)*cs + c]| as the BIT PATTERN of the absolute value:
+// unsigned order is the order of the magnitudes, an infinity lies above every finite value and a NaN above the infinity, so the
+// maximum both finds the largest magnitude and keeps a NaN.  A maximum does not depend on the order it is taken in (the atomic
+// is an integer maximum).  out[] zeroed by the caller.
+template <class T>
+__global__ __launch_bounds__(256) void dcn_absmax_kernel(const T *__restrict__ src, int rows, int cs, int c0, int cn,
+                                                         unsigned *__restrict__ out)
+{
+    const int n = blockIdx.y;
+    const long long total = (long long)rows * cn;
+    const T *img = src + (size_t)n * rows * cs + c0;
+    unsigned m = 0;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / cn;
+        m = max(m, abs_bits(dcn_widen(img[r * cs + (i - r * cn)])));
+    }
+    m = wave_max_u32(m);
+    if ((threadIdx.x & 63) == 0) atomicMax(out + n, m);
+}
+
+// out[0] = max over the rows (tap, channel) of the transposed weight pack [rows][cs] of sum_co |p[row][co]| (bit pattern, as above);
+// one wave per row, fixed summation order
+template <class T>
+__global__ __launch_bounds__(256) void dcn_wsum_max_kernel(const T *__restrict__ p, int rows, int cs, unsigned *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float s = 0.f;
+    for (int c = lane; c < cs; c += 64) s += fabsf(dcn_widen(p[(size_t)row * cs + c]));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) atomicMax(out, abs_bits(s));
+}
+
+// sexp[n] from A_n = amax[n] (grad_out), M_n = mmax[n] (masks of this group), W_g = wmax[0]; log2T = ceil(log2(Ho*Wo*kh*kw)).
+// Bound of one contribution: |gcol * mask * w_q| <= A W M in exact arithmetic; the GEMM, the weight sums and the two products round,
+// each by a relative 2^-24 per term, which one spare bit covers: with 2^e > A W M every contribution is below 2^(e + 1) = 2^E.
+// The product is formed in double (no overflow, no underflow); E > 127 counts as not finite (fp32 gcol may have overflowed).
+__global__ void dcn_sexp_kernel(const unsigned *__restrict__ amax, const unsigned *__restrict__ mmax, const unsigned *__restrict__ wmax,
+                                int *__restrict__ sexp, int N, int log2T)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const unsigned a = amax[n], m = mmax[n], w = wmax[0];
+    int s;
+    if (a >= 0x7F800000u || m >= 0x7F800000u || w >= 0x7F800000u) {
+        s = DCN_SEXP_NAN;
+    } else {
+        const double b = (double)__uint_as_float(a) * (double)__uint_as_float(m) * (double)__uint_as_float(w);
+        if (b == 0.0) {
+            s = 0;                                               // every contribution is zero
+        } else {
+            const int E = ilogb(b) + 2;
+            s = E > 127 ? DCN_SEXP_NAN : 62 - E - log2T;
+        }
+    }
+    sexp[n] = s;
+}
+
+// 64-bit sums [N*HW][in_cs] -> channel slice [c0s, c0s + C) of an NCHW tensor with Ctot channels: fp32(sum) * 2^-sexp[n] (the
+// conversion rounds to nearest, the scaling is exact), one more rounding to the stored type for bf16; NaN where sexp[n] says so
+template <class E>
+__global__ void dcn_nhwc_i64_to_nchw_kernel(const long long *__restrict__ in, int in_cs, const int *__restrict__ sexp,
+                                            typename E::T *__restrict__ out, int C, int HW, int Ctot, int c0s)
+{
+    __shared__ float t[32][33];
+    const int n = blockIdx.z, c0 = blockIdx.y * 32, p0 = blockIdx.x * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int s = sexp[n];
+    for (int r = ty; r < 32; r += 8) {
+        const int p = p0 + r, c = c0 + tx;
+        float v = 0.f;
+        if (c < C && p < HW)
+            v = s == DCN_SEXP_NAN ? __uint_as_float(0x7FC00000u) : ldexpf(__ll2float_rn(in[((size_t)n * HW + p) * in_cs + c]), -s);
         t[r][tx] = v;
     }
     __syncthreads();
@@ -408,10 +526,11 @@ struct DcnSampleArgs {
     const float *om;           // [P][om_cs]: 2k = dh, 2k+1 = dw, 2kk + k = mask
     const float *gcol;         // fp32 [P][kk*cp] or NULL (then only col is produced)
     typename E::T *col;        // [P][kk*cp] or NULL
-    float *gin;                // fp32 [N*H*W][cp], zeroed, or NULL
+    float *gin;                // fp32 [N*H*W][cp], zeroed, or NULL; the deterministic form: long long [N*H*W][cp], zeroed
     float *goff, *gmask;       // fp32 NCHW, already moved to this group's first channel, or NULL
     long long goff_img, gmask_img;   // floats between images of goff / gmask
     int P, H, W, Ho, Wo, cp, kh, kw, stride, pad, dil, om_cs;
+    const int *sexp;           // the deterministic form: [N], the fixed-point exponent of each image (DCN_SEXP_NAN: add nothing)
 };
 
 __device__ __forceinline__ float and_not(float v, int drop) { return __uint_as_float(__float_as_uint(v) & ~(unsigned)drop); }
@@ -427,7 +546,10 @@ __device__ __forceinline__ float wave_sum(float v)    // butterfly over the 64 l
 // The corner state of a tap is the same in every lane; whether a corner row gets its atomic add is decided on the scalar unit
 // (readfirstlane + scalar branch), not through a lane mask.  Everything after the load of a corner value and before the store
 // of col is fp32 whatever the element type.
-template <class E>
+// DET (a compile-time choice: the float form carries no trace of it): the contribution gm * w_q, the same fp32 value, is scaled by
+// 2^sexp[n] (exact), rounded to the nearest integer and added with a 64-bit integer atomic -- integer addition is associative, so
+// the sum does not depend on arrival order.  One atomic wave-instruction is 64 lanes x 8 bytes = 512 contiguous bytes.
+template <class E, bool DET>
 __global__ __launch_bounds__(256) void dcn_sample_kernel(DcnSampleArgs<E> a)
 {
     const int lane = threadIdx.x & 63;
@@ -441,6 +563,8 @@ __global__ __launch_bounds__(256) void dcn_sample_kernel(DcnSampleArgs<E> a)
     const float *omp = a.om + (size_t)p * a.om_cs;
     const size_t img = (size_t)n * a.H * a.W * a.cp;
     const typename E::T *inb = a.in + img;
+    int sn = 0;
+    if constexpr (DET) sn = a.gin ? __builtin_amdgcn_readfirstlane(a.sexp[n]) : 0;
     for (int k = 0; k < kk; ++k) {
         const int i = k / a.kw, j = k - i * a.kw;
         const float dh = omp[2 * k], dw = omp[2 * k + 1], mk = omp[2 * kk + k];
@@ -474,10 +598,19 @@ __global__ __launch_bounds__(256) void dcn_sample_kernel(DcnSampleArgs<E> a)
                 sw += g * (dww[0] * v[0] + dww[1] * v[1] + dww[2] * v[2] + dww[3] * v[3]);
                 if (a.gin) {
                     const float gm = g * mk;
-                    float *gb = a.gin + img + c;
+                    if constexpr (DET) {
+                        unsigned long long *gb = (unsigned long long *)a.gin + img + c;
+                        if (sn != DCN_SEXP_NAN) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (keep[q]) atomicAdd(gb + row[q], gm * w[q]);
+                            for (int q = 0; q < 4; ++q)
+                                if (keep[q]) atomicAdd(gb + row[q], (unsigned long long)__float2ll_rn(ldexpf(gm * w[q], sn)));
+                        }
+                    } else {
+                        float *gb = a.gin + img + c;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (keep[q]) atomicAdd(gb + row[q], gm * w[q]);
+                    }
                 }
             }
         }
@@ -712,14 +845,15 @@ __global__ void dcn_reduce_kernel(const float *__restrict__ slab, const float *_
 
 // ================================================================================================== backward: workspace
 struct DcnBwdWs {
-    long long in_off, om_off, go_off, wt_off, gcol_off, col_off, gin_off, slab_off, bslab_off, total;
+    long long in_off, om_off, go_off, wt_off, gcol_off, col_off, gin_off, slab_off, bslab_off, stat_off, total;
     int cp, co_pad, om_cs, ho, wo, K, splits, chunk;
 };
 
 // `c` = channels of ONE deformable group.  The layout does not depend on which gradients are wanted.  in / go / wt / col hold
-// elements of the operator's type; om, gcol, the grad_input staging buffer and the slabs are fp32.
+// elements of the operator's type; om, gcol, the grad_input staging buffer and the slabs are fp32.  `det`: the staging buffer holds
+// 64-bit sums and a last region holds the statistics of the exponent: amax[n], mmax[n], wmax[1] (unsigned), sexp[n] (int).
 template <class E>
-static DcnBwdWs dcn_bwd_ws(int n, int c, int h, int w, int co, int kh, int kw, int stride, int pad, int dil)
+static DcnBwdWs dcn_bwd_ws(int n, int c, int h, int w, int co, int kh, int kw, int stride, int pad, int dil, bool det)
 {
     DcnBwdWs s;
     s.cp = (int)rup(c, 64);          // the sampling kernel runs whole waves of 64 channels
@@ -744,32 +878,52 @@ static DcnBwdWs dcn_bwd_ws(int n, int c, int h, int w, int co, int kh, int kw, i
     s.wt_off = o;    o += rup((long long)s.K * s.co_pad * E::size, 256);
     s.gcol_off = o;  o += rup(P * s.K * 4, 256);
     s.col_off = o;   o += rup(P * s.K * E::size, 256);
-    s.gin_off = o;   o += rup((long long)n * h * w * s.cp * 4, 256);
+    s.gin_off = o;   o += rup((long long)n * h * w * s.cp * (det ? 8 : 4), 256);
     s.slab_off = o;  o += rup((long long)s.splits * s.co_pad * s.K * 4, 256);
     s.bslab_off = o; o += rup((long long)s.splits * s.co_pad * 4, 256);
+    s.stat_off = o;
+    if (det) o += rup(((long long)3 * n + 1) * 4, 256);
     s.total = o;
     return s;
 }
 
 template <class E>
-static long long dcn_bwd_ws_bytes(int n, int c, int h, int w, int co, int kh, int kw, int stride, int pad, int dil, int G)
+static long long dcn_bwd_ws_bytes(int n, int c, int h, int w, int co, int kh, int kw, int stride, int pad, int dil, int G, bool det)
 {
     if (!dcn_query_ok(E::is_bf16, n, c, h, w, co, kh, kw, stride, pad, dil, G)) return -1;
-    return dcn_bwd_ws<E>(n, c / G, h, w, co, kh, kw, stride, pad, dil).total;
+    return dcn_bwd_ws<E>(n, c / G, h, w, co, kh, kw, stride, pad, dil, det).total;
+}
+
+extern "C" long long m3d_dcn_v2_backward_det_workspace_bytes(int batch, int channels, int height, int width, int channels_out,
+                                                             int kernel_h, int kernel_w, int stride, int pad, int dilation,
+                                                             int deformable_group)
+{
+    return dcn_bwd_ws_bytes<DcnF32>(batch, channels, height, width, channels_out, kernel_h, kernel_w, stride, pad, dilation, deformable_group,
+                                    true);
+}
+
+extern "C" long long m3d_dcn_v2_backward_det_workspace_bytes_bf16(int batch, int channels, int height, int width, int channels_out,
+                                                                  int kernel_h, int kernel_w, int stride, int pad, int dilation,
+                                                                  int deformable_group)
+{
+    return dcn_bwd_ws_bytes<DcnBf16>(batch, channels, height, width, channels_out, kernel_h, kernel_w, stride, pad, dilation, deformable_group,
+                                     true);
 }
 
 extern "C" long long m3d_dcn_v2_backward_workspace_bytes(int batch, int channels, int height, int width, int channels_out,
                                                          int kernel_h, int kernel_w, int stride, int pad, int dilation,
                                                          int deformable_group)
 {
-    return dcn_bwd_ws_bytes<DcnF32>(batch, channels, height, width, channels_out, kernel_h, kernel_w, stride, pad, dilation, deformable_group);
+    return dcn_bwd_ws_bytes<DcnF32>(batch, channels, height, width, channels_out, kernel_h, kernel_w, stride, pad, dilation, deformable_group,
+                                    false);
 }
 
 extern "C" long long m3d_dcn_v2_backward_workspace_bytes_bf16(int batch, int channels, int height, int width, int channels_out,
                                                               int kernel_h, int kernel_w, int stride, int pad, int dilation,
                                                               int deformable_group)
 {
-    return dcn_bwd_ws_bytes<DcnBf16>(batch, channels, height, width, channels_out, kernel_h, kernel_w, stride, pad, dilation, deformable_group);
+    return dcn_bwd_ws_bytes<DcnBf16>(batch, channels, height, width, channels_out, kernel_h, kernel_w, stride, pad, dilation, deformable_group,
+                                     false);
 }
 
 // ================================================================================================== backward: per-type steps
@@ -862,7 +1016,7 @@ static void dcn_wgrad_launch(DcnBf16, dim3 grid, bool dw, const u16 *go, const u
 // (4) the size limits: E::max_in_elems / E::max_go_elems
 
 // ================================================================================================== backward: the driver
-template <class E>
+template <class E, bool DET>
 static int dcn_backward(const typename E::T *input, const typename E::T *weight, const DcnOmSrc &om_src, const typename E::T *grad_output,
                         typename E::T *grad_input, float *grad_offset, float *grad_mask, typename E::T *grad_weight, float *grad_bias,
                         int batch, int channels, int height, int width, int channels_out, int kernel_h, int kernel_w, int stride_h,
@@ -870,19 +1024,20 @@ static int dcn_backward(const typename E::T *input, const typename E::T *weight,
                         long long workspace_bytes, hipStream_t stream)
 {
     typedef typename E::T T;
+    const char *name = DET ? E::det_name : E::bwd_name;
     int rc;
-    if ((rc = dcn_check_args(E::bwd_name, E::is_bf16, input && weight && om_src.offset && om_src.mask && grad_output && workspace,
+    if ((rc = dcn_check_args(name, E::is_bf16, input && weight && om_src.offset && om_src.mask && grad_output && workspace,
                              dcn_shape_ok(E::is_bf16, batch, channels, height, width, channels_out, kernel_h, kernel_w, stride_h, pad_h,
                                           dilation_h),
                              channels, deformable_group, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, workspace)))
         return rc;
     const int G = deformable_group, cg = channels / G, kk = kernel_h * kernel_w;
-    const DcnBwdWs s = dcn_bwd_ws<E>(batch, cg, height, width, channels_out, kernel_h, kernel_w, stride_h, pad_h, dilation_h);
-    if ((rc = dcn_check_workspace(E::bwd_name, E::bwd_query, workspace_bytes, s.total))) return rc;
-    M3D_REQUIRE(s.ho > 0 && s.wo > 0, "%s: empty output", E::bwd_name);
+    const DcnBwdWs s = dcn_bwd_ws<E>(batch, cg, height, width, channels_out, kernel_h, kernel_w, stride_h, pad_h, dilation_h, DET);
+    if ((rc = dcn_check_workspace(name, DET ? E::det_query : E::bwd_query, workspace_bytes, s.total))) return rc;
+    M3D_REQUIRE(s.ho > 0 && s.wo > 0, "%s: empty output", name);
     const long long P = (long long)batch * s.ho * s.wo, HoWo = (long long)s.ho * s.wo;
     const long long in_elems = (long long)batch * height * width * s.cp;
-    M3D_REQUIRE(P < (1ll << 29) && in_elems < E::max_in_elems && P * s.co_pad < E::max_go_elems, "%s: tensor too large", E::bwd_name);
+    M3D_REQUIRE(P < (1ll << 29) && in_elems < E::max_in_elems && P * s.co_pad < E::max_go_elems, "%s: tensor too large", name);
     if (!grad_input && !grad_offset && !grad_mask && !grad_weight && !grad_bias) return M3D_OK;
     const int HW = height * width;
     char *ws = (char *)workspace;
@@ -892,6 +1047,18 @@ static int dcn_backward(const typename E::T *input, const typename E::T *weight,
     const bool need_gcol = grad_input || grad_offset || grad_mask, need_col = grad_weight != nullptr;
     const bool need_sample = need_gcol || need_col;
     if ((rc = dcn_pack_act(E(), grad_output, channels_out, 0, go, batch, channels_out, s.ho, s.wo, s.co_pad, stream))) return rc;
+    // the deterministic form: the statistics of the fixed-point exponent (dcn_sexp_kernel), all on the device
+    unsigned *amax = (unsigned *)(ws + s.stat_off), *mmax = amax + batch, *wmax = mmax + batch;
+    int *sexp = (int *)(wmax + 1);
+    const bool det_gin = DET && grad_input;
+    int log2T = 0;
+    while ((1ll << log2T) < HoWo * kk) ++log2T;
+    if (det_gin) {
+        M3D_HIP(hipMemsetAsync(amax, 0, ((size_t)2 * batch + 1) * 4, stream));
+        hipLaunchKernelGGL(dcn_absmax_kernel<T>, dim3(imin(cdiv(HoWo * s.co_pad, 256), 256), batch), dim3(256), 0, stream, (const T *)go,
+                           (int)HoWo, s.co_pad, 0, s.co_pad, amax);
+        M3D_LAUNCH_CHECK();
+    }
     for (int g = 0; g < G; ++g) {
         if (need_sample) {
             if ((rc = dcn_pack_act(E(), input, channels, g * cg, in_nhwc, batch, cg, height, width, s.cp, stream))) return rc;
@@ -904,20 +1071,34 @@ static int dcn_backward(const typename E::T *input, const typename E::T *weight,
             M3D_LAUNCH_CHECK();
             if ((rc = dcn_gcol_gemm(E(), go, wt, gcol, batch, s, stream))) return rc;
         }
-        if (grad_input) M3D_HIP(hipMemsetAsync(gin, 0, (size_t)in_elems * 4, stream));
+        if (det_gin) {
+            if (g > 0) M3D_HIP(hipMemsetAsync(mmax, 0, ((size_t)batch + 1) * 4, stream));
+            hipLaunchKernelGGL(dcn_absmax_kernel<float>, dim3(imin(cdiv(HoWo * kk, 256), 256), batch), dim3(256), 0, stream, (const float *)om,
+                               (int)HoWo, s.om_cs, 2 * kk, kk, mmax);
+            M3D_LAUNCH_CHECK();
+            hipLaunchKernelGGL(dcn_wsum_max_kernel<T>, dim3(cdiv(s.K, 4)), dim3(256), 0, stream, (const T *)wt, s.K, s.co_pad, wmax);
+            M3D_LAUNCH_CHECK();
+            hipLaunchKernelGGL(dcn_sexp_kernel, dim3(cdiv(batch, 64)), dim3(64), 0, stream, amax, mmax, wmax, sexp, batch, log2T);
+            M3D_LAUNCH_CHECK();
+        }
+        if (grad_input) M3D_HIP(hipMemsetAsync(gin, 0, (size_t)in_elems * (DET ? 8 : 4), stream));
         if (need_sample) {
             DcnSampleArgs<E> a;
             a.in = in_nhwc; a.om = om; a.gcol = need_gcol ? gcol : nullptr; a.col = need_col ? col : nullptr;
-            a.gin = grad_input ? gin : nullptr;
+            a.gin = grad_input ? gin : nullptr; a.sexp = det_gin ? sexp : nullptr;
             a.goff = grad_offset ? grad_offset + (size_t)g * 2 * kk * HoWo : nullptr;
             a.gmask = grad_mask ? grad_mask + (size_t)g * kk * HoWo : nullptr;
             a.goff_img = (long long)2 * kk * G * HoWo; a.gmask_img = (long long)kk * G * HoWo;
             a.P = (int)P; a.H = height; a.W = width; a.Ho = s.ho; a.Wo = s.wo; a.cp = s.cp; a.kh = kernel_h; a.kw = kernel_w;
             a.stride = stride_h; a.pad = pad_h; a.dil = dilation_h; a.om_cs = s.om_cs;
-            hipLaunchKernelGGL(dcn_sample_kernel<E>, dim3(cdiv(P, 4)), dim3(256), 0, stream, a);
+            hipLaunchKernelGGL((dcn_sample_kernel<E, DET>), dim3(cdiv(P, 4)), dim3(256), 0, stream, a);
             M3D_LAUNCH_CHECK();
         }
-        if (grad_input) {
+        if (det_gin) {
+            hipLaunchKernelGGL(dcn_nhwc_i64_to_nchw_kernel<E>, dim3(cdiv(HW, 32), cdiv(cg, 32), batch), dim3(256), 0, stream,
+                               (const long long *)gin, s.cp, sexp, grad_input, cg, HW, channels, g * cg);
+            M3D_LAUNCH_CHECK();
+        } else if (grad_input) {
             hipLaunchKernelGGL(dcn_nhwc_f32_to_nchw_kernel<E>, dim3(cdiv(HW, 32), cdiv(cg, 32), batch), dim3(256), 0, stream, gin, s.cp, 1, 0ll,
                                grad_input, cg, HW, channels, g * cg);
             M3D_LAUNCH_CHECK();
@@ -944,7 +1125,7 @@ extern "C" int m3d_dcn_v2_backward(const float *input, const float *weight, cons
                                    int dilation_h, int dilation_w, int deformable_group, void *workspace, long long workspace_bytes,
                                    m3d_stream_t stream_)
 {
-    return dcn_backward<DcnF32>(input, weight, DcnOmSrc{offset, mask, 0, 0}, grad_output, grad_input, grad_offset, grad_mask, grad_weight,
+    return dcn_backward<DcnF32, false>(input, weight, DcnOmSrc{offset, mask, 0, 0}, grad_output, grad_input, grad_offset, grad_mask, grad_weight,
                                 grad_bias, batch, channels, height, width, channels_out, kernel_h, kernel_w, stride_h, stride_w, pad_h,
                                 pad_w, dilation_h, dilation_w, deformable_group, workspace, workspace_bytes, (hipStream_t)stream_);
 }
@@ -956,8 +1137,36 @@ extern "C" int m3d_dcn_v2_backward_bf16(const void *input, const void *weight, c
                                         int dilation_h, int dilation_w, int deformable_group, void *workspace, long long workspace_bytes,
                                         m3d_stream_t stream_)
 {
-    return dcn_backward<DcnBf16>((const u16 *)input, (const u16 *)weight, DcnOmSrc{offset, mask, offset_is_bf16, mask_is_bf16},
+    return dcn_backward<DcnBf16, false>((const u16 *)input, (const u16 *)weight, DcnOmSrc{offset, mask, offset_is_bf16, mask_is_bf16},
                                  (const u16 *)grad_output, (u16 *)grad_input, grad_offset, grad_mask, (u16 *)grad_weight, grad_bias, batch,
                                  channels, height, width, channels_out, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
                                  dilation_w, deformable_group, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+// The same two calls with a bitwise-reproducible grad_input (64-bit fixed-point sums, see dcn_sexp_kernel); the other four gradients
+// take the path of the calls above and have their bits.
+extern "C" int m3d_dcn_v2_backward_det(const float *input, const float *weight, const float *offset, const float *mask,
+                                       const float *grad_output, float *grad_input, float *grad_offset, float *grad_mask,
+                                       float *grad_weight, float *grad_bias, int batch, int channels, int height, int width,
+                                       int channels_out, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w,
+                                       int dilation_h, int dilation_w, int deformable_group, void *workspace, long long workspace_bytes,
+                                       m3d_stream_t stream_)
+{
+    return dcn_backward<DcnF32, true>(input, weight, DcnOmSrc{offset, mask, 0, 0}, grad_output, grad_input, grad_offset, grad_mask,
+                                      grad_weight, grad_bias, batch, channels, height, width, channels_out, kernel_h, kernel_w, stride_h,
+                                      stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group, workspace, workspace_bytes,
+                                      (hipStream_t)stream_);
+}
+
+extern "C" int m3d_dcn_v2_backward_det_bf16(const void *input, const void *weight, const void *offset, int offset_is_bf16,
+                                            const void *mask, int mask_is_bf16, const void *grad_output, void *grad_input,
+                                            float *grad_offset, float *grad_mask, void *grad_weight, float *grad_bias, int batch,
+                                            int channels, int height, int width, int channels_out, int kernel_h, int kernel_w,
+                                            int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
+                                            int deformable_group, void *workspace, long long workspace_bytes, m3d_stream_t stream_)
+{
+    return dcn_backward<DcnBf16, true>((const u16 *)input, (const u16 *)weight, DcnOmSrc{offset, mask, offset_is_bf16, mask_is_bf16},
+                                       (const u16 *)grad_output, (u16 *)grad_input, grad_offset, grad_mask, (u16 *)grad_weight, grad_bias,
+                                       batch, channels, height, width, channels_out, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                                       dilation_h, dilation_w, deformable_group, workspace, workspace_bytes, (hipStream_t)stream_);
 }

@@ -94,14 +94,38 @@ def dcn_v2_forward(inp, offset, mask, weight, bias, stride, padding, dilation=1,
     return out
 
 
+_dcn_det_mode = None       # None: follow torch.are_deterministic_algorithms_enabled(); True / False: override it
+
+
+def set_dcn_deterministic(mode):
+    """Selects the form of grad_input in the DCNv2 backward and returns the previous mode.  ``True``: the bitwise-reproducible form
+    (m3d_dcn_v2_backward_det / _det_bf16: 64-bit fixed-point sums); ``False``: float atomics (last bits depend on arrival order);
+    ``None`` (the default): the reproducible form iff ``torch.are_deterministic_algorithms_enabled()``, warn-only or not --
+    PyTorch's rule for an operator that has a deterministic alternative."""
+    global _dcn_det_mode
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError("set_dcn_deterministic: mode must be None, True or False")
+    prev, _dcn_det_mode = _dcn_det_mode, mode
+    return prev
+
+
+def dcn_deterministic():
+    """The form a DCNv2 backward that runs now would take (see ``set_dcn_deterministic``)."""
+    return torch.are_deterministic_algorithms_enabled() if _dcn_det_mode is None else _dcn_det_mode
+
+
 def dcn_v2_backward(inp, offset, mask, weight, grad_output, stride, padding, dilation=1, deformable_groups=1,
-                    needs=(True, True, True, True, True)):
+                    needs=(True, True, True, True, True), deterministic=None):
     """DCNv2Function.backward (model/DCNv2/dcn_v2_func.py:40-62) on the HIP library: returns (grad_input, grad_offset, grad_mask,
     grad_weight, grad_bias); an entry of ``needs`` that is False gives None and skips the work only that gradient needs.
     Every returned gradient is freshly written (nothing is accumulated into).  The compute type is the dtype of ``inp`` (float32
     or bfloat16); each gradient comes back in the dtype of the tensor it belongs to (grad_bias: float32), so a float32 weight
-    under a bfloat16 input gets a float32 gradient that went through one bfloat16 rounding."""
+    under a bfloat16 input gets a float32 gradient that went through one bfloat16 rounding.
+    ``deterministic``: True = grad_input from m3d_dcn_v2_backward_det (a function of the inputs alone: the same bits on every launch
+    and in any batch; all NaN for an image whose grad_output, masks or the weights hold a NaN or infinity), False = float atomics,
+    None = ``dcn_deterministic()``.  The other four gradients are reproducible, with the same bits, either way."""
     _require_cuda(inp, offset, mask, weight, grad_output)
+    det = dcn_deterministic() if deterministic is None else bool(deterministic)
     owner_dtypes = (inp.dtype, offset.dtype, mask.dtype, weight.dtype, torch.float32)
     offset, mask, weight, dims, off16, mask16 = _dcn_prepare("dcn_v2_backward", inp, offset, mask, weight, stride, padding, dilation,
                                                              deformable_groups)
@@ -115,7 +139,10 @@ def dcn_v2_backward(inp, offset, mask, weight, grad_output, stride, padding, dil
     # what the kernels write: the compute type for grad_input / grad_weight, float32 for grad_offset / grad_mask / grad_bias
     kdt = (inp.dtype, torch.float32, torch.float32, inp.dtype, torch.float32)
     grads = [torch.empty(tuple(s), device=inp.device, dtype=dt) if need else None for s, dt, need in zip(shapes, kdt, needs)]
-    query = L.m3d_dcn_v2_backward_workspace_bytes_bf16 if bf16 else L.m3d_dcn_v2_backward_workspace_bytes
+    query, call = {(False, False): (L.m3d_dcn_v2_backward_workspace_bytes, L.m3d_dcn_v2_backward),
+                   (False, True): (L.m3d_dcn_v2_backward_det_workspace_bytes, L.m3d_dcn_v2_backward_det),
+                   (True, False): (L.m3d_dcn_v2_backward_workspace_bytes_bf16, L.m3d_dcn_v2_backward_bf16),
+                   (True, True): (L.m3d_dcn_v2_backward_det_workspace_bytes_bf16, L.m3d_dcn_v2_backward_det_bf16)}[(bf16, det)]
     nbytes = query(n, c, h, w, co, kh, kw, stride, padding, dilation, deformable_groups)
     if nbytes < 0:
         raise RuntimeError("dcn_v2_backward: bad shape")
@@ -124,11 +151,11 @@ def dcn_v2_backward(inp, offset, mask, weight, grad_output, stride, padding, dil
     geom = (n, c, h, w, co, kh, kw, stride, stride, padding, padding, dilation, dilation, deformable_groups)
     with torch.cuda.device(inp.device):
         if bf16:
-            _hip.check(L.m3d_dcn_v2_backward_bf16(inp.data_ptr(), weight.data_ptr(), offset.data_ptr(), off16, mask.data_ptr(), mask16,
-                                                  grad_output.data_ptr(), *ptrs, *geom, base, nbytes, _stream()))
+            _hip.check(call(inp.data_ptr(), weight.data_ptr(), offset.data_ptr(), off16, mask.data_ptr(), mask16,
+                            grad_output.data_ptr(), *ptrs, *geom, base, nbytes, _stream()))
         else:
-            _hip.check(L.m3d_dcn_v2_backward(inp.data_ptr(), weight.data_ptr(), offset.data_ptr(), mask.data_ptr(),
-                                             grad_output.data_ptr(), *ptrs, *geom, base, nbytes, _stream()))
+            _hip.check(call(inp.data_ptr(), weight.data_ptr(), offset.data_ptr(), mask.data_ptr(),
+                            grad_output.data_ptr(), *ptrs, *geom, base, nbytes, _stream()))
     return tuple(g if g is None else g.to(dt) for g, dt in zip(grads, owner_dtypes))
 
 
@@ -149,7 +176,8 @@ class _DCNv2(torch.autograd.Function):
 
 def dcn_v2(inp, offset, mask, weight, bias, stride, padding, dilation=1, deformable_groups=1):
     """The DCNv2 operator, differentiable in its five tensor arguments: m3d_dcn_v2_forward (the bits of ``dcn_v2_forward``) with
-    m3d_dcn_v2_backward behind it."""
+    m3d_dcn_v2_backward behind it -- or m3d_dcn_v2_backward_det, whose grad_input is bitwise reproducible, when ``dcn_deterministic()``
+    holds at the time the backward runs (``torch.use_deterministic_algorithms(True)`` or ``set_dcn_deterministic(True)``)."""
     _require_cuda(inp, offset, mask, weight, bias)
     return _DCNv2.apply(inp, offset, mask, weight, bias, stride, padding, dilation, deformable_groups)
 

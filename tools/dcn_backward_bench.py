@@ -16,7 +16,15 @@ Budget printed next to the backward measurement: the scatt
 the chip-wide float-atomic rate of 1.3 TB/s (fp32 atomics in both types), plus the two GEMMs of 2 * N*Ho*Wo * Co * kk*C FLOP each
 at the rate the forward's wave-granular convolution reaches (94 TFLOP/s).
 
+--deterministic times m3d_dcn_v2_backward_det / _det_bf16 (grad_input as a 64-bit fixed-point sum: bitwise reproducible) next to the
+float-atomic form: per shape and type, for the full call and for grad_input alone, the legs float, det, float again alternate inside
+one process; the line carries their medians and interquartile ranges, `spread_ms` as above, `det_over_float` = det median / first
+float median and, for grad_input alone, the rate of the 64-bit atomics if they were all the call did (`atomic_bytes` = N*Ho*Wo * kk *
+4 corners * C * 8 bytes over the det median: a lower bound of the rate, the GEMM and the sampling are in the time).  The lines also
+go to --out (default profiles/dcn_backward_det_bench.jsonl).
+
 usage: python tools/dcn_backward_bench.py [--reps 50] [--warmup 5] [--batch 8] [--dtype f32|bf16|both] [--forward]
+       python tools/dcn_backward_bench.py --deterministic [--reps 50] [--warmup 5] [--batch 8] [--out FILE]
 (one JSON line per shape on stdout)"""
 import argparse
 import ctypes
@@ -47,7 +55,7 @@ MODES = {"all": (1, 1, 1, 1, 1), "weight_only": (0, 0, 0, 1, 0), "input_only": (
 class Leg:
     """One compute type of one shape: its device tensors, workspaces and the two calls."""
 
-    def __init__(self, dtype, data, geom, pad, dev, stream):
+    def __init__(self, dtype, data, geom, pad, dev, stream, det=False):
         self.bf16 = dtype == "bf16"
         L = self.L = _hip.lib()
         dt = torch.bfloat16 if self.bf16 else torch.float32
@@ -60,7 +68,9 @@ class Leg:
                       torch.empty(co, device=dev)]
         q = (n, c, h, w, co, k, k, 1, pad, 1, 1)
         self.fbytes = (L.m3d_dcn_v2_workspace_bytes_bf16 if self.bf16 else L.m3d_dcn_v2_workspace_bytes_grouped)(*q)
-        self.bbytes = (L.m3d_dcn_v2_backward_workspace_bytes_bf16 if self.bf16 else L.m3d_dcn_v2_backward_workspace_bytes)(*q)
+        name = "m3d_dcn_v2_backward_det" if det else "m3d_dcn_v2_backward"
+        self.bwd = getattr(L, name + ("_bf16" if self.bf16 else ""))
+        self.bbytes = getattr(L, name + "_workspace_bytes" + ("_bf16" if self.bf16 else ""))(*q)
         self.ws = torch.empty(max(self.fbytes, self.bbytes) + 256, device=dev, dtype=torch.uint8)
         self.base = (self.ws.data_ptr() + 255) // 256 * 256
         self.tail = (n, c, h, w, co, k, k, 1, 1, pad, pad, 1, 1, 1, self.base)
@@ -80,11 +90,9 @@ class Leg:
         L, p = self.L, lambda t: t.data_ptr()                      # noqa: E731
         ptrs = [t.data_ptr() if wnt else None for t, wnt in zip(self.grads, want)]
         if self.bf16:
-            rc = L.m3d_dcn_v2_backward_bf16(p(self.x), p(self.wt), p(self.off), 0, p(self.m), 0, p(self.go), *ptrs, *self.tail,
-                                            self.bbytes, self.stream)
+            rc = self.bwd(p(self.x), p(self.wt), p(self.off), 0, p(self.m), 0, p(self.go), *ptrs, *self.tail, self.bbytes, self.stream)
         else:
-            rc = L.m3d_dcn_v2_backward(p(self.x), p(self.wt), p(self.off), p(self.m), p(self.go), *ptrs, *self.tail, self.bbytes,
-                                       self.stream)
+            rc = self.bwd(p(self.x), p(self.wt), p(self.off), p(self.m), p(self.go), *ptrs, *self.tail, self.bbytes, self.stream)
         _hip.check(rc)
 
 
@@ -101,7 +109,48 @@ def timed(fn, warmup, reps):
         e1.synchronize()
         ts.append(e0.elapsed_time(e1))
     ts.sort()
-    return {"median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4)}
+    return {"median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4), "iqr": round(ts[(3 * len(ts)) // 4] - ts[len(ts) // 4], 4)}
+
+
+def make_data(n, c, co, h, w, k, sigma, dev):
+    kk = k * k
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(n, c, h, w, generator=g).to(dev)
+    off = (torch.randn(n, 2 * kk, h, w, generator=g) * sigma).to(dev)
+    m = torch.sigmoid(torch.randn(n, kk, h, w, generator=g)).to(dev)
+    wt = (torch.randn(co, c, k, k, generator=g) / (c * kk) ** 0.5).to(dev)
+    go = torch.randn(n, co, h, w, generator=g).to(dev)
+    return x, off, m, wt, torch.zeros(co, device=dev), go
+
+
+def main_deterministic(a, dev, stream):
+    out = open(a.out, "w") if a.out else None
+    for name, c, co, h, w, k, pad, sigma in SHAPES:
+        n, kk = a.batch, k * k
+        data = make_data(n, c, co, h, w, k, sigma, dev)
+        res = {"shape": name, "batch": n, "reps": a.reps, "op": "backward_det", "workspace_mb": {}}
+        atomic_bytes = n * h * w * kk * 4 * c * 8
+        for dtype in ("f32", "bf16"):
+            legs = {"float": Leg(dtype, data, (n, c, h, w, co, k), pad, dev, stream),
+                    "det": Leg(dtype, data, (n, c, h, w, co, k), pad, dev, stream, det=True)}
+            res["workspace_mb"][dtype] = {form: round(lg.bbytes / 2 ** 20, 1) for form, lg in legs.items()}
+            for mode in ("all", "input_only"):
+                entry = {}
+                for o in ("float", "det", "float_repeat"):
+                    lg = legs[o.split("_")[0]]
+                    entry[o] = timed(lambda: lg.backward(MODES[mode]), a.warmup, a.reps)
+                entry["spread_ms"] = round(abs(entry["float_repeat"]["median"] - entry["float"]["median"]), 4)
+                entry["det_over_float"] = round(entry["det"]["median"] / entry["float"]["median"], 3)
+                if mode == "input_only":
+                    entry["atomic_bytes"] = atomic_bytes
+                    entry["atomic_tb_per_s_at_least"] = round(atomic_bytes / (entry["det"]["median"] * 1e-3) / 1e12, 3)
+                res.setdefault(mode + "_ms", {})[dtype] = entry
+            del legs
+        line = json.dumps(res)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
 
 
 def main():
@@ -111,21 +160,20 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--dtype", choices=("f32", "bf16", "both"), default="f32")
     ap.add_argument("--forward", action="store_true", help="time the operator's forward instead of the backward")
+    ap.add_argument("--deterministic", action="store_true", help="time the bitwise-reproducible backward next to the float-atomic one")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                  "dcn_backward_det_bench.jsonl"), help="--deterministic: file the lines go to")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("dcn_backward_bench: no ROCm device")
     dev = torch.device("cuda:0")
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if a.deterministic:
+        return main_deterministic(a, dev, stream)
     order = {"f32": ("f32",), "bf16": ("bf16",), "both": ("f32", "bf16", "f32_repeat")}[a.dtype]
     for name, c, co, h, w, k, pad, sigma in SHAPES:
         n, kk = a.batch, k * k
-        g = torch.Generator().manual_seed(1)
-        x = torch.randn(n, c, h, w, generator=g).to(dev)
-        off = (torch.randn(n, 2 * kk, h, w, generator=g) * sigma).to(dev)
-        m = torch.sigmoid(torch.randn(n, kk, h, w, generator=g)).to(dev)
-        wt = (torch.randn(co, c, k, k, generator=g) / (c * kk) ** 0.5).to(dev)
-        go = torch.randn(n, co, h, w, generator=g).to(dev)
-        b = torch.zeros(co, device=dev)
+        x, off, m, wt, b, go = make_data(n, c, co, h, w, k, sigma, dev)
         legs = {d: Leg(d, (x, off, m, wt, b, go), (n, c, h, w, co, k), pad, dev, stream) for d in set(o.split("_")[0] for o in order)}
         res = {"shape": name, "batch": n, "reps": a.reps, "op": "forward" if a.forward else "backward", "dtype": a.dtype,
                "workspace_mb": {d: round((lg.fbytes if a.forward else lg.bbytes) / 2 ** 20, 1) for d, lg in legs.items()}}
