@@ -35,6 +35,8 @@ PSP_SIZES = (1, 4, 8, 16)
 # channels of the stem, level0 .. level5 (pose_dla_dcn.py:419-440); channels[3] is the width of feats0 and every map after it
 BACKBONE_CHANNELS = {"dla34": (16, 32, 64, 128, 256, 512), "dla102": (16, 32, 128, 256, 512, 1024)}
 DLA102_LEVELS = (1, 1, 1, 3, 4, 1)
+# the box heads in the order of their rows in the planar box staging [B][11][A][HW]
+BOX_HEADS = ("bbox_x", "bbox_y", "bbox_w", "bbox_h", "bbox_x3d", "bbox_y3d", "bbox_z3d", "bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d")
 
 
 def _rup(a, b):
@@ -67,6 +69,20 @@ class _Stream:
         return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def fold_affine(device, cout, bias=None, bn=None):
+    """Per-channel fp32 (scale, shift) that stand for a conv's bias and the BatchNorm(eval) behind it, bn = (weight, bias,
+    running_mean, running_var): y = conv(x) * scale + shift."""
+    scale = torch.ones(cout, device=device, dtype=torch.float32)
+    shift = torch.zeros(cout, device=device, dtype=torch.float32)
+    if bias is not None:
+        shift = bias.detach().to(device, torch.float32).clone()
+    if bn is not None:
+        g, b, m, v = (t.detach().to(device, torch.float32) for t in bn)
+        scale = g / torch.sqrt(v + BN_EPS)
+        shift = (shift - m) * scale + b
+    return scale.contiguous(), shift.contiguous()
+
+
 class PackedConv:
     """Packed weights + folded affine of one conv (or DCN main conv)."""
 
@@ -78,16 +94,7 @@ class PackedConv:
         self.wp = torch.empty(self.cout_pad * self.kh * self.kw * self.cin_pad, device=eng.device, dtype=torch.float32)
         _hip.check(eng.L.m3d_pack_conv_weight(w.data_ptr(), self.wp.data_ptr(), self.cout, self.cout_pad, self.cin,
                                               self.cin_pad, self.kh, self.kw, _Stream.current()))
-        scale = torch.ones(self.cout, device=eng.device, dtype=torch.float32)
-        shift = torch.zeros(self.cout, device=eng.device, dtype=torch.float32)
-        if bias is not None:
-            shift = bias.detach().to(eng.device, torch.float32).clone()
-        if bn is not None:
-            g, b, m, v = (t.detach().to(eng.device, torch.float32) for t in bn)
-            s = g / torch.sqrt(v + BN_EPS)
-            shift = (shift - m) * s + b
-            scale = s
-        self.scale, self.shift = scale.contiguous(), shift.contiguous()
+        self.scale, self.shift = fold_affine(eng.device, self.cout, bias, bn)
         self.has_affine = (bias is not None) or (bn is not None)
         self._eng_device = eng.device
         self._frag = None
@@ -225,6 +232,29 @@ class _Plan:
         # only the top-k decode reads the box staging (Engine.run_plan(tail=True)); None: the plan has none
         self.tail = None
         self.tail_start = None
+        # index into ops -> factory(rpn stage record) of the launch that stands in for that op in the tail (its row-list / gated
+        # form), registered where the dense op is appended; the tail takes it for ops behind anchor_select (Engine._rpn_tail)
+        self.sparse = {}
+
+    def sparse_form(self, factory):
+        """Register the detection-only form of the op appended last."""
+        self.sparse[len(self.ops) - 1] = factory
+
+
+class _RpnStage:
+    """State of the RPN stage of one plan, shared by the steps both plan builders make it from (Engine._rpn_*): sizes, the planar
+    fp32 staging of the head outputs, and what anchor_select, the output bundling and the tail's selection pass add to it."""
+
+    def __init__(self, B, A, NC, fh, fw):
+        self.B, self.A, self.NC, self.fh, self.fw = B, A, NC, fh, fw
+        self.HW = fh * fw
+        self.R = A * self.HW
+
+    def box_planar(self, k):
+        return (self.box_pl, 11 * self.A * self.HW, k * self.A)
+
+    def box_ptr(self, k):
+        return self.box_pl.data_ptr() + 4 * k * self.A * self.HW          # image 0; per-image stride handled via [B][11][A][HW]
 
 
 class Engine:
@@ -265,6 +295,15 @@ class Engine:
         sd = self.sd
         return PackedConv(self, sd[conv + ".weight"], sd.get(conv + ".bias"), self._bn(bn) if bn else None, **kw)
 
+    DCN_PACK = dict(cout_pad_to=64)     # how _pc packs the main conv of a DCN (the bf16 engine pads none)
+
+    def _pack_front(self, sd, P):
+        """Front-end extras of this engine: level0 also as a direct VALU conv, weights [(i*3+j)*16 + cin][cout], and as F(4x4,3x3)."""
+        w0 = sd["base.base.level0.0.weight"].detach().to(self.device, torch.float32)
+        c16 = tuple(w0.shape) == (16, 16, 3, 3)
+        P["level0.direct"] = w0.permute(2, 3, 1, 0).contiguous() if c16 else None
+        P["level0.wino44"] = pack_wino44_c16(w0, self.device) if (USE_WINO44 and c16) else None
+
     def _pack(self, sd):
         dev = self.device
         P = {}
@@ -272,15 +311,10 @@ class Engine:
         # stem 7x7: [16,3,7,7] -> [(i*7+j)*3+c][16]
         w = sd[b + ".base_layer.0.weight"].detach().to(dev, torch.float32)
         P["stem.w"] = w.permute(2, 3, 1, 0).contiguous()
-        g, be, m, v = (t.detach().to(dev, torch.float32) for t in self._bn(b + ".base_layer.1"))
-        s = g / torch.sqrt(v + BN_EPS)
-        P["stem.scale"], P["stem.shift"] = s.contiguous(), (be - m * s).contiguous()
+        P["stem.scale"], P["stem.shift"] = fold_affine(dev, w.shape[0], None, self._bn(b + ".base_layer.1"))
         P["level0"] = self._pc(b + ".level0.0", b + ".level0.1")
-        # level0 also as a direct VALU conv: weights [(i*3+j)*16 + cin][cout]
-        w0 = sd[b + ".level0.0.weight"].detach().to(dev, torch.float32)
-        P["level0.direct"] = w0.permute(2, 3, 1, 0).contiguous() if tuple(w0.shape) == (16, 16, 3, 3) else None
-        P["level0.wino44"] = pack_wino44_c16(w0, self.device) if (USE_WINO44 and tuple(w0.shape) == (16, 16, 3, 3)) else None
         P["level1"] = self._pc(b + ".level1.0", b + ".level1.1")
+        self._pack_front(sd, P)
 
         def block(p):
             P[p + ".conv1"] = self._pc(p + ".conv1", p + ".bn1")
@@ -322,8 +356,7 @@ class Engine:
 
         def deform(p):
             P[p + ".om"] = self._pc(p + ".conv.conv_offset_mask")
-            P[p + ".dcn"] = PackedConv(self, sd[p + ".conv.weight"], sd[p + ".conv.bias"], self._bn(p + ".actf.0"),
-                                       cout_pad_to=64)
+            P[p + ".dcn"] = self._pc(p + ".conv", p + ".actf.0", **self.DCN_PACK)
 
         def ida(p, n):
             for i in range(1, n):
@@ -353,33 +386,31 @@ class Engine:
         self.anab_off = dict(q=0, k=self.ck_pad, v=self.ck_pad + self.ck, s=self.ck_pad + self.ck + self.cv)
         self.anab_ctot = wall.shape[0]
 
+    def _pack_head(self, sd, P, p):
+        """The three layers of head p, and the 1x1 ones also in the fragment order of the fused-MLP kernel."""
+        P[p + ".0"] = self._pc(p + ".0", p + ".1")
+        P[p + ".3"] = self._pc(p + ".3", p + ".4")
+        P[p + ".6"] = self._pc(p + ".6", cout_pad_to=256 if p == "cls" else 64)   # fused-MLP output tile
+        for li, rows in ((".0", 256), (".3", 256), (".6", P[p + ".6"].cout_pad)):
+            wt = sd[p + li + ".weight"]
+            if wt.shape[2] == 1:                                                    # 1x1 layers only
+                P[p + li + ".frag"] = pack_frag(wt.reshape(wt.shape[0], wt.shape[1]), rows, self.device)
+
     def _pack_heads(self, sd, P):
+        """Heads, align stages and ANAB; an engine packs the layers its own kernels read in _pack_head / _pack_anab."""
         dev = self.device
-
-        def head(p):
-            P[p + ".0"] = self._pc(p + ".0", p + ".1")
-            P[p + ".3"] = self._pc(p + ".3", p + ".4")
-            P[p + ".6"] = self._pc(p + ".6", cout_pad_to=256 if p == "cls" else 64)   # fused-MLP output tile
-            for li, rows in ((".0", 256), (".3", 256), (".6", P[p + ".6"].cout_pad)):
-                wt = sd[p + li + ".weight"]
-                if wt.shape[2] == 1:                                                    # 1x1 layers only
-                    P[p + li + ".frag"] = pack_frag(wt.reshape(wt.shape[0], wt.shape[1]), rows, dev)
-
-        self.box_heads = ["bbox_x", "bbox_y", "bbox_w", "bbox_h", "bbox_x3d", "bbox_y3d", "bbox_z3d", "bbox_w3d",
-                          "bbox_h3d", "bbox_l3d", "bbox_rY3d"]
+        self.box_heads = list(BOX_HEADS)
         for h in ["cls"] + self.box_heads:
-            head(h)
+            self._pack_head(sd, P, h)
         with_shape, with_center, with_anab = self.flags
         for p in ("shape_align",) * with_shape + ("center_align2d", "center_align3d") * with_center:
-            P[p] = PackedConv(self, sd[p + ".align.weight"], sd[p + ".align.bias"], None, cout_pad_to=64)
-
+            P[p] = self._pc(p + ".align", **self.DCN_PACK)
         if with_anab:
             a = "bbox_z3d_gl.0"
             self._pack_anab(P, sd[a + ".query_conv.weight"], sd[a + ".key_conv.weight"], sd[a + ".value_conv.weight"],
                             sd[a + ".spatial_conv.weight"])
-            g, be, m, v = (t.detach().to(dev, torch.float32) for t in self._bn("bbox_z3d_gl.1"))
-            s = g / torch.sqrt(v + BN_EPS)
-            P["anab.bn.scale"], P["anab.bn.shift"] = s.contiguous(), (be - m * s).contiguous()
+            bn = self._bn("bbox_z3d_gl.1")
+            P["anab.bn.scale"], P["anab.bn.shift"] = fold_affine(dev, bn[0].shape[0], None, bn)
 
         # constants of the align stages
         anchors = torch.as_tensor(np.asarray(self.conf.anchors), dtype=torch.float32)
@@ -697,17 +728,11 @@ class Engine:
             return plan
 
         # ---- RPN heads ----------------------------------------------------------------
-        fh, fw = feats0.h, feats0.w
-        HW = fh * fw
-        A, NC = self.A, self.NC
-        R = A * HW
-        cls_pl = torch.empty(B * NC * A * HW, device=self.device, dtype=torch.float32)
-        box_pl = torch.empty(B * 11 * A * HW, device=self.device, dtype=torch.float32)
-        plan.keep += [cls_pl, box_pl]
-        plan.named["cls_planar"], plan.named["box_planar"] = cls_pl, box_pl
-        # every op from here on may write the planar staging: a detection stage that reads it for the PREVIOUS batch
-        # (m3dssd_amd.pipeline.PipelinedDetector, planar form) has to be done before op `planar_first_op` of this one starts
-        plan.named["planar_first_op"] = len(plan.ops)
+        r = self._rpn_stage(plan, B, feats0.h, feats0.w)
+        fh, fw, HW, A, NC = r.fh, r.fw, r.HW, r.A, r.NC
+        with_shape, with_center, with_anab = self.flags
+        # detection-only tail: bbox_x3d / bbox_y3d feed feats_align3d, which ANAB pools over the whole map: dense in every launch
+        dense_heads = {"bbox_x3d", "bbox_y3d"} if with_center else set()
 
         def head_desc(p, x, planar, first):
             t, img_stride, ch_off = planar
@@ -724,7 +749,8 @@ class Engine:
             return d, flops
 
         def heads(items):
-            """1x1 heads with no mutual dependency as ONE fused-MLP launch (grid.y = head): items = [(p, x, planar)]."""
+            """1x1 heads with no mutual dependency as ONE fused-MLP launch (grid.y = head): items = [(p, x, planar)].  The 64-wide
+            launches have a row-list form for the tail: bit i of its mask = head i runs at the listed pixels only."""
             arr = (MlpDesc * len(items))()
             flops = 0.0
             for i, (p, x, planar) in enumerate(items):
@@ -734,6 +760,10 @@ class Engine:
             name = "+".join(p for p, _, _ in items) + ".mlp"
             plan.ops.append((name, "head_mlp<3,%d>" % arr[0].Cout_pad, flops,
                              lambda st: _hip.check(L.m3d_head_mlp_forward_batched(arr, n, st)), arr))
+            if arr[0].Cout_pad == 64:
+                mask = sum(1 << i for i, (p, _, _) in enumerate(items) if p not in dense_heads)
+                plan.sparse_form(lambda r: lambda st: _hip.check(L.m3d_head_mlp_forward_rows(
+                    arr, n, r.rows.data_ptr(), r.n_rows.data_ptr(), mask, st)))
 
         def head(p, x, planar, k0=1):
             """3-layer head.  A 1x1 head runs as one fused-MLP launch; the cls head runs its 3x3 conv through the
@@ -747,13 +777,81 @@ class Engine:
             plan.ops.append((p + ".mlp", "head_mlp<2,%d>" % d.Cout_pad, flops,
                              lambda st: _hip.check(L.m3d_head_mlp_forward(ref, st)), d))
 
-        head("cls", feats0, (cls_pl, NC * A * HW, 0), 3)
-        sel_idx = torch.empty(B * HW, device=self.device, dtype=torch.int32)
-        sel_prob = torch.empty(B * HW, device=self.device, dtype=torch.float32)
+        head("cls", feats0, (r.cls_pl, NC * A * HW, 0), 3)
+        self._rpn_select(plan, r)
+
+        # the stages the configuration has (M3d_inference_align.py:241-277): without shape_align the heads read feats0, without
+        # center_align the size heads read `feats`, without ANAB the z3d head reads feats_align3d; an absent stage's map is
+        # published under its reference name as an alias of the map that stands in for it
+        if with_shape:
+            om_sa = self._buf(plan, B, fh, fw, 27, 28)
+            self._rpn_shape_offsets(plan, r, om_sa, cost=True)
+            feats = self._buf(plan, B, fh, fw, c3, name="feats")
+            self._conv(plan, "shape_align.dcn", P["shape_align"], feats0, feats, 1, 1, act=0, res=feats0, om=om_sa)
+        else:
+            feats = plan.named["feats"] = feats0
+
+        def center_align(p, x, kx, ky, mi, out):
+            om = self._buf(plan, B, fh, fw, 3, 4)
+            self._rpn_center_offsets(plan, r, p, om, kx, ky, mi, cost=True)
+            self._conv(plan, p + ".dcn", P[p], x, out, 1, 0, act=0, res=x, om=om)
+
+        # heads are grouped by the feature map they read (M3d_inference_align.py:139-176): the four centre heads first,
+        # then both centre alignments, then the six size / orientation heads (+ z3d without ANAB).  Without the centre
+        # alignments every box head but an ANAB-fed z3d reads `feats`: one launch.
+        z3d_now = [] if with_anab else ["bbox_z3d"]
+        if with_center:
+            heads([("bbox_x", feats, r.box_planar(0)), ("bbox_y", feats, r.box_planar(1)),
+                   ("bbox_x3d", feats, r.box_planar(4)), ("bbox_y3d", feats, r.box_planar(5))])
+            f2d = self._buf(plan, B, fh, fw, c3, name="feats_align2d")
+            center_align("center_align2d", feats, 0, 1, 0, f2d)
+            f3d = self._buf(plan, B, fh, fw, c3, name="feats_align3d")
+            center_align("center_align3d", feats, 4, 5, 4, f3d)
+            heads([("bbox_w", f2d, r.box_planar(2)), ("bbox_h", f2d, r.box_planar(3))] +
+                  [(h, f3d, r.box_planar(self.box_heads.index(h))) for h in z3d_now + ["bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d"]])
+        else:
+            f2d = f3d = plan.named["feats_align2d"] = plan.named["feats_align3d"] = feats
+            heads([(h, feats, r.box_planar(k)) for k, h in enumerate(self.box_heads) if h != "bbox_z3d" or not with_anab])
+
+        # ---- ANAB ---------------------------------------------------------------------
+        if with_anab:
+            # zeroed: the tail's row-list attention writes it at the listed pixels only, and it is published in plan.named
+            gl = self._buf(plan, B, fh, fw, c3, name="feats_gl", zero=True)
+            self._anab_ops(plan, f3d, gl, P["anab.bn.scale"], P["anab.bn.shift"], act=1, res_mode=1)
+            head("bbox_z3d", gl, r.box_planar(6))
+        else:
+            plan.named["feats_gl"] = f3d
+
+        self._rpn_outputs(plan, r)
+        self._rpn_tail(plan, r)
+        return plan
+
+    # ------------------------------------------------------------------ RPN-stage steps shared by the fp32 and the bf16 plan
+    # (what they launch reads and writes fp32 / integer data in both: the planar staging, the selection, the align offsets)
+    def _rpn_stage(self, plan, B, fh, fw):
+        """The stage's record with the planar fp32 staging of the head outputs: cls [B][NC][A][HW], box [B][11][A][HW]."""
+        r = _RpnStage(B, self.A, self.NC, fh, fw)
+        r.cls_pl = torch.empty(B * r.NC * r.R, device=self.device, dtype=torch.float32)
+        r.box_pl = torch.empty(B * 11 * r.R, device=self.device, dtype=torch.float32)
+        plan.keep += [r.cls_pl, r.box_pl]
+        plan.named["cls_planar"], plan.named["box_planar"] = r.cls_pl, r.box_pl
+        # every op from here on may write the planar staging: a detection stage that reads it for the PREVIOUS batch
+        # (m3dssd_amd.pipeline.PipelinedDetector, planar form) has to be done before op `planar_first_op` of this one starts
+        plan.named["planar_first_op"] = len(plan.ops)
+        r.means = np.asarray(self.conf.bbox_means, dtype=np.float32).reshape(-1)
+        r.stds = np.asarray(self.conf.bbox_stds, dtype=np.float32).reshape(-1)
+        return r
+
+    def _rpn_select(self, plan, r):
+        """anchor_select behind the class head: per pixel the best anchor and its foreground probability."""
+        L, B, A, NC, HW = self.L, r.B, r.A, r.NC, r.HW
+        cls_pl = r.cls_pl
+        sel_idx = r.sel_idx = torch.empty(B * HW, device=self.device, dtype=torch.int32)
+        sel_prob = r.sel_prob = torch.empty(B * HW, device=self.device, dtype=torch.float32)
         plan.keep += [sel_idx, sel_prob]
         plan.named["sel_idx"], plan.named["sel_prob"] = sel_idx, sel_prob
         if NC == 4 and A >= 4 and SELECT_KEYS:
-            # + the detection stage's sort keys (plan.named["score_bits"], created below) while the logits are in registers
+            # + the detection stage's sort keys (plan.named["score_bits"], created by _rpn_outputs) while the logits are in registers
             plan.named["keys_by_select"] = True
             plan.named["score_bits_first_write_op"] = len(plan.ops)     # a detect(k-1) beside forward(k) must be done before it
             self._op(plan, "anchor_select", "select", lambda st: _hip.check(L.m3d_anchor_select_keys(
@@ -764,72 +862,37 @@ class Engine:
                 cls_pl.data_ptr(), B, A, NC, HW, sel_idx.data_ptr(), sel_prob.data_ptr(), None, st)),
                 nbytes=B * HW * (A * NC + 2) * 4)
 
-        means = np.asarray(self.conf.bbox_means, dtype=np.float32).reshape(-1)
-        stds = np.asarray(self.conf.bbox_stds, dtype=np.float32).reshape(-1)
+    def _rpn_shape_offsets(self, plan, r, om, cost):
+        """shape_align's DCN offsets (27 per pixel into `om`) from the selected anchor's shape; the DCN itself is the caller's.
+        cost: state the launch's HBM bytes (the fp32 plan does, the bf16 plan never did)."""
+        L, P, B, A, HW = self.L, self.P, r.B, r.A, r.HW
+        self._op(plan, "shape_align.offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
+            0, r.sel_idx.data_ptr(), r.sel_prob.data_ptr(), 0.5, P["shape.table"].data_ptr(), None, None, None, 0.0, 1.0, 0.0,
+            1.0, om.ptr, om.cs, B, A, HW, 9, 0, st)), nbytes=B * HW * (2 + 28) * 4 if cost else None)
 
-        def box_planar(k):
-            return (box_pl, 11 * A * HW, k * A)
+    def _rpn_center_offsets(self, plan, r, p, om, kx, ky, mi, cost):
+        """The DCN offsets of centre alignment p (3 per pixel into `om`) from box rows kx, ky of the staging, de-normalised with
+        means / stds [mi], [mi + 1]; the DCN itself is the caller's.  center_align2d has a gated form for the tail: the 1x1
+        alignment is a per-pixel function, so behind sparse bbox_x / bbox_y it reads them at the needed pixels only."""
+        L, P, B, A, HW = self.L, self.P, r.B, r.A, r.HW
+        ms = (float(r.means[mi]), float(r.stds[mi]), float(r.means[mi + 1]), float(r.stds[mi + 1]))
+        self._op(plan, p + ".offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
+            1, r.sel_idx.data_ptr(), r.sel_prob.data_ptr(), 0.5, None, r.box_ptr(kx), r.box_ptr(ky), P["anchor_wh"].data_ptr(),
+            *ms, om.ptr, om.cs, B, A, HW, 1, 11 * A * HW, st)), nbytes=B * HW * (2 + 2 + 4) * 4 if cost else None)
+        if p == "center_align2d":
+            plan.sparse_form(lambda r: lambda st: _hip.check(L.m3d_align_offsets_gated(
+                r.sel_idx.data_ptr(), r.sel_prob.data_ptr(), 0.5, r.box_ptr(kx), r.box_ptr(ky), P["anchor_wh"].data_ptr(), *ms,
+                r.need.data_ptr(), om.ptr, om.cs, B, A, HW, 11 * A * HW, st)))
 
-        def box_ptr(k):
-            return box_pl.data_ptr() + 4 * k * A * HW          # image 0; per-image stride handled via [B][11][A][HW]
-
-        # the stages the configuration has (M3d_inference_align.py:241-277): without shape_align the heads read feats0, without
-        # center_align the size heads read `feats`, without ANAB the z3d head reads feats_align3d; an absent stage's map is
-        # published under its reference name as an alias of the map that stands in for it
-        with_shape, with_center, with_anab = self.flags
-        if with_shape:
-            om_sa = self._buf(plan, B, fh, fw, 27, 28)
-            self._op(plan, "shape_align.offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
-                0, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, P["shape.table"].data_ptr(), None, None, None, 0.0, 1.0, 0.0,
-                1.0, om_sa.ptr, om_sa.cs, B, A, HW, 9, 0, st)), nbytes=B * HW * (2 + 28) * 4)
-            feats = self._buf(plan, B, fh, fw, c3, name="feats")
-            self._conv(plan, "shape_align.dcn", P["shape_align"], feats0, feats, 1, 1, act=0, res=feats0, om=om_sa)
-        else:
-            feats = plan.named["feats"] = feats0
-
-        align_args = {}                  # p -> what a gated form of p's offsets launch needs (detection-only tail)
-
-        def center_align(p, x, kx, ky, mi, out):
-            om = self._buf(plan, B, fh, fw, 3, 4)
-            align_args[p] = (om, kx, ky, mi)
-            self._op(plan, p + ".offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
-                1, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, None, box_ptr(kx), box_ptr(ky),
-                P["anchor_wh"].data_ptr(), float(means[mi]), float(stds[mi]), float(means[mi + 1]),
-                float(stds[mi + 1]), om.ptr, om.cs, B, A, HW, 1, 11 * A * HW, st)), nbytes=B * HW * (2 + 2 + 4) * 4)
-            self._conv(plan, p + ".dcn", P[p], x, out, 1, 0, act=0, res=x, om=om)
-
-        # heads are grouped by the feature map they read (M3d_inference_align.py:139-176): the four centre heads first,
-        # then both centre alignments, then the six size / orientation heads (+ z3d without ANAB).  Without the centre
-        # alignments every box head but an ANAB-fed z3d reads `feats`: one launch.
-        z3d_now = [] if with_anab else ["bbox_z3d"]
-        if with_center:
-            heads([("bbox_x", feats, box_planar(0)), ("bbox_y", feats, box_planar(1)),
-                   ("bbox_x3d", feats, box_planar(4)), ("bbox_y3d", feats, box_planar(5))])
-            f2d = self._buf(plan, B, fh, fw, c3, name="feats_align2d")
-            center_align("center_align2d", feats, 0, 1, 0, f2d)
-            f3d = self._buf(plan, B, fh, fw, c3, name="feats_align3d")
-            center_align("center_align3d", feats, 4, 5, 4, f3d)
-            heads([("bbox_w", f2d, box_planar(2)), ("bbox_h", f2d, box_planar(3))] +
-                  [(h, f3d, box_planar(self.box_heads.index(h))) for h in z3d_now + ["bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d"]])
-        else:
-            f2d = f3d = plan.named["feats_align2d"] = plan.named["feats_align3d"] = feats
-            heads([(h, feats, box_planar(k)) for k, h in enumerate(self.box_heads) if h != "bbox_z3d" or not with_anab])
-
-        # ---- ANAB ---------------------------------------------------------------------
-        if with_anab:
-            # zeroed: the tail's row-list attention writes it at the listed pixels only, and it is published in plan.named
-            gl = self._buf(plan, B, fh, fw, c3, name="feats_gl", zero=True)
-            self._anab_ops(plan, f3d, gl, P["anab.bn.scale"], P["anab.bn.shift"], act=1, res_mode=1)
-            head("bbox_z3d", gl, box_planar(6))
-        else:
-            plan.named["feats_gl"] = f3d
-
-        # ---- outputs ------------------------------------------------------------------
+    def _rpn_outputs(self, plan, r):
+        """The bundled outputs [B, R, .] and the op that writes them from the planar staging."""
+        L, B, A, NC, HW, R = self.L, r.B, r.A, r.NC, r.HW, r.R
+        cls_pl, box_pl = r.cls_pl, r.box_pl
         cls = torch.empty(B, R, NC, device=self.device, dtype=torch.float32)
         prob = torch.empty(B, R, NC, device=self.device, dtype=torch.float32)
         b2 = torch.empty(B, R, 4, device=self.device, dtype=torch.float32)
         b3 = torch.empty(B, R, 7, device=self.device, dtype=torch.float32)
-        key = torch.empty(B, R, device=self.device, dtype=torch.int32)   # monotone score bits (u32)
+        key = r.key = torch.empty(B, R, device=self.device, dtype=torch.int32)   # monotone score bits (u32)
         plan.named.update(cls=cls, prob=prob, bbox_2d=b2, bbox_3d=b3, score_bits=key)
         assert NC == 4, "bundle kernel is written for 4 classes (bg + 3)"
         # destination of the four bundled outputs: the plan's own buffers, or -- for one forward -- fresh tensors handed in by
@@ -838,62 +901,44 @@ class Engine:
         self._op(plan, "bundle_outputs", "bundle", lambda st: _hip.check(L.m3d_bundle_outputs(
             cls_pl.data_ptr(), box_pl.data_ptr(), dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), dst[3].data_ptr(),
             key.data_ptr(), B, A, HW, st)), nbytes=B * R * (NC + 11 + 2 * NC + 4 + 7 + 1) * 4)
-        plan.feat = (fh, fw)
 
-        # ---- detection-only tail ------------------------------------------------------
-        # m3d_topk_decode_planar reads the box staging at the nms_topN_pre best rows of an image and nowhere else, the score is a
-        # function of the class head alone (anchor_select has written the keys), and row a * HW + pix belongs to pixel pix: a box
-        # head whose planar output feeds nothing but the decode is needed at the pixels that hold one of those rows.  The centre
-        # alignments are 1x1 (feats_align2d[p] depends on bbox_x[p], bbox_y[p] and the dense `feats`), so with them bbox_x / bbox_y
-        # stay sparse behind gated offsets; bbox_x3d / bbox_y3d feed feats_align3d, which ANAB pools over the whole map: dense.
-        if plan.named.get("keys_by_select"):
-            t0 = plan.named["score_bits_first_write_op"] + 1
-            # zeroed: the dense forward (plan.ops) never writes them, and the list is written up to n_rows only -- they are
-            # published in plan.named and must not show what the allocation held (uninitialised memory)
-            need = torch.zeros(B * HW, device=self.device, dtype=torch.uint8)
-            rows = torch.zeros(B * HW, device=self.device, dtype=torch.int32)
-            n_rows = torch.zeros(1, device=self.device, dtype=torch.int32)
-            thresh = torch.zeros(B, device=self.device, dtype=torch.int32)
-            nb = L.m3d_need_rows_workspace_bytes(B, HW)
-            ws = torch.empty(nb, device=self.device, dtype=torch.uint8)
-            plan.keep += [need, rows, n_rows, thresh, ws]
-            plan.named.update(need=need, need_rows=rows, n_rows=n_rows, need_thresh=thresh)
-            k_pre = plan.named["sparse_k"] = [min(int(self.conf.nms_topN_pre), R)]      # set by the caller at launch time
-            tail = [("need_rows", "select", 0.0, lambda st: _hip.check(L.m3d_need_rows(
-                key.data_ptr(), B, A, HW, int(k_pre[0]), thresh.data_ptr(), need.data_ptr(), rows.data_ptr(), n_rows.data_ptr(),
-                ws.data_ptr(), nb, st)), OpCost(B * R * 4 * 4))]
-            dense_heads = {"bbox_x3d", "bbox_y3d"} if with_center else set()
-
-            def rows_op(op):
-                name, kind, flops, _, arr = op
-                hs = name[:-len(".mlp")].split("+")
-                mask = sum(1 << i for i, h in enumerate(hs) if h not in dense_heads)
-                n = len(hs)
-                return (name, kind, flops, lambda st: _hip.check(L.m3d_head_mlp_forward_rows(
-                    arr, n, rows.data_ptr(), n_rows.data_ptr(), mask, st)), arr)
-
-            def gated_op(op, p):
-                om, kx, ky, mi = align_args[p]
-                return op[:3] + (lambda st: _hip.check(L.m3d_align_offsets_gated(
-                    sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, box_ptr(kx), box_ptr(ky), P["anchor_wh"].data_ptr(),
-                    float(means[mi]), float(stds[mi]), float(means[mi + 1]), float(stds[mi + 1]), need.data_ptr(), om.ptr, om.cs,
-                    B, A, HW, 11 * A * HW, st)), op[4])
-
-            # feats_gl feeds bbox_z3d and nothing else, and that head runs at the listed pixels: so does the attention behind the
-            # dense K | V | S projection and pooling (its queries, softmax, P.V and epilogue are per-pixel functions)
-            attend_rows = getattr(plan, "anab_attend", None) if ANAB_ROWS else None
-
-            for op in plan.ops[t0:-1]:
-                if op[1] == "head_mlp<3,64>":
-                    op = rows_op(op)
-                elif op[0] == "anab.attend" and attend_rows is not None:
-                    op = op[:3] + (attend_rows(L.m3d_anab_attend_f32_rows, rows.data_ptr(), n_rows.data_ptr()), op[4])
-                elif op[0] == "center_align2d.offsets":
-                    op = gated_op(op, "center_align2d")
-                tail.append(op)
-            plan.tail, plan.tail_start = tail, t0
-        return plan
-
+    def _rpn_tail(self, plan, r):
+        """The detection-only tail (plan.tail) of a plan whose anchor_select writes the keys.
+        m3d_topk_decode_planar reads the box staging at the nms_topN_pre best rows of an image and nowhere else, the score is a
+        function of the class head alone (anchor_select has written the keys), and row a * HW + pix belongs to pixel pix: a box
+        head whose planar output feeds nothing but the decode is needed at the pixels that hold one of those rows.  The centre
+        alignments are 1x1 (feats_align2d[p] depends on bbox_x[p], bbox_y[p] and the dense `feats`), so with them bbox_x / bbox_y
+        stay sparse behind gated offsets; bbox_x3d / bbox_y3d feed feats_align3d, which ANAB pools over the whole map: dense.
+        feats_gl feeds bbox_z3d and nothing else, and that head runs at the listed pixels: so does the attention behind the dense
+        projection and pooling (its queries, softmax, P.V and epilogue are per-pixel functions).
+        What the selection reads and writes is fp32 / integer in the bf16 plan too, so m3d_need_rows and m3d_align_offsets_gated
+        serve both.  An op has a sparse form where the code that appended it registered one (plan.sparse); every other op of
+        ops[tail_start:-1] is taken as it is.  A registration in front of anchor_select (ANAB + z3d of the bf16 ANAB-only
+        configuration, which run beside the class head) is not looked at: those ops run before the selection exists and stay dense.
+        Issued on one stream (run_plan(tail=True)): a side branch of the plan is time-neutral here."""
+        if not plan.named.get("keys_by_select"):
+            return
+        L, B, A, HW, R = self.L, r.B, r.A, r.HW, r.R
+        t0 = plan.named["score_bits_first_write_op"] + 1
+        # zeroed: the dense forward (plan.ops) never writes them, and the list is written up to n_rows only -- they are
+        # published in plan.named and must not show what the allocation held (DESIGN.md section 2, uninitialised memory)
+        need = r.need = torch.zeros(B * HW, device=self.device, dtype=torch.uint8)
+        rows = r.rows = torch.zeros(B * HW, device=self.device, dtype=torch.int32)
+        n_rows = r.n_rows = torch.zeros(1, device=self.device, dtype=torch.int32)
+        thresh = torch.zeros(B, device=self.device, dtype=torch.int32)
+        nb = L.m3d_need_rows_workspace_bytes(B, HW)
+        ws = torch.empty(nb, device=self.device, dtype=torch.uint8)
+        plan.keep += [need, rows, n_rows, thresh, ws]
+        plan.named.update(need=need, need_rows=rows, n_rows=n_rows, need_thresh=thresh)
+        k_pre = plan.named["sparse_k"] = [min(int(self.conf.nms_topN_pre), R)]      # set by the caller at launch time
+        key = r.key
+        tail = [("need_rows", "select", 0.0, lambda st: _hip.check(L.m3d_need_rows(
+            key.data_ptr(), B, A, HW, int(k_pre[0]), thresh.data_ptr(), need.data_ptr(), rows.data_ptr(), n_rows.data_ptr(),
+            ws.data_ptr(), nb, st)), OpCost(B * R * 4 * 4))]
+        for i in range(t0, len(plan.ops) - 1):
+            op, sparse = plan.ops[i], plan.sparse.get(i)
+            tail.append(op if sparse is None else op[:3] + (sparse(r), op[4]))
+        plan.tail, plan.tail_start = tail, t0
 
     def _dla102_levels(self, plan, l1, maxpool):
         """level2 .. level5 of DLA-102 (pose_dla_dcn.py:162-200,261-327): Trees of Bottlenecks of depth 1, 3, 4, 1 with residual
@@ -1025,10 +1070,11 @@ class Engine:
                     qv.ptr, qv.cs, khat.data_ptr(), self.ck_pad, vhatT.data_ptr(), B, HW, self.ck, n_bins, keys_pad, self.cv, rp,
                     rcs, res_mode, sp, hp, 1 if act else 0, out.ptr, out.cs, *row_list, st))
 
-            plan.anab_attend = attend       # (the detection-only tail builds its row-list form from it)
             self._op(plan, "anab.attend", "anab_attend", attend(L.m3d_anab_attend_f32),
                      flops=2.0 * B * HW * n_bins * (self.ck + self.cv),
                 nbytes=B * HW * (self.ck + 3 * self.cv) * 4 + B * keys_pad * (self.ck + self.cv) * 4)
+            if ANAB_ROWS:
+                plan.sparse_form(lambda r: attend(L.m3d_anab_attend_f32_rows, r.rows.data_ptr(), r.n_rows.data_ptr()))
             return
 
         def image(v, i):

@@ -17,12 +17,11 @@ with the fp32 oracle to ~1e-1 absolute (measured and asserted in tests/test_gpu_
 import ctypes
 import os
 
-import numpy as np
 import torch
 
 from . import _hip
 from ._hip import ConvBf16Desc, Head2Bf16Desc, HeadBf16Desc, QkvsBf16Desc, Tail2Bf16Desc, TreeEntryBf16Desc
-from .engine import BN_EPS, PSP_SIZES, SELECT_KEYS, Engine, OpCost, _Plan, _rup
+from .engine import PSP_SIZES, Engine, OpCost, _Plan, _rup, fold_affine
 
 BF16 = torch.bfloat16
 FUSED_ANAB = os.environ.get("M3D_BF16_FUSED_ANAB", "1") != "0"
@@ -212,16 +211,7 @@ class PackedBf16:
         self.cout, self.cin, self.kh, self.kw = weight.shape
         self.wp, self.kpad = pack_conv_bf16(weight, cout_pad, None, dev)
         self.cout_pad = self.wp.shape[0]
-        scale = torch.ones(self.cout, device=dev, dtype=torch.float32)
-        shift = torch.zeros(self.cout, device=dev, dtype=torch.float32)
-        if bias is not None:
-            shift = bias.detach().to(dev, torch.float32).clone()
-        if bn is not None:
-            g, b, m, v = (t.detach().to(dev, torch.float32) for t in bn)
-            s = g / torch.sqrt(v + BN_EPS)
-            shift = (shift - m) * s + b
-            scale = s
-        self.scale, self.shift = scale.contiguous(), shift.contiguous()
+        self.scale, self.shift = fold_affine(dev, self.cout, bias, bn)
         self.has_affine = (bias is not None) or (bn is not None)
 
 
@@ -233,96 +223,28 @@ class EngineBF16(Engine):
         sd = self.sd
         return PackedBf16(self, sd[conv + ".weight"], sd.get(conv + ".bias"), self._bn(bn) if bn else None, **kw)
 
-    def _pack(self, sd):
-        dev = self.device
-        P = {}
+    DCN_PACK = {}                       # no output-channel padding beyond PackedBf16's own
+
+    def _pack_front(self, sd, P):
+        """Front-end extra of this engine: stem, level0 and level1 as the operands of the one-launch front end."""
         b = "base.base"
-        w = sd[b + ".base_layer.0.weight"].detach().to(dev, torch.float32)
-        P["stem.w"] = w.permute(2, 3, 1, 0).contiguous()
-        g, be, m, v = (t.detach().to(dev, torch.float32) for t in self._bn(b + ".base_layer.1"))
-        s = g / torch.sqrt(v + BN_EPS)
-        P["stem.scale"], P["stem.shift"] = s.contiguous(), (be - m * s).contiguous()
-        P["level0"] = self._pc(b + ".level0.0", b + ".level0.1")
-        P["level1"] = self._pc(b + ".level1.0", b + ".level1.1")
         P["front2"] = pack_frontend_f16(sd[b + ".base_layer.0.weight"], (P["stem.scale"], P["stem.shift"]),
                                         sd[b + ".level0.0.weight"], (P["level0"].scale, P["level0"].shift),
-                                        sd[b + ".level1.0.weight"], (P["level1"].scale, P["level1"].shift), dev)
+                                        sd[b + ".level1.0.weight"], (P["level1"].scale, P["level1"].shift), self.device)
 
-        def block(p):
-            P[p + ".conv1"] = self._pc(p + ".conv1", p + ".bn1")
-            P[p + ".conv2"] = self._pc(p + ".conv2", p + ".bn2")
+    def _pack_head(self, sd, P, p):
+        P[p + ".0"] = self._pc(p + ".0", p + ".1")
+        P[p + ".3"] = self._pc(p + ".3", p + ".4")
+        P[p + ".6"] = self._pc(p + ".6", cout_pad=_rup(sd[p + ".6.weight"].shape[0], 64))
 
-        def tree1(p):
-            block(p + ".tree1")
-            block(p + ".tree2")
-            P[p + ".root"] = self._pc(p + ".root.conv", p + ".root.bn")
-            if (p + ".project.0.weight") in sd:
-                P[p + ".project"] = self._pc(p + ".project.0", p + ".project.1")
-
-        tree1(b + ".level2")
-        for lv in (3, 4):
-            tree1("%s.level%d.tree1" % (b, lv))
-            tree1("%s.level%d.tree2" % (b, lv))
-        tree1(b + ".level5")
-
-        def deform(p):
-            P[p + ".om"] = self._pc(p + ".conv.conv_offset_mask")
-            P[p + ".dcn"] = PackedBf16(self, sd[p + ".conv.weight"], sd[p + ".conv.bias"], self._bn(p + ".actf.0"))
-
-        def ida(p, n):
-            for i in range(1, n):
-                deform("%s.proj_%d" % (p, i))
-                deform("%s.node_%d" % (p, i))
-                up = sd["%s.up_%d.weight" % (p, i)].detach().to(dev, torch.float32)
-                P["%s.up_%d" % (p, i)] = up[:, 0].permute(1, 2, 0).contiguous()
-
-        ida("base.dla_up.ida_0", 2)
-        ida("base.dla_up.ida_1", 3)
-        ida("base.ida_up", 2)
-        self.P = P
-        if not self.backbone_only:
-            self._pack_heads_bf16(sd, P)
-        torch.cuda.synchronize(self.device)
-
-    def _pack_heads_bf16(self, sd, P):
-        dev = self.device
-        self.box_heads = ["bbox_x", "bbox_y", "bbox_w", "bbox_h", "bbox_x3d", "bbox_y3d", "bbox_z3d", "bbox_w3d",
-                          "bbox_h3d", "bbox_l3d", "bbox_rY3d"]
-        for p in ["cls"] + self.box_heads:
-            P[p + ".0"] = self._pc(p + ".0", p + ".1")
-            P[p + ".3"] = self._pc(p + ".3", p + ".4")
-            P[p + ".6"] = self._pc(p + ".6", cout_pad=_rup(sd[p + ".6.weight"].shape[0], 64))
-        with_shape, with_center, with_anab = self.flags
-        for p in ("shape_align",) * with_shape + ("center_align2d", "center_align3d") * with_center:
-            P[p] = PackedBf16(self, sd[p + ".align.weight"], sd[p + ".align.bias"], None)
-        if with_anab:
-            a = "bbox_z3d_gl.0"
-            wq, wk, wv, ws = (sd[a + n].detach().cpu().float() for n in
-                              (".query_conv.weight", ".key_conv.weight", ".value_conv.weight", ".spatial_conv.weight"))
-            self.ck, self.cv, self.ns = wq.shape[0], wv.shape[0], ws.shape[0]
-            self.ck_pad = _rup(self.ck, 64)                                  # K of the logits GEMM
-            P["anab.q"] = PackedBf16(self, wq, None, None, cout_pad=self.ck_pad)
-            P["anab.kvs"] = PackedBf16(self, torch.cat([wk, wv, ws], 0), None, None)
-            P["anab.kv"] = PackedBf16(self, torch.cat([wk, wv], 0), None, None)          # bf16 K|V map + fp32 gates (KV_BF16)
-            P["anab.s"] = PackedBf16(self, ws, None, None)
-            g, be, m, v = (t.detach().to(dev, torch.float32) for t in self._bn("bbox_z3d_gl.1"))
-            s = g / torch.sqrt(v + BN_EPS)
-            P["anab.bn.scale"], P["anab.bn.shift"] = s.contiguous(), (be - m * s).contiguous()
-        anchors = torch.as_tensor(np.asarray(self.conf.anchors), dtype=torch.float32)
-        aw = (anchors[:, 2] - anchors[:, 0])
-        ah = (anchors[:, 3] - anchors[:, 1])
-        tab = torch.zeros(self.A, 18, dtype=torch.float32)
-        h_step, w_step = ah / self.stride / 3, aw / self.stride / 3
-        for i in range(3):
-            for j in range(3):
-                k = i * 3 + j
-                tab[:, 2 * k] = (h_step - 1) * (i - 3 / 2 + 0.5)
-                tab[:, 2 * k + 1] = (w_step - 1) * (j - 3 / 2 + 0.5)
-        P["shape.table"] = tab.to(dev).contiguous()
-        P["anchor_wh"] = torch.stack([aw / self.stride, ah / self.stride], 1).to(dev).contiguous()
-        P["anchors"] = anchors.to(dev).contiguous()
-        P["means"] = torch.as_tensor(np.asarray(self.conf.bbox_means), dtype=torch.float32).reshape(-1).to(dev)
-        P["stds"] = torch.as_tensor(np.asarray(self.conf.bbox_stds), dtype=torch.float32).reshape(-1).to(dev)
+    def _pack_anab(self, P, wq, wk, wv, ws):
+        wq, wk, wv, ws = (w.detach().cpu().float() for w in (wq, wk, wv, ws))
+        self.ck, self.cv, self.ns = wq.shape[0], wv.shape[0], ws.shape[0]
+        self.ck_pad = _rup(self.ck, 64)                                  # K of the logits GEMM
+        P["anab.q"] = PackedBf16(self, wq, None, None, cout_pad=self.ck_pad)
+        P["anab.kvs"] = PackedBf16(self, torch.cat([wk, wv, ws], 0), None, None)
+        P["anab.kv"] = PackedBf16(self, torch.cat([wk, wv], 0), None, None)          # bf16 K|V map + fp32 gates (KV_BF16)
+        P["anab.s"] = PackedBf16(self, ws, None, None)
 
     # ------------------------------------------------------------------ launch helpers
     def _buf16(self, plan, n, h, w, c, cs=None, name=None, dtype=BF16, zero=False):
@@ -568,17 +490,11 @@ class EngineBF16(Engine):
             return plan
 
         # ---- RPN heads ----------------------------------------------------------------
-        fh, fw = feats0.h, feats0.w
-        HW = fh * fw
-        A, NC = self.A, self.NC
-        R = A * HW
-        cls_pl = torch.empty(B * NC * A * HW, device=self.device, dtype=torch.float32)
-        box_pl = torch.empty(B * 11 * A * HW, device=self.device, dtype=torch.float32)
-        plan.keep += [cls_pl, box_pl]
-        plan.named["cls_planar"], plan.named["box_planar"] = cls_pl, box_pl
-        # every op from here on may write the planar staging: a detection stage that reads it for the PREVIOUS batch
-        # (m3dssd_amd.pipeline.PipelinedDetector, planar form) has to be done before op `planar_first_op` of this one starts
-        plan.named["planar_first_op"] = len(plan.ops)
+        # (the steps shared with the fp32 plan -- staging, selection, align offsets, outputs, tail -- are Engine._rpn_*)
+        r = self._rpn_stage(plan, B, feats0.h, feats0.w)
+        fh, fw, HW, A, NC = r.fh, r.fw, r.HW, r.A, r.NC
+        cls_pl, box_pl = r.cls_pl, r.box_pl
+        with_shape, with_center, with_anab = self.flags
 
         def stacked(names, li):
             key = "stack:" + "+".join(names) + li
@@ -616,6 +532,11 @@ class EngineBF16(Engine):
                 flops = 2.0 * B * HW * G * (128 * 256 + 256 * 256 + 256 * A)
                 plan.ops.append(("+".join(names) + ".mlp", "bf16_head2", flops,
                                  lambda st: _hip.check(L.m3d_head_mlp2_bf16_forward(ref, st)), d))
+                # detection-only tail: a launch is wholly sparse or wholly dense; with the centre alignments bbox_x3d + bbox_y3d feed
+                # feats_align3d, which ANAB pools over the whole map.  Heads that do not run as bf16_head2 stay dense too.
+                if not (with_center and names == ["bbox_x3d", "bbox_y3d"]):
+                    plan.sparse_form(lambda r: lambda st: _hip.check(L.m3d_head_mlp2_bf16_forward_rows(
+                        ref, r.rows.data_ptr(), r.n_rows.data_ptr(), st)))
                 return
             if FUSED_HEADS and x.c == 128 and cp == 64:
                 d = HeadBf16Desc()
@@ -651,7 +572,6 @@ class EngineBF16(Engine):
 
         # the stages the configuration has (M3d_inference_align.py:241-277); an absent stage's map is published under its
         # reference name as an alias of the map that stands in for it
-        with_shape, with_center, with_anab = self.flags
         branch = None
         if with_anab and not (with_shape or with_center):
             # ANAB reads feats0: its side branch starts where feats0 is ready, beside the cls head and the box heads
@@ -682,50 +602,24 @@ class EngineBF16(Engine):
             self._pconv(plan, "cls.3", P["cls.3"], c1, c2, 1, 0, act=1)
             self._conv16(plan, "cls.6", c2, None, wgt=pc.wp, kpad=pc.kpad, cout=pc.cout, cout_pad=pc.cout_pad, scale=pc.scale,
                          shift=pc.shift, planar=(cls_pl, NC * A * HW, 0), cin=256)
-        sel_idx = torch.empty(B * HW, device=self.device, dtype=torch.int32)
-        sel_prob = torch.empty(B * HW, device=self.device, dtype=torch.float32)
-        plan.keep += [sel_idx, sel_prob]
-        plan.named["sel_idx"], plan.named["sel_prob"] = sel_idx, sel_prob
-        if NC == 4 and A >= 4 and SELECT_KEYS:
-            # + the detection stage's sort keys (plan.named["score_bits"], created below) while the logits are in registers
-            plan.named["keys_by_select"] = True
-            plan.named["score_bits_first_write_op"] = len(plan.ops)     # a detect(k-1) beside forward(k) must be done before it
-            self._op(plan, "anchor_select", "select", lambda st: _hip.check(L.m3d_anchor_select_keys(
-                cls_pl.data_ptr(), B, A, HW, sel_idx.data_ptr(), sel_prob.data_ptr(), plan.named["score_bits"].data_ptr(), st)),
-                nbytes=B * HW * (A * NC + 2 + A) * 4)
-        else:
-            self._op(plan, "anchor_select", "select", lambda st: _hip.check(L.m3d_anchor_select(
-                cls_pl.data_ptr(), B, A, NC, HW, sel_idx.data_ptr(), sel_prob.data_ptr(), None, st)),
-                nbytes=B * HW * (A * NC + 2) * 4)
-        means = np.asarray(self.conf.bbox_means, dtype=np.float32).reshape(-1)
-        stds = np.asarray(self.conf.bbox_stds, dtype=np.float32).reshape(-1)
-
-        def box_ptr(k):
-            return box_pl.data_ptr() + 4 * k * A * HW
+        self._rpn_select(plan, r)
 
         if with_shape:
             om_sa = self._buf16(plan, B, fh, fw, 27, 28, dtype=torch.float32)
-            self._op(plan, "shape_align.offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
-                0, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, P["shape.table"].data_ptr(), None, None, None, 0.0, 1.0, 0.0,
-                1.0, om_sa.ptr, om_sa.cs, B, A, HW, 9, 0, st)))
+            self._rpn_shape_offsets(plan, r, om_sa, cost=False)
             feats = self._buf16(plan, B, fh, fw, 128, name="feats")
             self._pconv(plan, "shape_align.dcn", P["shape_align"], feats0, feats, 1, 1, act=0, res=feats0, om=om_sa,
                         patch=SHAPE_PATCH)   # anchor-shaped offsets (up to half an anchor): which tiles fit the LDS window is decided per tile
         else:
             feats = plan.named["feats"] = feats0
 
-        align_args = {}                  # p -> what a gated form of p's offsets launch needs (detection-only tail)
         if with_center:
             heads(["bbox_x", "bbox_y"], feats, 0)
             heads(["bbox_x3d", "bbox_y3d"], feats, 4)
 
             def center_align(p, x, kx, ky, mi, out):
                 om = self._buf16(plan, B, fh, fw, 3, 4, dtype=torch.float32)
-                align_args[p] = (om, kx, ky, mi)
-                self._op(plan, p + ".offsets", "align", lambda st: _hip.check(L.m3d_align_offsets(
-                    1, sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, None, box_ptr(kx), box_ptr(ky),
-                    P["anchor_wh"].data_ptr(), float(means[mi]), float(stds[mi]), float(means[mi + 1]),
-                    float(stds[mi + 1]), om.ptr, om.cs, B, A, HW, 1, 11 * A * HW, st)))
+                self._rpn_center_offsets(plan, r, p, om, kx, ky, mi, cost=False)
                 self._pconv(plan, p + ".dcn", P[p], x, out, 1, 0, act=0, res=x, om=om)
 
             f2d = self._buf16(plan, B, fh, fw, 128, name="feats_align2d")
@@ -760,68 +654,9 @@ class EngineBF16(Engine):
         elif BRANCH:
             plan.branches.append(branch + (len(plan.ops),))
 
-        cls = torch.empty(B, R, NC, device=self.device, dtype=torch.float32)
-        prob = torch.empty(B, R, NC, device=self.device, dtype=torch.float32)
-        b2 = torch.empty(B, R, 4, device=self.device, dtype=torch.float32)
-        b3 = torch.empty(B, R, 7, device=self.device, dtype=torch.float32)
-        key = torch.empty(B, R, device=self.device, dtype=torch.int32)
-        plan.named.update(cls=cls, prob=prob, bbox_2d=b2, bbox_3d=b3, score_bits=key)
-        # destination of the four bundled outputs: the plan's own buffers, or -- for one forward -- fresh tensors handed in by
-        # Engine.forward(fresh=True) (RPN.forward returns fresh tensors like the reference: written in place, no copies)
-        dst = plan.named["out_dst"] = [cls, prob, b2, b3]
-        self._op(plan, "bundle_outputs", "bundle", lambda st: _hip.check(L.m3d_bundle_outputs(
-            cls_pl.data_ptr(), box_pl.data_ptr(), dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), dst[3].data_ptr(),
-            key.data_ptr(), B, A, HW, st)), nbytes=B * R * (NC + 11 + 2 * NC + 4 + 7 + 1) * 4)
-
-        # ---- detection-only tail ------------------------------------------------------
-        # The fp32 plan's argument (Engine._build_plan) carries over: the top-k decode reads the box staging at the nms_topN_pre best
-        # rows of an image, the score is a function of the class head alone, row a * HW + pix belongs to pixel pix, and every box head
-        # and the 1x1 centre alignments are per-pixel functions.  What the selection reads and writes is fp32 / integer here too, so
-        # m3d_need_rows and m3d_align_offsets_gated serve as they are.  A launch of this plan is wholly sparse or wholly dense:
-        # bbox_x3d + bbox_y3d have a launch of their own, and with the centre alignments they feed feats_align3d, which ANAB pools
-        # over the whole map.  Ops in front of anchor_select (ANAB + z3d of the ANAB-only configuration) stay dense, and so do heads
-        # that do not run as bf16_head2.  Issued on one stream (Engine.run_plan(tail=True)): the side branch is time-neutral here.
-        if SPARSE_TAIL and plan.named.get("keys_by_select"):
-            t0 = plan.named["score_bits_first_write_op"] + 1
-            # zeroed: the dense forward (plan.ops) never writes them, and the list is written up to n_rows only -- they are
-            # published in plan.named and must not show what the allocation held (uninitialised memory)
-            need = torch.zeros(B * HW, device=self.device, dtype=torch.uint8)
-            rows = torch.zeros(B * HW, device=self.device, dtype=torch.int32)
-            n_rows = torch.zeros(1, device=self.device, dtype=torch.int32)
-            thresh = torch.zeros(B, device=self.device, dtype=torch.int32)
-            nb = L.m3d_need_rows_workspace_bytes(B, HW)
-            ws = torch.empty(nb, device=self.device, dtype=torch.uint8)
-            plan.keep += [need, rows, n_rows, thresh, ws]
-            plan.named.update(need=need, need_rows=rows, n_rows=n_rows, need_thresh=thresh)
-            k_pre = plan.named["sparse_k"] = [min(int(self.conf.nms_topN_pre), R)]      # set by the caller at launch time
-            tail = [("need_rows", "select", 0.0, lambda st: _hip.check(L.m3d_need_rows(
-                key.data_ptr(), B, A, HW, int(k_pre[0]), thresh.data_ptr(), need.data_ptr(), rows.data_ptr(), n_rows.data_ptr(),
-                ws.data_ptr(), nb, st)), OpCost(B * R * 4 * 4))]
-
-            def rows_op(op):
-                ref = ctypes.byref(op[4])
-                return op[:3] + (lambda st: _hip.check(L.m3d_head_mlp2_bf16_forward_rows(
-                    ref, rows.data_ptr(), n_rows.data_ptr(), st)), op[4])
-
-            def gated_op(op, p):
-                om, kx, ky, mi = align_args[p]
-                return op[:3] + (lambda st: _hip.check(L.m3d_align_offsets_gated(
-                    sel_idx.data_ptr(), sel_prob.data_ptr(), 0.5, box_ptr(kx), box_ptr(ky), P["anchor_wh"].data_ptr(),
-                    float(means[mi]), float(stds[mi]), float(means[mi + 1]), float(stds[mi + 1]), need.data_ptr(), om.ptr, om.cs,
-                    B, A, HW, 11 * A * HW, st)), op[4])
-
-            # feats_gl feeds bbox_z3d and nothing else, and that head runs at the listed pixels: so does the attention behind the
-            # dense Q | K | V | S projection and pooling
-            attend_rows = getattr(plan, "anab_attend", None) if ANAB_ROWS else None
-            for op in plan.ops[t0:-1]:
-                if op[1] == "bf16_head2" and not (with_center and op[0] == "bbox_x3d+bbox_y3d.mlp"):
-                    op = rows_op(op)
-                elif op[0] == "anab.attend" and attend_rows is not None:
-                    op = op[:3] + (attend_rows(L.m3d_anab_attend_bf16_rows, rows.data_ptr(), n_rows.data_ptr()), op[4])
-                elif op[0] == "center_align2d.offsets":
-                    op = gated_op(op, "center_align2d")
-                tail.append(op)
-            plan.tail, plan.tail_start = tail, t0
+        self._rpn_outputs(plan, r)
+        if SPARSE_TAIL:
+            self._rpn_tail(plan, r)
         return plan
 
     def sparse_heads_default(self, plan, k):
@@ -933,9 +768,9 @@ class EngineBF16(Engine):
                     q.ptr, q.cs, khat16.data_ptr(), vhat16.data_ptr(), B, HW, ck_pad, n_bins, keys_pad, cv, x.ptr, x.cs,
                     sc.data_ptr(), sh.data_ptr(), 1, out.ptr, out.cs, *row_list, st))
 
-            plan.anab_attend = attend       # (the detection-only tail builds its row-list form from it)
-            self._op(plan, "anab.attend", "bf16_anab", attend(L.m3d_anab_attend_bf16))
-            plan.ops[-1] = plan.ops[-1][:2] + (2.0 * B * HW * n_bins * (ck + cv),) + plan.ops[-1][3:]
+            self._op(plan, "anab.attend", "bf16_anab", attend(L.m3d_anab_attend_bf16), flops=2.0 * B * HW * n_bins * (ck + cv))
+            if ANAB_ROWS:
+                plan.sparse_form(lambda r: attend(L.m3d_anab_attend_bf16_rows, r.rows.data_ptr(), r.n_rows.data_ptr()))
             return
         logits = self._buf16(plan, B, fh, fw, n_bins, keys_pad, dtype=torch.float32)
         self._conv16(plan, "anab.logits", q, logits, wgt=khat16, kpad=ck_pad, cout=n_bins, cout_pad=keys_pad, out_mode=1,
