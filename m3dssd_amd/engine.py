@@ -6,7 +6,11 @@ Design (MI355X-first):
   * every conv / DCN is one ``m3d_conv2d_forward`` launch with BatchNorm(eval) + bias folded into a
     per-channel affine, residual add and LeakyReLU in the epilogue;
   * parameters are folded / packed once (``Engine.__init__``), buffers and launch descriptors are
-    built once per input shape (``_Plan``) and replayed; PyTorch only owns device memory + streams.
+    built once per input shape (``_Plan``) and replayed; PyTorch only owns device memory + streams;
+  * the backbone of a plan is one walk, ``Engine._dla_levels`` (the Trees of level2 .. level5, driven by ``BACKBONE_TREES``) and
+    ``Engine._dla_up`` (DLAUp / IDAUp), for DLA-34 and DLA-102 and for this engine and the bf16 one (``engine_bf16.EngineBF16``):
+    an engine supplies the primitives the walk calls -- ``_front`` (everything up to level1), ``_act``, ``_layer``, ``_offmask``,
+    ``_maxpool``, ``_upsample_add``, ``_tree_entry`` -- and its own RPN stage (``_rpn_ops``, on the shared ``_rpn_*`` steps).
 
 Reference graph being executed: model/M3d_inference_align.py:215-313 (RPN.forward),
 model/pose_dla_dcn.py:391-397,314-327,546-578,687-696 (DLA-34, Tree, IDAUp, DLAUp, DLASeg), :162-200,261-269,435-441
@@ -34,7 +38,9 @@ SPARSE_HEADS_MAX_FRACTION = 0.5
 PSP_SIZES = (1, 4, 8, 16)
 # channels of the stem, level0 .. level5 (pose_dla_dcn.py:419-440); channels[3] is the width of feats0 and every map after it
 BACKBONE_CHANNELS = {"dla34": (16, 32, 64, 128, 256, 512), "dla102": (16, 32, 128, 256, 512, 1024)}
-DLA102_LEVELS = (1, 1, 1, 3, 4, 1)
+# what the one walk of level2 .. level5 (Engine._dla_levels) and the one packer of their Trees need to know of a backbone: the depths
+# of the four Trees, the convs of a block (2: BasicBlock, 3: Bottleneck), and whether a Root adds children[0] to its output
+BACKBONE_TREES = {"dla34": ((1, 2, 2, 1), 2, False), "dla102": ((1, 3, 4, 1), 3, True)}
 # the box heads in the order of their rows in the planar box staging [B][11][A][HW]
 BOX_HEADS = ("bbox_x", "bbox_y", "bbox_w", "bbox_h", "bbox_x3d", "bbox_y3d", "bbox_z3d", "bbox_w3d", "bbox_h3d", "bbox_l3d", "bbox_rY3d")
 
@@ -316,43 +322,24 @@ class Engine:
         P["level1"] = self._pc(b + ".level1.0", b + ".level1.1")
         self._pack_front(sd, P)
 
-        def block(p):
-            P[p + ".conv1"] = self._pc(p + ".conv1", p + ".bn1")
-            P[p + ".conv2"] = self._pc(p + ".conv2", p + ".bn2")
+        depths, block_convs, _ = BACKBONE_TREES[self.back_bone]
 
-        def tree1(p):
-            block(p + ".tree1")
-            block(p + ".tree2")
+        def tree(p, levels):
+            """Any Tree: leaves carry the two blocks, the root and the project.  The project of a Tree of depth > 1 is computed by
+            the reference and then ignored (its tree1 computes its own): not packed."""
+            if levels > 1:
+                tree(p + ".tree1", levels - 1)
+                tree(p + ".tree2", levels - 1)
+                return
+            for blk in (p + ".tree1", p + ".tree2"):
+                for i in range(1, block_convs + 1):
+                    P["%s.conv%d" % (blk, i)] = self._pc("%s.conv%d" % (blk, i), "%s.bn%d" % (blk, i))
             P[p + ".root"] = self._pc(p + ".root.conv", p + ".root.bn")
             if (p + ".project.0.weight") in sd:
                 P[p + ".project"] = self._pc(p + ".project.0", p + ".project.1")
 
-        def bottleneck(p):
-            for i in (1, 2, 3):
-                P["%s.conv%d" % (p, i)] = self._pc("%s.conv%d" % (p, i), "%s.bn%d" % (p, i))
-
-        def tree(p, levels):
-            """Any Tree of Bottlenecks (DLA-102): leaves carry the blocks, the root and the project.  The project of a Tree of
-            depth > 1 is computed by the reference and then ignored (its tree1 computes its own): not packed."""
-            if levels == 1:
-                bottleneck(p + ".tree1")
-                bottleneck(p + ".tree2")
-                P[p + ".root"] = self._pc(p + ".root.conv", p + ".root.bn")
-                if (p + ".project.0.weight") in sd:
-                    P[p + ".project"] = self._pc(p + ".project.0", p + ".project.1")
-            else:
-                tree(p + ".tree1", levels - 1)
-                tree(p + ".tree2", levels - 1)
-
-        if self.back_bone == "dla102":
-            for lv in (2, 3, 4, 5):
-                tree("%s.level%d" % (b, lv), DLA102_LEVELS[lv])
-        else:
-            tree1(b + ".level2")
-            for lv in (3, 4):
-                tree1("%s.level%d.tree1" % (b, lv))
-                tree1("%s.level%d.tree2" % (b, lv))
-            tree1(b + ".level5")
+        for lv, levels in zip((2, 3, 4, 5), depths):
+            tree("%s.level%d" % (b, lv), levels)
 
         def deform(p):
             P[p + ".om"] = self._pc(p + ".conv.conv_offset_mask")
@@ -591,17 +578,33 @@ class Engine:
 
     # ------------------------------------------------------------------ plan construction
     def _build_plan(self, B, H, W):
-        L, P = self.L, self.P
+        """The plan of both engines: the backbone is one walk (_dla_levels, _dla_up) over the primitives an engine implements
+        (_front, _act, _layer, _offmask, _maxpool, _upsample_add, _tree_entry); the RPN stage is the engine's own (_rpn_ops)."""
         plan = _Plan()
-        chs = BACKBONE_CHANNELS[self.back_bone]
-        b = "base.base"
-        in_ptr = [0]                      # set by forward(): the caller's NCHW tensor is read in place
-        plan.named["input_ptr"] = in_ptr
-        s0 = self._buf(plan, B, H, W, 16)
-        in_u8 = [0, 0, 0]                 # (ptr, h, w) of uint8 BGR frames; set by forward_u8() instead of in_ptr
-        plan.named["input_u8"] = in_u8
+        l1 = self._front(plan, B, H, W)
+        feats0 = self._dla_up(plan, *self._dla_levels(plan, l1))
+        if not self.backbone_only:
+            self._rpn_ops(plan, feats0)
+        return plan
+
+    def _plan_input(self, plan):
+        """The plan's input slots and the constants of the uint8 path: (in_ptr, in_u8, mean3, stds3).  in_ptr = [pointer] is set
+        by forward() (the caller's NCHW tensor is read in place), in_u8 = [pointer, h, w] of uint8 BGR frames by forward_u8()."""
+        in_ptr, in_u8 = [0], [0, 0, 0]
+        plan.named["input_ptr"], plan.named["input_u8"] = in_ptr, in_u8
         mean3 = (ctypes.c_float * 3)(*[float(v) for v in self.conf.image_means])
         stds3 = (ctypes.c_float * 3)(*[float(v) for v in self.conf.image_stds])
+        return in_ptr, in_u8, mean3, stds3
+
+    # ---- what the backbone walk is made of in this engine: fp32 NHWC maps, one m3d_conv2d_forward-family launch per layer
+    _act = _buf                 # an activation map
+    _layer = _conv              # one conv layer from a packed conv
+
+    def _front(self, plan, B, H, W):
+        """Stem, level0 (in one of its three forms) and level1; returns level1."""
+        L, P = self.L, self.P
+        in_ptr, in_u8, mean3, stds3 = self._plan_input(plan)
+        s0 = self._buf(plan, B, H, W, 16)
 
         def stem(st):
             if in_u8[0]:                  # test-time input path fused into the stem's loads (SURVEY 8f row 4)
@@ -628,106 +631,148 @@ class Engine:
             self._conv(plan, "level0", P["level0"], s0, l0, 1, 1, act=1)
         l1 = self._buf(plan, B, H // 2, W // 2, 32, name="level1")
         self._conv(plan, "level1", P["level1"], l0, l1, 2, 1, act=1)
+        return l1
 
-        def maxpool(name, x, out):
-            self._op(plan, name, "maxpool", lambda st: _hip.check(L.m3d_maxpool2x2(
-                x.ptr, x.cs, out.ptr, out.cs, x.n, x.h, x.w, x.c, st)), nbytes=x.n * x.h * x.w * x.c * 5)
+    def _offmask(self, plan, p, x):
+        """The 27 offset / mask channels of DCN p over x (18 offsets, 9 sigmoid masks), from its own 3x3 conv."""
+        om = self._buf(plan, x.n, x.h, x.w, 27, 28)
+        self._conv(plan, p + ".offset_mask", self.P[p + ".om"], x, om, 1, 1, act=0, sigmoid_from=18)
+        return om
 
-        if self.back_bone == "dla102":
-            l3, l4, l5 = self._dla102_levels(plan, l1, maxpool)
-        else:
-            def block(p, x, res, out, stride):
-                co = P[p + ".conv1"].cout
-                t = self._buf(plan, B, out.h, out.w, co)
-                self._conv(plan, p + ".conv1", P[p + ".conv1"], x, t, stride, 1, act=1)
-                self._conv(plan, p + ".conv2", P[p + ".conv2"], t, out, 1, 1, act=1, res=res)
+    def _maxpool(self, plan, name, x, out):
+        self._op(plan, name, "maxpool", lambda st: _hip.check(self.L.m3d_maxpool2x2(
+            x.ptr, x.cs, out.ptr, out.cs, x.n, x.h, x.w, x.c, st)), nbytes=x.n * x.h * x.w * x.c * 5)
 
-            def tree1(p, x, co, stride, out, bottom=None):
-                """Tree(levels=1, level_root=False): pose_dla_dcn.py:314-323; root input = (x2, x1)."""
-                h, w = x.h // stride, x.w // stride
-                cat = self._buf(plan, B, h, w, 2 * co)
-                x2v, x1v = cat.slice(0, co), cat.slice(co, co)
+    def _upsample_add(self, plan, name, x, upw, skip, out):
+        """out = the depthwise 4x4 stride-2 transposed conv (weights upw) of x + skip."""
+        self._op(plan, name, "upsample", lambda st: _hip.check(self.L.m3d_upsample2x_add(
+            x.ptr, x.cs, upw.data_ptr(), skip.ptr, skip.cs, out.ptr, out.cs, x.n, x.h, x.w, x.c, st)),
+            flops=2.0 * x.n * 4 * x.h * x.w * x.c * 4, nbytes=x.n * x.h * x.w * x.c * 4 * (1 + 4 + 4))
+
+    def _tree_entry(self, plan, p, x, co, bottom, res):
+        """Max-pool (-> bottom, or nowhere if None) + project (-> res) + the stride-2 tree1.conv1 of leaf Tree p as one launch:
+        returns conv1's output map, or None where the engine has no such launch (this one has none)."""
+        return None
+
+    # ---- the backbone walk, shared by the fp32 and the bf16 plan and by DLA-34 and DLA-102
+    def _dla_levels(self, plan, l1):
+        """level2 .. level5 (pose_dla_dcn.py:162-200,261-327): four Trees of BasicBlocks (DLA-34: depths 1, 2, 2, 1) or Bottlenecks
+        (DLA-102: 1, 3, 4, 1, residual roots); returns (level3, level4, level5).  The walk follows Tree.forward for any depth: a
+        Tree of depth > 1 hands its `children` (the downsampled input when it is a level root, then the output of every tree1 on the
+        way down) to its tree2, and the leaf at the end of the tree2 chain concatenates (x2, x1, *children) for its root.  That
+        concatenation is one buffer, allocated by the outermost Tree of the chain; every child is written straight into its slice
+        of it, so DLA-34's level3 root reads [x2 | x1 | bottom | X1] and its level5 root [x2 | x1 | bottom]."""
+        P, B = self.P, l1.n
+        chs = BACKBONE_CHANNELS[self.back_bone]
+        depths, block_convs, root_residual = BACKBONE_TREES[self.back_bone]
+
+        def conv(name, x, out, stride, pad, act=1, res=None):        # (a layer's name in the plan is its key in P)
+            self._layer(plan, name, P[name], x, out, stride, pad, act=act, res=res)
+
+        def basic(p, x, res, out, stride):
+            """3x3 (stride) -> 3x3 + residual, each with BN + LeakyReLU."""
+            t = self._act(plan, B, out.h, out.w, P[p + ".conv1"].cout)
+            conv(p + ".conv1", x, t, stride, 1)
+            conv(p + ".conv2", t, out, 1, 1, res=res)
+
+        def bottleneck(p, x, res, out, stride):
+            """1x1 (at the input resolution) -> 3x3 (stride) -> 1x1 + residual, each with BN + LeakyReLU."""
+            cb = P[p + ".conv1"].cout
+            t1 = self._act(plan, B, x.h, x.w, cb)
+            conv(p + ".conv1", x, t1, 1, 0)
+            t2 = self._act(plan, B, out.h, out.w, cb)
+            conv(p + ".conv2", t1, t2, stride, 1)
+            conv(p + ".conv3", t2, out, 1, 0, res=res)
+
+        block = basic if block_convs == 2 else bottleneck
+
+        def tree(p, levels, x, co, stride, out, level_root=False, root_dim=0, cat=None, pos=None, bottom=None, pool=None):
+            """Tree.forward writing its result into `out`.  cat / pos: the root concatenation this Tree ends in and the list
+            holding its next free channel (None: this Tree starts a chain and allocates it).  pool / bottom: the name of the
+            max-pool of a stride-2 Tree and the slice it goes to when a root reads it, both decided by the outermost Tree of a
+            tree1 chain (every tree1 pools the same input as its parent); the leaf of the chain launches it."""
+            ci = x.c
+            root_dim = (root_dim or 2 * co) + (ci if level_root else 0)
+            h, w = x.h // stride, x.w // stride
+            if cat is None:
+                # width of the leaf root at the end of the tree2 chain: each level down adds one child of width co
+                cat = self._act(plan, B, h, w, root_dim + co * (levels - 1))
+                pos = [2 * co]
+            if stride > 1 and pool is None:
+                pool = p + ".downsample"
+                if level_root:                                       # children.append(bottom): pooled into its slice
+                    bottom = cat.slice(pos[0], ci)
+                    pos[0] += ci
+            if levels > 1:
+                # (the project of a Tree of depth > 1 is computed by the reference and then ignored: its tree1 computes its own)
+                x1 = cat.slice(pos[0], co)                            # children.append(x1) after tree1
+                pos[0] += co
+                tree(p + ".tree1", levels - 1, x, co, stride, x1, bottom=bottom, pool=pool)
+                tree(p + ".tree2", levels - 1, x1, co, 1, out, root_dim=root_dim + co, cat=cat, pos=pos)
+                return
+            assert cat.c == root_dim, (p, cat.c, root_dim)
+            x2v, x1v = cat.slice(0, co), cat.slice(co, co)
+            project = P.get(p + ".project")
+            res = self._act(plan, B, h, w, co) if project is not None else None
+            t = None
+            if stride > 1 and project is not None and block is basic:
+                t = self._tree_entry(plan, p, x, co, bottom, res)
+            if t is not None:
+                conv(p + ".tree1.conv2", t, x1v, 1, 1, res=res)
+            else:
                 if stride == 1:
                     bottom = x
-                elif bottom is None:
-                    bottom = self._buf(plan, B, h, w, x.c)
-                    maxpool(p + ".downsample", x, bottom)
-                if (p + ".project") in P:
-                    res = self._buf(plan, B, h, w, co)
-                    self._conv(plan, p + ".project", P[p + ".project"], bottom, res, 1, 0, act=0)
+                else:
+                    if bottom is None:
+                        bottom = self._act(plan, B, h, w, ci)
+                    self._maxpool(plan, pool, x, bottom)
+                if project is not None:
+                    conv(p + ".project", bottom, res, 1, 0, act=0)
                 else:
                     res = bottom
                 block(p + ".tree1", x, res, x1v, stride)
-                block(p + ".tree2", x1v, x1v, x2v, 1)
-                self._conv(plan, p + ".root", P[p + ".root"], cat, out, 1, 0, act=1)
+            block(p + ".tree2", x1v, x1v, x2v, 1)
+            # Root: LeakyReLU(BN(conv(cat)) [+ children[0] = x2])
+            conv(p + ".root", cat, out, 1, 0, res=x2v if root_residual else None)
 
-            # level2: Tree(1, 32 -> 64, stride 2)
-            l2 = self._buf(plan, B, H // 4, W // 4, 64, name="level2")
-            tree1(b + ".level2", l1, 64, 2, l2)
+        outs = [l1]
+        for lv, levels in zip((2, 3, 4, 5), depths):
+            x = outs[-1]
+            out = self._act(plan, B, x.h // 2, x.w // 2, chs[lv], name="level%d" % lv)
+            tree("base.base.level%d" % lv, levels, x, chs[lv], 2, out, level_root=lv > 2)
+            outs.append(out)
+        return outs[2:]
 
-            def tree2(p, x, co, out):
-                """Tree(levels=2, level_root=True): pose_dla_dcn.py:314-327."""
-                ci = x.c
-                h, w = x.h // 2, x.w // 2
-                # tree2's root input: (x2'', x1'', bottom, X1)
-                catb = self._buf(plan, B, h, w, 2 * co + ci + co)
-                bottom = catb.slice(2 * co, ci)
-                X1 = catb.slice(2 * co + ci, co)
-                maxpool(p + ".downsample", x, bottom)
-                tree1(p + ".tree1", x, co, 2, X1, bottom=bottom)
-                # tree2 = Tree(1, co -> co, stride 1) writing x2'', x1'' into catb[0:2co]
-                x2v, x1v = catb.slice(0, co), catb.slice(co, co)
-                block(p + ".tree2.tree1", X1, X1, x1v, 1)
-                block(p + ".tree2.tree2", x1v, x1v, x2v, 1)
-                self._conv(plan, p + ".tree2.root", P[p + ".tree2.root"], catb, out, 1, 0, act=1)
+    def _dla_up(self, plan, l3, l4, l5):
+        """DLAUp / IDAUp (pose_dla_dcn.py:546-578,687-696): every step is DCN -> up-sample + add -> DCN; returns feats0."""
+        P, B = self.P, l3.n
 
-            l3 = self._buf(plan, B, H // 8, W // 8, 128, name="level3")
-            tree2(b + ".level3", l2, 128, l3)
-            l4 = self._buf(plan, B, H // 16, W // 16, 256, name="level4")
-            tree2(b + ".level4", l3, 256, l4)
-            # level5: Tree(1, 256 -> 512, stride 2, level_root): root input (x2, x1, bottom)
-            l5 = self._buf(plan, B, H // 32, W // 32, 512, name="level5")
-            h5, w5 = H // 32, W // 32
-            cat5 = self._buf(plan, B, h5, w5, 1024 + 256)
-            bottom5 = cat5.slice(1024, 256)
-            maxpool(b + ".level5.downsample", l4, bottom5)
-            res5 = self._buf(plan, B, h5, w5, 512)
-            self._conv(plan, b + ".level5.project", P[b + ".level5.project"], bottom5, res5, 1, 0, act=0)
-            block(b + ".level5.tree1", l4, res5, cat5.slice(512, 512), 2)
-            block(b + ".level5.tree2", cat5.slice(512, 512), cat5.slice(512, 512), cat5.slice(0, 512), 1)
-            self._conv(plan, b + ".level5.root", P[b + ".level5.root"], cat5, l5, 1, 0, act=1)
-
-        # ---- DLAUp / IDAUp ------------------------------------------------------------
         def deform(p, x, out):
-            om = self._buf(plan, B, x.h, x.w, 27, 28)
-            self._conv(plan, p + ".offset_mask", P[p + ".om"], x, om, 1, 1, act=0, sigmoid_from=18)
-            self._conv(plan, p + ".dcn", P[p + ".dcn"], x, out, 1, 1, act=1, om=om)
+            om = self._offmask(plan, p, x)
+            self._layer(plan, p + ".dcn", P[p + ".dcn"], x, out, 1, 1, act=1, om=om)
             plan.named[p + ".out"] = out
 
         def ida_step(p, i, x, skip, co):
-            proj = self._buf(plan, B, x.h, x.w, co)
+            proj = self._act(plan, B, x.h, x.w, co)
             deform("%s.proj_%d" % (p, i), x, proj)
-            summed = self._buf(plan, B, 2 * x.h, 2 * x.w, co)
-            upw = P["%s.up_%d" % (p, i)]
-            self._op(plan, "%s.up_%d" % (p, i), "upsample", lambda st: _hip.check(L.m3d_upsample2x_add(
-                proj.ptr, proj.cs, upw.data_ptr(), skip.ptr, skip.cs, summed.ptr, summed.cs, B, proj.h, proj.w, co, st)),
-                flops=2.0 * B * 4 * proj.h * proj.w * co * 4, nbytes=B * proj.h * proj.w * co * 4 * (1 + 4 + 4))
-            node = self._buf(plan, B, 2 * x.h, 2 * x.w, co)
+            summed = self._act(plan, B, 2 * x.h, 2 * x.w, co)
+            self._upsample_add(plan, "%s.up_%d" % (p, i), proj, P["%s.up_%d" % (p, i)], skip, summed)
+            node = self._act(plan, B, 2 * x.h, 2 * x.w, co)
             deform("%s.node_%d" % (p, i), summed, node)
             return node
 
-        c3, c4 = chs[3], chs[4]                                        # DLA-34: 128 / 256, DLA-102: 256 / 512
+        c3, c4 = BACKBONE_CHANNELS[self.back_bone][3:5]                # DLA-34: 128 / 256, DLA-102: 256 / 512
         L5a = ida_step("base.dla_up.ida_0", 1, l5, l4, c4)             # c4 @ H/16
         L4b = ida_step("base.dla_up.ida_1", 1, l4, l3, c3)             # c3 @ H/8
         L5b = ida_step("base.dla_up.ida_1", 2, L5a, L4b, c3)           # c3 @ H/8
-        feats0 = ida_step("base.ida_up", 1, L5a, L5b, c3)              # c3 @ H/8
-        plan.named["feats0"] = feats0
-
+        feats0 = plan.named["feats0"] = ida_step("base.ida_up", 1, L5a, L5b, c3)     # c3 @ H/8
         plan.feat = (feats0.h, feats0.w)
-        if self.backbone_only:
-            return plan
+        return feats0
 
-        # ---- RPN heads ----------------------------------------------------------------
+    def _rpn_ops(self, plan, feats0):
+        """Everything behind feats0 (M3d_inference_align.py:241-313): heads, align stages, ANAB, outputs, the detection-only tail."""
+        L, P = self.L, self.P
+        B, c3 = feats0.n, feats0.c
         r = self._rpn_stage(plan, B, feats0.h, feats0.w)
         fh, fw, HW, A, NC = r.fh, r.fw, r.HW, r.A, r.NC
         with_shape, with_center, with_anab = self.flags
@@ -824,7 +869,6 @@ class Engine:
 
         self._rpn_outputs(plan, r)
         self._rpn_tail(plan, r)
-        return plan
 
     # ------------------------------------------------------------------ RPN-stage steps shared by the fp32 and the bf16 plan
     # (what they launch reads and writes fp32 / integer data in both: the planar staging, the selection, the align offsets)
@@ -939,78 +983,6 @@ class Engine:
             op, sparse = plan.ops[i], plan.sparse.get(i)
             tail.append(op if sparse is None else op[:3] + (sparse(r), op[4]))
         plan.tail, plan.tail_start = tail, t0
-
-    def _dla102_levels(self, plan, l1, maxpool):
-        """level2 .. level5 of DLA-102 (pose_dla_dcn.py:162-200,261-327): Trees of Bottlenecks of depth 1, 3, 4, 1 with residual
-        roots.  The walk follows Tree.forward for any depth: a Tree of depth > 1 hands its `children` (the downsampled input when it
-        is a level root, then the output of every tree1 on the way down) to its tree2, and the leaf at the end of the tree2 chain
-        concatenates (x2, x1, *children) for its root.  That concatenation is one buffer, allocated by the outermost Tree of the
-        chain; every child is written straight into its slice of it."""
-        P = self.P
-        B = l1.n
-        b = "base.base"
-        chs = BACKBONE_CHANNELS["dla102"]
-
-        def bottleneck(p, x, res, out, stride):
-            """1x1 (at the input resolution) -> 3x3 (stride) -> 1x1 + residual, each with BN + LeakyReLU."""
-            cb = P[p + ".conv1"].cout
-            t1 = self._buf(plan, B, x.h, x.w, cb)
-            self._conv(plan, p + ".conv1", P[p + ".conv1"], x, t1, 1, 0, act=1)
-            t2 = self._buf(plan, B, out.h, out.w, cb)
-            self._conv(plan, p + ".conv2", P[p + ".conv2"], t1, t2, stride, 1, act=1)
-            self._conv(plan, p + ".conv3", P[p + ".conv3"], t2, out, 1, 0, act=1, res=res)
-
-        def tree(p, levels, x, co, stride, out, level_root=False, root_dim=0, cat=None, pos=None, bottom=None):
-            """Tree.forward writing its result into `out`.  cat / pos: the root concatenation this Tree ends in and the list
-            holding its next free channel (None: this Tree starts a chain and allocates it); bottom: the downsampled input,
-            when an enclosing Tree has already computed it (tree1 pools the same input as its parent)."""
-            ci = x.c
-            if root_dim == 0:
-                root_dim = 2 * co
-            if level_root:
-                root_dim += ci
-            h, w = x.h // stride, x.w // stride
-            if cat is None:
-                # width of the leaf root at the end of the tree2 chain: each level down adds one child of width co
-                cat = self._buf(plan, B, h, w, root_dim + co * (levels - 1))
-                pos = [2 * co]
-            if stride == 1:
-                bottom = x
-            elif bottom is None:
-                if level_root:                                       # children.append(bottom): pooled into its slice
-                    bottom = cat.slice(pos[0], ci)
-                    pos[0] += ci
-                else:
-                    bottom = self._buf(plan, B, h, w, ci)
-                maxpool(p + ".downsample", x, bottom)
-            if levels == 1:
-                if (p + ".project") in P:
-                    res = self._buf(plan, B, h, w, co)
-                    self._conv(plan, p + ".project", P[p + ".project"], bottom, res, 1, 0, act=0)
-                else:
-                    res = bottom
-                assert cat.c == root_dim, (p, cat.c, root_dim)
-                x2v, x1v = cat.slice(0, co), cat.slice(co, co)
-                bottleneck(p + ".tree1", x, res, x1v, stride)
-                bottleneck(p + ".tree2", x1v, x1v, x2v, 1)
-                # Root with residual: BN(conv(cat)) + children[0] (= x2), LeakyReLU
-                self._conv(plan, p + ".root", P[p + ".root"], cat, out, 1, 0, act=1, res=x2v)
-                return
-            # (the project of a Tree of depth > 1 is computed by the reference and then ignored: its tree1 computes its own)
-            x1 = cat.slice(pos[0], co)                                # children.append(x1) after tree1
-            pos[0] += co
-            tree(p + ".tree1", levels - 1, x, co, stride, x1, bottom=bottom if stride > 1 else None)
-            tree(p + ".tree2", levels - 1, x1, co, 1, out, root_dim=root_dim + co, cat=cat, pos=pos)
-
-        outs = []
-        x = l1
-        for lv in (2, 3, 4, 5):
-            h, w = x.h // 2, x.w // 2
-            out = self._buf(plan, B, h, w, chs[lv], name="level%d" % lv)
-            tree("%s.level%d" % (b, lv), DLA102_LEVELS[lv], x, chs[lv], 2, out, level_root=lv > 2)
-            outs.append(out)
-            x = out
-        return outs[1], outs[2], outs[3]
 
     def _anab_ops(self, plan, x, out, scale, shift, act, res_mode):
         """Append the ANAB launches: fused QKVS 1x1 conv -> weighted pyramid pooling -> logits GEMM (per-image

@@ -1,6 +1,9 @@
 """bf16 inference engine (BASELINE.json configs[2]: bs = 64, bf16 storage, MFMA v_mfma_f32_32x32x16_bf16).
 
-Same graph and the same plan / launch machinery as ``engine.Engine`` (model/M3d_inference_align.py:215-313), with
+Same graph and the same plan / launch machinery as ``engine.Engine`` (model/M3d_inference_align.py:215-313).  The backbone of the
+plan is ``Engine``'s walk (``Engine._dla_levels``, ``_dla_up``); this file holds what the walk is made of here -- the front end,
+bf16 maps, ``_pconv`` layers, fp32 offset / mask maps, the bf16 max-pool and up-sampling, the fused tree entry -- and the bf16 RPN
+stage (``_rpn_ops``).  The differences to the fp32 engine:
 
   * activations and weights stored as bf16 in HBM, fp32 accumulation, fp32 folded-BatchNorm / bias / residual / activation
     epilogues inside the producing kernel (``m3d_conv_bf16_forward``) -- every activation crosses HBM once, as bf16;
@@ -21,7 +24,7 @@ import torch
 
 from . import _hip
 from ._hip import ConvBf16Desc, Head2Bf16Desc, HeadBf16Desc, QkvsBf16Desc, Tail2Bf16Desc, TreeEntryBf16Desc
-from .engine import PSP_SIZES, Engine, OpCost, _Plan, _rup, fold_affine
+from .engine import PSP_SIZES, Engine, OpCost, _rup, fold_affine
 
 BF16 = torch.bfloat16
 FUSED_ANAB = os.environ.get("M3D_BF16_FUSED_ANAB", "1") != "0"
@@ -325,16 +328,14 @@ class EngineBF16(Engine):
                                                and sigmoid_from < 0 and x.c == pc.cin) else None)
 
     # ------------------------------------------------------------------ plan construction
-    def _build_plan(self, B, H, W):
+    # (Engine._build_plan: the shared backbone walk over the primitives below, then _rpn_ops)
+    _act = _buf16               # an activation map: bf16 NHWC
+    _layer = _pconv             # one conv layer from a packed conv
+
+    def _front(self, plan, B, H, W):
+        """Stem, level0 and level1 -- one launch, or three with FUSED_FRONT = False; returns level1."""
         L, P = self.L, self.P
-        plan = _Plan()
-        b = "base.base"
-        in_ptr = [0]
-        plan.named["input_ptr"] = in_ptr
-        in_u8 = [0, 0, 0]
-        plan.named["input_u8"] = in_u8
-        mean3 = (ctypes.c_float * 3)(*[float(v) for v in self.conf.image_means])
-        stds3 = (ctypes.c_float * 3)(*[float(v) for v in self.conf.image_stds])
+        in_ptr, in_u8, mean3, stds3 = self._plan_input(plan)
         l1 = self._buf16(plan, B, H // 2, W // 2, 32, name="level1")
         if FUSED_FRONT:
             # stem -> level0 -> level1 in one launch: the 16-channel full-resolution maps never reach HBM
@@ -349,148 +350,69 @@ class EngineBF16(Engine):
             # (bytes: the fp32 NCHW image in, the 32-channel half-resolution bf16 map out)
             plan.ops.append(("stem+level0+level1", "bf16_frontend2", flops, front,
                              OpCost(B * H * W * 3 * 4 + B * (H // 2) * (W // 2) * 32 * 2)))
-        else:
-            s0 = self._buf16(plan, B, H, W, 16)
+            return l1
+        s0 = self._buf16(plan, B, H, W, 16)
 
-            def stem(st):
-                u8 = 1 if in_u8[0] else 0
-                _hip.check(L.m3d_stem_conv7x7_bf16(in_u8[0] if u8 else in_ptr[0], u8, in_u8[1], in_u8[2], mean3, stds3,
-                                                   P["stem.w"].data_ptr(), P["stem.scale"].data_ptr(), P["stem.shift"].data_ptr(),
-                                                   s0.ptr, s0.cs, B, H, W, st))
-            self._op(plan, "stem", "stem_bf16", stem, flops=2.0 * B * H * W * 16 * 147, nbytes=B * H * W * (3 * 4 + 16 * 2))
-            l0 = self._buf16(plan, B, H, W, 16, name="level0")
-            self._pconv(plan, "level0", P["level0"], s0, l0, 1, 1, act=1)
-            self._pconv(plan, "level1", P["level1"], l0, l1, 2, 1, act=1)
+        def stem(st):
+            u8 = 1 if in_u8[0] else 0
+            _hip.check(L.m3d_stem_conv7x7_bf16(in_u8[0] if u8 else in_ptr[0], u8, in_u8[1], in_u8[2], mean3, stds3,
+                                               P["stem.w"].data_ptr(), P["stem.scale"].data_ptr(), P["stem.shift"].data_ptr(),
+                                               s0.ptr, s0.cs, B, H, W, st))
+        self._op(plan, "stem", "stem_bf16", stem, flops=2.0 * B * H * W * 16 * 147, nbytes=B * H * W * (3 * 4 + 16 * 2))
+        l0 = self._buf16(plan, B, H, W, 16, name="level0")
+        self._pconv(plan, "level0", P["level0"], s0, l0, 1, 1, act=1)
+        self._pconv(plan, "level1", P["level1"], l0, l1, 2, 1, act=1)
+        return l1
 
-        def maxpool(name, x, out):
-            self._op(plan, name, "maxpool_bf16", lambda st: _hip.check(L.m3d_maxpool2x2_bf16(
-                x.ptr, x.cs, out.ptr, out.cs, x.n, x.h, x.w, x.c, st)), nbytes=x.n * x.h * x.w * x.c * 5 // 2)
+    def _offmask(self, plan, p, x):
+        """The offsets / masks of DCN p stay fp32 (they address memory): 27 channels in rows of 32, published as p + ".om"."""
+        om = self._buf16(plan, x.n, x.h, x.w, 27, 32, name=p + ".om", dtype=torch.float32)
+        self._pconv(plan, p + ".offset_mask", self.P[p + ".om"], x, om, 1, 1, act=0, sigmoid_from=18, out_mode=1)
+        return om
 
-        def block(p, x, res, out, stride):
-            co = P[p + ".conv1"].cout
-            t = self._buf16(plan, B, out.h, out.w, co)
-            self._pconv(plan, p + ".conv1", P[p + ".conv1"], x, t, stride, 1, act=1)
-            self._pconv(plan, p + ".conv2", P[p + ".conv2"], t, out, 1, 1, act=1, res=res)
+    def _maxpool(self, plan, name, x, out):
+        self._op(plan, name, "maxpool_bf16", lambda st: _hip.check(self.L.m3d_maxpool2x2_bf16(
+            x.ptr, x.cs, out.ptr, out.cs, x.n, x.h, x.w, x.c, st)), nbytes=x.n * x.h * x.w * x.c * 5 // 2)
 
-        def tree_entry(p, x, co, bottom, res, t):
-            """maxpool (-> bottom view or None) + project (-> res) + tree1.conv1 (stride 2, -> t) as ONE launch; False = not applicable."""
-            if not (TREE_ENTRY and (p + ".project") in P and x.c % 32 == 0 and co % 64 == 0):
-                return False
-            key = "tree_entry:" + p
-            if key not in P:
-                sd = self.sd
-                P[key] = pack_tree_entry(sd[p + ".tree1.conv1.weight"], P[p + ".tree1.conv1"].scale, sd[p + ".project.0.weight"],
-                                         P[p + ".project"].scale, self.device)
-            d = TreeEntryBf16Desc()
-            d.inp, d.in_cs, d.N, d.H, d.W, d.Cin, d.Cout = x.ptr, x.cs, x.n, x.h, x.w, x.c, co
-            d.wfrag, d.shift1, d.shiftp = P[key].data_ptr(), P[p + ".tree1.conv1"].shift.data_ptr(), P[p + ".project"].shift.data_ptr()
-            d.t, d.t_cs, d.res, d.res_cs = t.ptr, t.cs, res.ptr, res.cs
-            if bottom is not None:
-                d.bottom, d.bottom_cs = bottom.ptr, bottom.cs
-            ref = ctypes.byref(d)
-            if not L.m3d_tree_entry_bf16_applicable(ref):
-                return False
-            plan.keep += [P[key], P[p + ".tree1.conv1"].shift, P[p + ".project"].shift]
-            ho, wo = x.h // 2, x.w // 2
-            flops = 2.0 * x.n * ho * wo * co * x.c * 10
-            nbytes = x.n * (x.h * x.w * x.c + ho * wo * (2 * co + (x.c if bottom is not None else 0))) * 2 + co * x.c * 10 * 2
-            plan.ops.append((p + ".entry", "bf16_tree_entry", flops,
-                             lambda st: _hip.check(L.m3d_tree_entry_bf16_forward(ref, st)), OpCost(nbytes)))
-            return True
+    def _upsample_add(self, plan, name, x, upw, skip, out):
+        self._op(plan, name, "upsample_bf16", lambda st: _hip.check(self.L.m3d_upsample2x_add_bf16(
+            x.ptr, x.cs, upw.data_ptr(), skip.ptr, skip.cs, out.ptr, out.cs, x.n, x.h, x.w, x.c, st)),
+            flops=2.0 * x.n * 4 * x.h * x.w * x.c * 4, nbytes=x.n * x.h * x.w * x.c * 2 * (1 + 4 + 4))
 
-        def tree1(p, x, co, stride, out, bottom=None):
-            h, w = x.h // stride, x.w // stride
-            cat = self._buf16(plan, B, h, w, 2 * co)
-            x2v, x1v = cat.slice(0, co), cat.slice(co, co)
-            if stride == 2 and (p + ".project") in P:
-                # fused entry: bottom (only materialised when a root reads it: `bottom` given by the caller), project, conv1
-                res = self._buf16(plan, B, h, w, co)
-                t = self._buf16(plan, B, h, w, co)
-                if tree_entry(p, x, co, bottom, res, t):
-                    self._pconv(plan, p + ".tree1.conv2", P[p + ".tree1.conv2"], t, x1v, 1, 1, act=1, res=res)
-                    block(p + ".tree2", x1v, x1v, x2v, 1)
-                    self._pconv(plan, p + ".root", P[p + ".root"], cat, out, 1, 0, act=1)
-                    return
-                if bottom is not None:
-                    maxpool(p + ".downsample", x, bottom)
-            if stride == 1:
-                bottom = x
-            elif bottom is None:
-                bottom = self._buf16(plan, B, h, w, x.c)
-                maxpool(p + ".downsample", x, bottom)
-            if (p + ".project") in P:
-                res = self._buf16(plan, B, h, w, co)
-                self._pconv(plan, p + ".project", P[p + ".project"], bottom, res, 1, 0, act=0)
-            else:
-                res = bottom
-            block(p + ".tree1", x, res, x1v, stride)
-            block(p + ".tree2", x1v, x1v, x2v, 1)
-            self._pconv(plan, p + ".root", P[p + ".root"], cat, out, 1, 0, act=1)
+    def _tree_entry(self, plan, p, x, co, bottom, res):
+        """Max-pool (-> the `bottom` view; None: no root reads it, not materialised) + project (-> res) + tree1.conv1 (stride 2) of
+        leaf Tree p as ONE launch; returns conv1's output map, or None where the launch does not apply."""
+        L, P = self.L, self.P
+        if not (TREE_ENTRY and x.c % 32 == 0 and co % 64 == 0):
+            return None
+        key = "tree_entry:" + p
+        if key not in P:
+            sd = self.sd
+            P[key] = pack_tree_entry(sd[p + ".tree1.conv1.weight"], P[p + ".tree1.conv1"].scale, sd[p + ".project.0.weight"],
+                                     P[p + ".project"].scale, self.device)
+        t = self._buf16(plan, x.n, x.h // 2, x.w // 2, co)
+        d = TreeEntryBf16Desc()
+        d.inp, d.in_cs, d.N, d.H, d.W, d.Cin, d.Cout = x.ptr, x.cs, x.n, x.h, x.w, x.c, co
+        d.wfrag, d.shift1, d.shiftp = P[key].data_ptr(), P[p + ".tree1.conv1"].shift.data_ptr(), P[p + ".project"].shift.data_ptr()
+        d.t, d.t_cs, d.res, d.res_cs = t.ptr, t.cs, res.ptr, res.cs
+        if bottom is not None:
+            d.bottom, d.bottom_cs = bottom.ptr, bottom.cs
+        ref = ctypes.byref(d)
+        if not L.m3d_tree_entry_bf16_applicable(ref):
+            return None
+        plan.keep += [P[key], P[p + ".tree1.conv1"].shift, P[p + ".project"].shift]
+        ho, wo = x.h // 2, x.w // 2
+        flops = 2.0 * x.n * ho * wo * co * x.c * 10
+        nbytes = x.n * (x.h * x.w * x.c + ho * wo * (2 * co + (x.c if bottom is not None else 0))) * 2 + co * x.c * 10 * 2
+        plan.ops.append((p + ".entry", "bf16_tree_entry", flops,
+                         lambda st: _hip.check(L.m3d_tree_entry_bf16_forward(ref, st)), OpCost(nbytes)))
+        return t
 
-        l2 = self._buf16(plan, B, H // 4, W // 4, 64, name="level2")
-        tree1(b + ".level2", l1, 64, 2, l2)
-
-        def tree2(p, x, co, out):
-            ci = x.c
-            h, w = x.h // 2, x.w // 2
-            catb = self._buf16(plan, B, h, w, 2 * co + ci + co)
-            bottom = catb.slice(2 * co, ci)
-            X1 = catb.slice(2 * co + ci, co)
-            tree1(p + ".tree1", x, co, 2, X1, bottom=bottom)      # (writes `bottom` itself: fused entry or its own max-pool launch)
-            x2v, x1v = catb.slice(0, co), catb.slice(co, co)
-            block(p + ".tree2.tree1", X1, X1, x1v, 1)
-            block(p + ".tree2.tree2", x1v, x1v, x2v, 1)
-            self._pconv(plan, p + ".tree2.root", P[p + ".tree2.root"], catb, out, 1, 0, act=1)
-
-        l3 = self._buf16(plan, B, H // 8, W // 8, 128, name="level3")
-        tree2(b + ".level3", l2, 128, l3)
-        l4 = self._buf16(plan, B, H // 16, W // 16, 256, name="level4")
-        tree2(b + ".level4", l3, 256, l4)
-        l5 = self._buf16(plan, B, H // 32, W // 32, 512, name="level5")
-        h5, w5 = H // 32, W // 32
-        cat5 = self._buf16(plan, B, h5, w5, 1024 + 256)
-        bottom5 = cat5.slice(1024, 256)
-        res5 = self._buf16(plan, B, h5, w5, 512)
-        t5 = self._buf16(plan, B, h5, w5, 512)
-        if tree_entry(b + ".level5", l4, 512, bottom5, res5, t5):
-            self._pconv(plan, b + ".level5.tree1.conv2", P[b + ".level5.tree1.conv2"], t5, cat5.slice(512, 512), 1, 1, act=1, res=res5)
-        else:
-            maxpool(b + ".level5.downsample", l4, bottom5)
-            self._pconv(plan, b + ".level5.project", P[b + ".level5.project"], bottom5, res5, 1, 0, act=0)
-            block(b + ".level5.tree1", l4, res5, cat5.slice(512, 512), 2)
-        block(b + ".level5.tree2", cat5.slice(512, 512), cat5.slice(512, 512), cat5.slice(0, 512), 1)
-        self._pconv(plan, b + ".level5.root", P[b + ".level5.root"], cat5, l5, 1, 0, act=1)
-
-        # ---- DLAUp / IDAUp: offsets / masks stay fp32 (they address memory) ---------------------------
-        def deform(p, x, out):
-            om = self._buf16(plan, B, x.h, x.w, 27, 32, name=p + ".om", dtype=torch.float32)
-            self._pconv(plan, p + ".offset_mask", P[p + ".om"], x, om, 1, 1, act=0, sigmoid_from=18, out_mode=1)
-            self._pconv(plan, p + ".dcn", P[p + ".dcn"], x, out, 1, 1, act=1, om=om)
-            plan.named[p + ".out"] = out
-
-        def ida_step(p, i, x, skip, co):
-            proj = self._buf16(plan, B, x.h, x.w, co)
-            deform("%s.proj_%d" % (p, i), x, proj)
-            summed = self._buf16(plan, B, 2 * x.h, 2 * x.w, co)
-            upw = P["%s.up_%d" % (p, i)]
-            self._op(plan, "%s.up_%d" % (p, i), "upsample_bf16", lambda st: _hip.check(L.m3d_upsample2x_add_bf16(
-                proj.ptr, proj.cs, upw.data_ptr(), skip.ptr, skip.cs, summed.ptr, summed.cs, B, proj.h, proj.w, co, st)),
-                flops=2.0 * B * 4 * proj.h * proj.w * co * 4, nbytes=B * proj.h * proj.w * co * 2 * (1 + 4 + 4))
-            node = self._buf16(plan, B, 2 * x.h, 2 * x.w, co)
-            deform("%s.node_%d" % (p, i), summed, node)
-            return node
-
-        L5a = ida_step("base.dla_up.ida_0", 1, l5, l4, 256)
-        L4b = ida_step("base.dla_up.ida_1", 1, l4, l3, 128)
-        L5b = ida_step("base.dla_up.ida_1", 2, L5a, L4b, 128)
-        feats0 = ida_step("base.ida_up", 1, L5a, L5b, 128)
-        plan.named["feats0"] = feats0
-        plan.feat = (feats0.h, feats0.w)
-        if self.backbone_only:
-            return plan
-
-        # ---- RPN heads ----------------------------------------------------------------
-        # (the steps shared with the fp32 plan -- staging, selection, align offsets, outputs, tail -- are Engine._rpn_*)
+    def _rpn_ops(self, plan, feats0):
+        """Everything behind feats0; the steps shared with the fp32 plan -- staging, selection, align offsets, outputs, tail -- are
+        Engine._rpn_*."""
+        L, P = self.L, self.P
+        B = feats0.n
         r = self._rpn_stage(plan, B, feats0.h, feats0.w)
         fh, fw, HW, A, NC = r.fh, r.fw, r.HW, r.A, r.NC
         cls_pl, box_pl = r.cls_pl, r.box_pl
@@ -657,7 +579,6 @@ class EngineBF16(Engine):
         self._rpn_outputs(plan, r)
         if SPARSE_TAIL:
             self._rpn_tail(plan, r)
-        return plan
 
     def sparse_heads_default(self, plan, k):
         """The plan-time rule of a detector's sparse_heads=None on a bf16 module: the fp32 rule (min(k, HW) at most

@@ -16,6 +16,13 @@ for _dt in ("f32", "bf16"):
 # a 12x28 feature map: no multiple of 128 pixels, so the unfused attention and a tail with no row-list attention
 CASES["f32-anab_fullalign-b2-96x224"] = ("f32", "anab_fullalign", "dla34", 2, (96, 224))
 CASES["f32-dla102-anab_fullalign-b1-128x320"] = ("f32", "anab_fullalign", "dla102", 1, (128, 320))
+# id -> m3dssd_amd.engine_bf16 module attributes set while the case's engine and plan are built: the bf16 backbone paths that the
+# defaults do not reach (the un-fused tree entries; stem, level0 and level1 as three launches)
+KNOBS = {}
+for _knob in ("TREE_ENTRY", "FUSED_FRONT"):
+    _id = "bf16-anab_fullalign-b2-128x320-%s=False" % _knob
+    CASES[_id] = CASES["bf16-anab_fullalign-b2-128x320"]
+    KNOBS[_id] = {_knob: False}
 
 
 def build_engine(dtype, config, back_bone, B, crop):
@@ -53,9 +60,18 @@ def _cost(c):
 
 
 def dump_case(case_id):
+    from m3dssd_amd import engine_bf16
     dtype, config, back_bone, B, crop = CASES[case_id]
-    eng = build_engine(dtype, config, back_bone, B, crop)
-    plan = eng.plan_for(B, *crop)
+    knobs = KNOBS.get(case_id, {})
+    saved = {k: getattr(engine_bf16, k) for k in knobs}
+    try:
+        for k, v in knobs.items():
+            setattr(engine_bf16, k, v)
+        eng = build_engine(dtype, config, back_bone, B, crop)
+        plan = eng.plan_for(B, *crop)
+    finally:
+        for k, v in saved.items():
+            setattr(engine_bf16, k, v)
     tail = plan.tail
     dense = plan.ops[plan.tail_start:-1] if tail is not None else []
     return {

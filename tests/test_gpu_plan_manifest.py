@@ -1,8 +1,9 @@
 """GPU test (-m gpu; it launches only the parameter packing): the launch plans and the packed parameters of both engines are what
 tests/golden/plan_manifest.json.gz (gzip-compressed JSON) records -- op names, kinds, order, exact flops, cost slots, side branches, the detection-only
 tail and which of its entries are the dense ops themselves, the keys of plan.named and the layout of eng.P.  The record was made by
-tools/gen_golden_plan_manifest.py before the RPN stage of the two plan builders was put on shared steps; there is no tolerance and
-no skipped field."""
+tools/gen_golden_plan_manifest.py before the RPN stage of the two plan builders was put on shared steps; the two cases with an
+``engine_bf16`` knob off (plan_manifest.KNOBS) were added to it before the backbone was put on one DLA walk, with the one rename the
+tool's docstring states.  There is no tolerance and no skipped field."""
 import gzip
 import json
 import os
