@@ -22,7 +22,7 @@ import torch
 from .. import _hip
 
 MODE_NONE, MODE_CONTRAST_FIRST, MODE_CONTRAST_LAST = 0, 1, 2
-PARAM_COLS = 14        # M3D_AUGMENT_PARAMS: h w mode delta alpha sat hue - Minv[6]
+PARAM_COLS = _hip.CONSTANTS["M3D_AUGMENT_PARAMS"]        # 14: h w mode delta alpha sat hue - Minv[6]
 # PhotometricDistort's ranges (augmentations.py:243,266,308,380)
 BRIGHTNESS_DELTA, CONTRAST_RANGE, SATURATION_RANGE, HUE_DELTA = 32, (0.5, 1.5), (0.5, 1.5), 18.0
 

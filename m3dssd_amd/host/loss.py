@@ -30,13 +30,13 @@ import torch.nn as nn
 from .. import _hip
 from . import ops
 
-MAX_GT = 128          # M3D_RPN_MAX_GT
-GT_COLS = 12          # M3D_RPN_GT_COLS
-CONF_COUNT = 35       # M3D_RPN_CONF_COUNT
-STAT_NAMES = ("loss", "cls", "bbox_2d", "bbox_3d", "iou_loss", "z", "ry", "iou_acc", "acc_fg", "acc_bg", "n_fg", "n_bg", "fg_num",
-              "bg_num", "n_active", "fg_weight")          # M3D_RPN_STAT_*
-SMP_STAT_BAD_LABELS = 16          # M3D_RPN_SMP_STAT_BAD_LABELS: the stat block of m3d_rpn_loss_smp has one more slot
-SMP_STAT_COUNT = 17               # M3D_RPN_SMP_STAT_COUNT
+_C = _hip.CONSTANTS          # the header's #defines and enumerators
+MAX_GT, GT_COLS, CONF_COUNT = _C["M3D_RPN_MAX_GT"], _C["M3D_RPN_GT_COLS"], _C["M3D_RPN_CONF_COUNT"]
+# "loss", "cls", "bbox_2d", ...: the slots of the stat block, M3D_RPN_STAT_* in value order
+STAT_NAMES = tuple(n[len("M3D_RPN_STAT_"):].lower() for n in sorted(_C, key=_C.get)
+                   if n.startswith("M3D_RPN_STAT_") and n != "M3D_RPN_STAT_COUNT")
+SMP_STAT_BAD_LABELS = _C["M3D_RPN_SMP_STAT_BAD_LABELS"]          # the stat block of m3d_rpn_loss_smp has one more slot
+SMP_STAT_COUNT = _C["M3D_RPN_SMP_STAT_COUNT"]
 IGN_FLAG = 3000
 
 
@@ -356,7 +356,7 @@ def rpn_precompute_targets(anchors, conf_vec, gt_table, feat_size, device):
     return dict(labels=labels, gt_index=gt_index, bbox_2d=b2t, bbox_3d=b3t, meta=dict(any_val=any_val))
 
 
-TARGET_STATS_COLS = 23          # M3D_RPN_TARGET_STATS_COLS: n_fg, 11 sums, 11 sums of squares
+TARGET_STATS_COLS = _C["M3D_RPN_TARGET_STATS_COLS"]          # n_fg, 11 sums, 11 sums of squares
 
 
 def rpn_target_stats(anchors, conf_vec, gt_table, feat_size, center=None, device="cuda:0"):

@@ -1,6 +1,7 @@
 """CPU checks of the drop-in boundary: the C-ABI library loads and exports every symbol that
 include/m3dssd_hip.h declares (no compute calls -- there is no GPU here), the ctypes signature table
 covers exactly the header, and the import-path shims expose the reference's names."""
+import ctypes
 import os
 import re
 
@@ -27,8 +28,56 @@ def test_library_exports_every_declared_symbol():
     assert L.m3d_abi_version() == 5
 
 
+def test_lib_types_every_declared_symbol():
+    """lib() has set restype / argtypes, from the table, on every function the header declares."""
+    L = _hip.lib()
+    names = _declared()
+    assert len(names) == len(_hip.SIGNATURES) >= 126
+    for n in names:
+        fn, (res, args) = getattr(L, n), _hip.SIGNATURES[n]
+        assert fn.argtypes is not None and list(fn.argtypes) == args, n
+        assert fn.restype is res, n
+        assert res in (None, ctypes.c_int, ctypes.c_longlong, ctypes.c_char_p), (n, res)
+    assert L._nms.restype is None and L.m3d_last_error.restype is ctypes.c_char_p and L.m3d_last_error.argtypes == []
+
+
+def test_abi_version_mismatch_is_refused(monkeypatch):
+    """A library built from a header of another M3D_ABI_VERSION is refused at load, with both numbers and the build command."""
+    monkeypatch.setattr(_hip, "_lib", None)
+    monkeypatch.setitem(_hip.CONSTANTS, "M3D_ABI_VERSION", 6)
+    with pytest.raises(RuntimeError, match=r"(?s)version 5\b.*declares 6\b.*build\(\)"):
+        _hip.lib()
+    assert _hip._lib is None
+
+
+def _header_structs():
+    """{struct: [(field, "ptr" or its scalar type words)]} read off the header text, independently of the binding's reader."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(_hip.HEADER).read(), flags=re.S)
+    out = {}
+    for m in re.finditer(r"typedef struct (\w+) \{(.*?)\} \1;", hdr, flags=re.S):
+        fields = out[m.group(1)] = []
+        for decl in m.group(2).split(";")[:-1]:
+            first, *more = decl.split(",")
+            words = first.replace("*", " * ").split()
+            base = " ".join(w for w in words[:-1] if w not in ("const", "*"))
+            fields.append((words[-1], "ptr" if "*" in words else base))
+            fields += [(d.strip().lstrip("* "), "ptr" if d.strip().startswith("*") else base) for d in more]
+    return out
+
+
 def test_conv_desc_layout_matches_header():
-    """Field order/count of the ctypes mirror follows the C struct (names differ only for `in`)."""
+    """Field order/count of the ctypes structures follows the C structs (names differ only for `in`), and every field has the
+    class of its declaration: a pointer, or the scalar of that width."""
+    scalar = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float}
+    structs = _header_structs()
+    assert sorted(structs) == sorted(_hip.STRUCTS) and len(structs) == 8
+    for name, fields in structs.items():
+        cls = _hip.STRUCTS[name]
+        assert cls is getattr(_hip, "".join(w.capitalize() for w in name.split("_")[1:]))
+        assert [("in" if n == "inp" else n) for n, _ in cls._fields_] == [n for n, _ in fields], name
+        for (n, kind), (_, ctype) in zip(fields, cls._fields_):
+            assert ctype is (ctypes.c_void_p if kind == "ptr" else scalar[kind]), (name, n, kind, ctype)
+    assert _hip.STRUCTS["m3d_conv_desc"] is _hip.ConvDesc and _hip.STRUCTS["m3d_head2_bf16_desc"] is _hip.Head2Bf16Desc
     hdr = open(_hip.HEADER).read()
     body = hdr[hdr.index("typedef struct m3d_conv_desc {"):hdr.index("} m3d_conv_desc;")]
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
