@@ -18,6 +18,7 @@ model/pose_dla_dcn.py:391-397,314-327,546-578,687-696 (DLA-34, Tree, IDAUp, DLAU
 model/DCNv2/dcn_v2.py:64-70 (DCN), model/module/feturealign_mgpu.py:48-99,153-208,
 model/module/attention.py:183-216.
 """
+import collections
 import ctypes
 import math
 import os
@@ -263,6 +264,54 @@ class _RpnStage:
         return self.box_pl.data_ptr() + 4 * k * self.A * self.HW          # image 0; per-image stride handled via [B][11][A][HW]
 
 
+def conv_desc(name, pc, x, out, stride, pad, act=0, res=None, res_mode=0, sigmoid_from=-1, om=None, affine=True, wgt_ptr=None,
+              wgt_img_stride=0, cout=None, cout_pad=None, scale=None, shift=None, kh=None, kw=None):
+    """The m3d_conv_desc of one layer: weights and sizes from the packed conv `pc`, or, with pc = None, from wgt_ptr (+
+    wgt_img_stride) / cout / cout_pad / kh / kw; input x, NHWC output view `out`; epilogue = scale / shift (given, or pc's folded
+    affine unless affine = False), residual, act / sigmoid_from; om = the offset / mask map of a deformable layer."""
+    assert (pc is None) != (wgt_ptr is None), name
+    d = ConvDesc()
+    d.inp, d.in_cs, d.N, d.H, d.W, d.Cin = x.ptr, x.cs, x.n, x.h, x.w, x.c
+    d.wgt, d.wgt_img_stride = (pc.wp.data_ptr() if pc is not None else wgt_ptr), wgt_img_stride
+    d.Cout = pc.cout if cout is None else cout
+    d.Cout_pad = pc.cout_pad if cout_pad is None else cout_pad
+    d.kh, d.kw, d.stride, d.pad, d.dil = (pc.kh if kh is None else kh), (pc.kw if kw is None else kw), stride, pad, 1
+    d.Ho = (x.h + 2 * pad - d.kh) // stride + 1
+    d.Wo = (x.w + 2 * pad - d.kw) // stride + 1
+    assert out.h == d.Ho and out.w == d.Wo and out.c >= d.Cout, (name, out.h, out.w, d.Ho, d.Wo)
+    d.out, d.out_cs = out.ptr, out.cs
+    if scale is not None:
+        d.scale, d.shift = scale.data_ptr(), shift.data_ptr()
+    elif affine and pc is not None and pc.has_affine:
+        d.scale, d.shift = pc.scale.data_ptr(), pc.shift.data_ptr()
+    if res is not None:
+        d.res, d.res_cs, d.res_mode = res.ptr, res.cs, res_mode
+    d.act, d.sigmoid_from = act, sigmoid_from
+    if om is not None:
+        d.dcn_offmask, d.dcn_om_cs = om.ptr, om.cs
+    return d
+
+
+def desc_with(d, **fields):
+    """A copy of descriptor d with `fields` set: a route of Engine._conv never changes the descriptor it was asked about."""
+    c = type(d).from_buffer_copy(d)
+    for k, v in fields.items():
+        setattr(c, k, v)
+    return c
+
+
+def conv_kind(family, tile=(), deform=False, splitk=1, wgsplit=1, kpair=False, per_image=False):
+    """The kind of a conv op: "family<tile,options>", the options in this order (bench.py and profiles/ key on the strings)."""
+    parts = [str(t) for t in tile] + ["deform"] * deform + ["splitk%d" % splitk] * (splitk > 1) \
+        + ["wgsplit%d" % wgsplit] * (wgsplit > 1) + ["kpair"] * kpair + ["per_image"] * per_image
+    return family + ("<%s>" % ",".join(parts) if parts else "")
+
+
+# what a route of Engine._conv answers when it takes a layer: kind (family, tile, conv_kind's options), launch closure, the
+# descriptor it launches (slot 4 of the op) and the tensors the plan has to keep alive for it
+_Route = collections.namedtuple("_Route", "family tile options launch desc keep")
+
+
 class Engine:
     def __init__(self, state_dict, conf, device=None, backbone_only=False):
         self.L = _hip.lib()
@@ -426,150 +475,127 @@ class Engine:
             plan.named[name] = v
         return v
 
-    def _conv(self, plan, name, pc, x, out, stride=1, pad=0, act=0, res=None, res_mode=0, sigmoid_from=-1, om=None,
-              planar=None, affine=True, wgt_ptr=None, wgt_img_stride=0, cout=None, cout_pad=None, scale=None, shift=None,
-              kh=None, kw=None, cin_true=None, wgt_frag=False):
-        d = ConvDesc()
-        d.inp, d.in_cs, d.N, d.H, d.W, d.Cin = x.ptr, x.cs, x.n, x.h, x.w, x.c
-        kh = pc.kh if kh is None else kh
-        kw = pc.kw if kw is None else kw
-        d.wgt = pc.wp.data_ptr() if wgt_ptr is None else wgt_ptr
-        d.wgt_img_stride = wgt_img_stride
-        d.Cout = pc.cout if cout is None else cout
-        d.Cout_pad = pc.cout_pad if cout_pad is None else cout_pad
-        d.kh, d.kw, d.stride, d.pad, d.dil = kh, kw, stride, pad, 1
-        d.Ho = (x.h + 2 * pad - kh) // stride + 1
-        d.Wo = (x.w + 2 * pad - kw) // stride + 1
-        if planar is not None:
-            t, img_stride, ch_off = planar
-            d.out, d.out_nchw, d.out_img_stride = t.data_ptr() + 4 * ch_off * d.Ho * d.Wo, 1, img_stride
-        else:
-            assert out.h == d.Ho and out.w == d.Wo and out.c >= d.Cout, (name, out.h, out.w, d.Ho, d.Wo)
-            d.out, d.out_cs = out.ptr, out.cs
-        if scale is not None:
-            d.scale, d.shift = scale.data_ptr(), shift.data_ptr()
-            plan.keep += [scale, shift]
-        elif affine and pc is not None and pc.has_affine:
-            d.scale, d.shift = pc.scale.data_ptr(), pc.shift.data_ptr()
-        if res is not None:
-            d.res, d.res_cs, d.res_mode = res.ptr, res.cs, res_mode
-        d.act, d.sigmoid_from = act, sigmoid_from
-        if om is not None:
-            d.dcn_offmask, d.dcn_om_cs = om.ptr, om.cs
-        L = self.L
+    def _conv(self, plan, name, pc, x, out, stride=1, pad=0, cin_true=None, wgt_frag=False, per_image=False, **layer):
+        """Append one convolution: its descriptor (conv_desc takes `layer`), launched by the first kernel family that takes it: F(4x4)
+        Winograd, F(2x2) Winograd, wave kernel on the caller's fragment-ordered weights (wgt_frag), wave kernel, implicit GEMM.
+        cin_true: the input channels the FLOPs count (default: pc's, or x's); per_image only marks the kind (image_gemm)."""
+        d = conv_desc(name, pc, x, out, stride, pad, **layer)
+        plan.keep += [layer[k] for k in ("scale", "shift") if layer.get(k) is not None]
+        route = (self._route_wino44(plan, name, d, pc) or self._route_wino(d, pc) or self._route_frag(name, d, wgt_frag)
+                 or self._route_wave(d, pc) or self._route_igemm(d))
+        plan.keep += route.keep
+        # algorithmic FLOPs of the layer: 2 * pixels * Cout * taps * Cin (true channel counts, no padding)
+        cin_true = cin_true if cin_true is not None else pc.cin if pc is not None else x.c
+        flops = 2.0 * d.N * d.Ho * d.Wo * d.Cout * d.kh * d.kw * cin_true
+        kind = conv_kind(route.family, route.tile, deform=d.dcn_offmask is not None, per_image=per_image, **route.options)
+        plan.ops.append((name, kind, flops, route.launch, route.desc))
+
+    def _launch(self, fn, d, *args):
+        """The launch closure of a descriptor entry point: fn(d, *args, stream)."""
         ref = ctypes.byref(d)
-        # the Winograd kernel works on 256-pixel x 32-channel tiles: a narrow layer (the 27-channel DCN offset/mask
-        # convs) on a small map yields < 128 workgroups and goes to the split-K igemm instead
-        wino_blocks = -(-(x.n * x.h * x.w) // 256) * (d.Cout_pad // 32)
-        strips = -(-(x.n * x.h * x.w) // 256)
+        return lambda st: _hip.check(fn(ref, *args, st))
+
+    def _splitk(self, plan_fn, d, workspace=lambda splits: True):
+        """Split-K of d as the library's `plan_fn` plans it -> (splits, the descriptor to launch, tensors to keep): a copy of d with
+        a fresh workspace where the plan splits and names scratch bytes (and `workspace(splits)` holds), else d itself."""
+        splits, nbytes = ctypes.c_int(), ctypes.c_longlong()
+        _hip.check(plan_fn(ctypes.byref(d), ctypes.byref(splits), ctypes.byref(nbytes)))
+        if splits.value > 1 and nbytes.value > 0 and workspace(splits.value):
+            ws = torch.empty(nbytes.value // 4, device=self.device, dtype=torch.float32)
+            return splits.value, desc_with(d, splitk_ws=ws.data_ptr(), splitk_ws_bytes=nbytes.value), [ws]
+        return splits.value, d, []
+
+    def _route_wino44(self, plan, name, d, pc):
+        """Winograd F(4x4,3x3): 4x fewer MFMA FLOPs than the direct convolution (F(2x2,3x3): 2.25x) where the layer fills the chip
+        with 16-tile workgroups (csrc/wino44_conv.hip).  The only route that touches the plan: it owns the touch bookkeeping."""
+        L = self.L
+        if (pc is None or pc._w_cpu is None or d.dcn_offmask is not None or d.sigmoid_from >= 0
+                or L.m3d_wino44_applicable(ctypes.byref(d)) != 1):
+            return None
+        strips = -(-(d.N * d.H * d.W) // 256)
         nb = 2 if (d.Cout_pad % 128 == 0 and strips * (d.Cout_pad // 128) >= WINO44_MIN_WGS) else \
             (1 if strips * (d.Cout_pad // 64) >= WINO44_MIN_WGS_NB1 else 0)
-        w44ok = (pc is not None and wgt_ptr is None and getattr(pc, "_w_cpu", None) is not None and om is None and planar is None
-                 and sigmoid_from < 0 and L.m3d_wino44_applicable(ref) == 1)
-        ks44 = 1
-        if w44ok and not nb and USE_WINO44_SPLITK:
+        splits, keep = 1, []
+        if not nb and USE_WINO44_SPLITK:
             # small maps (256 -> 256 @ 24x80, 512 -> 512 @ 12x40 at bs 8): K slices as gridDim.z fill the chip, a second launch
             # adds the partial outputs in slice order
-            ssplits, sbytes = ctypes.c_int(), ctypes.c_longlong()
-            _hip.check(L.m3d_wino44_splitk_plan(ref, ctypes.byref(ssplits), ctypes.byref(sbytes)))
-            if ssplits.value > 1:
-                ws = torch.empty(sbytes.value // 4, device=self.device, dtype=torch.float32)
-                plan.keep.append(ws)
-                d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), sbytes.value
-                nb, ks44 = W44_SPLIT_NB, ssplits.value
-        if w44ok and nb:
-            # Winograd F(4x4,3x3): 4x fewer MFMA FLOPs than the direct convolution (F(2x2,3x3): 2.25x) where the layer fills the
-            # chip with 16-tile workgroups (csrc/wino44_conv.hip)
-            u44 = pc.wino44()
-            plan.keep.append(u44)
-            d.wgt = u44.data_ptr()
-            flops = 2.0 * x.n * d.Ho * d.Wo * d.Cout * 9 * pc.cin
-            # U (2.4-38 MB) is cold in HBM when the layer starts and the kernel's B fragments run only ~1400 cycles ahead of the
-            # MFMAs: the PREVIOUS F(4x4) launch touches this layer's U (every thread a few lines, under its own first loads); a
-            # layer with no F(4x4) launch shortly before it gets a touch launch of its own
-            nxt = {"ptr": None, "bytes": 0}
-            if WINO44_TOUCH:
-                nbytes = u44.numel() * 4
-                if plan.w44_prev is not None and len(plan.ops) - plan.w44_prev[0] <= WINO44_TOUCH_SPAN:
-                    plan.w44_prev[1]["ptr"], plan.w44_prev[1]["bytes"] = u44.data_ptr(), nbytes
-                else:
-                    plan.ops.append((name + ".touch", "touch", 0.0,
-                                     lambda st: _hip.check(L.m3d_cache_touch(u44.data_ptr(), nbytes, st)), OpCost(nbytes)))
-            plan.w44_prev = (len(plan.ops), nxt)
-            kp = ",kpair" if (nb == 1 and ((ks44 == 1 and L.m3d_wino44_kpair(ref) == 1) or (ks44 > 1 and W44_SPLIT_KPAIR))) else ""
-            plan.ops.append((name, "wino44<16,%d%s%s>" % (16 * nb, ",splitk%d" % ks44 if ks44 > 1 else "", kp), flops,
-                             lambda st: _hip.check(L.m3d_wino44_conv3x3_forward_touch(ref, nb, nxt["ptr"], nxt["bytes"], st)), d))
-            return
-        if (pc is not None and wgt_ptr is None and getattr(pc, "wino", None) is not None and kh == 3 and kw == 3
-                and stride == 1 and pad == 1 and om is None and planar is None and x.h % 2 == 0 and x.w % 2 == 0
-                and wino_blocks >= WINO_MIN_BLOCKS):
-            # Winograd F(2x2,3x3): 2.25x fewer MFMA FLOPs for the plain 3x3 stride-1 layers
-            d.wgt = pc.wino.data_ptr()
-            flops = 2.0 * x.n * d.Ho * d.Wo * d.Cout * 9 * pc.cin
-            ssplits, sbytes = ctypes.c_int(), ctypes.c_longlong()          # thin layers: wave kernel split along K across waves
-            _hip.check(L.m3d_wino_conv3x3_splitk_plan(ref, ctypes.byref(ssplits), ctypes.byref(sbytes)))
-            if ssplits.value > 1:
-                ws = torch.empty(sbytes.value // 4, device=self.device, dtype=torch.float32)
-                plan.keep.append(ws)
-                d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), sbytes.value
-            if L.m3d_wino_conv3x3_variant(ref) == 1:
-                kind = "wino_wave<32,32%s>" % (",splitk%d" % ssplits.value if ssplits.value > 1 else "")
+            splits, d, keep = self._splitk(L.m3d_wino44_splitk_plan, d)
+            nb = W44_SPLIT_NB if splits > 1 else 0
+        if not nb:
+            return None
+        u44 = pc.wino44()
+        d = desc_with(d, wgt=u44.data_ptr())
+        # U (2.4-38 MB) is cold in HBM when the layer starts and the kernel's B fragments run only ~1400 cycles ahead of the
+        # MFMAs: the PREVIOUS F(4x4) launch touches this layer's U (every thread a few lines, under its own first loads); a
+        # layer with no F(4x4) launch shortly before it gets a touch launch of its own
+        nxt = {"ptr": None, "bytes": 0}
+        if WINO44_TOUCH:
+            nbytes = u44.numel() * 4
+            if plan.w44_prev is not None and len(plan.ops) - plan.w44_prev[0] <= WINO44_TOUCH_SPAN:
+                plan.w44_prev[1]["ptr"], plan.w44_prev[1]["bytes"] = u44.data_ptr(), nbytes
             else:
-                kind = "wino_lds<64,32,16>"
-            plan.ops.append((name, kind, flops, lambda st: _hip.check(L.m3d_wino_conv3x3_forward(ref, st)), d))
-            return
-        flops_true = 2.0 * x.n * d.Ho * d.Wo * d.Cout * kh * kw * (
-            cin_true if cin_true is not None else (pc.cin if (pc is not None and wgt_ptr is None) else x.c))
-        if wgt_frag:
-            # explicit fragment-ordered (per-image) weights: the caller has already decided for the wave-granular kernel
-            assert wgt_ptr is not None and planar is None and x.cs % 32 == 0 and x.ptr % 128 == 0, name
-            if L.m3d_conv_wave_applicable(ref) <= 0:
-                raise RuntimeError("%s: fragment-ordered weights but the wave kernel does not apply" % name)
-            plan.ops.append((name, "conv_wave", flops_true, lambda st: _hip.check(L.m3d_conv_wave_forward(ref, st)), d))
-            return
-        if (pc is not None and wgt_ptr is None and planar is None and (USE_DCN_WAVE if om is not None else USE_CONV_WAVE)
-                and x.cs % 32 == 0 and x.ptr % 128 == 0 and pc.cin_pad == x.c):
-            # wave-granular kernel (csrc/dcn_wave.hip); thin layers are split along K across the waves of a workgroup
-            wsplits, wbytes = ctypes.c_int(), ctypes.c_longlong()
-            _hip.check(L.m3d_conv_wave_splitk_plan(ref, ctypes.byref(wsplits), ctypes.byref(wbytes)))
-            if wsplits.value > 1 and USE_CONV_WAVE_WGSPLIT and (d.Cout_pad % 64 == 0 or (USE_OFFMASK_WAVE and wsplits.value <= 4)):
-                # (a plan that splits has already passed the fill threshold WITH its split)
-                frag = pc.frag()
-                d.wgt = frag.data_ptr()
-                kind = "conv_wave<%s>" % ",".join((["deform"] if om is not None else []) + ["wgsplit%d" % wsplits.value])
-                plan.ops.append((name, kind, flops_true, lambda st: _hip.check(L.m3d_conv_wave_forward_wgsplit(ref, st)), d))
-                return
-            ws = None
-            if wsplits.value > 1 and wbytes.value > 0:
-                ws = torch.empty(wbytes.value // 4, device=self.device, dtype=torch.float32)
-                d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), wbytes.value
-            if L.m3d_conv_wave_applicable(ref) > 0:
-                frag = pc.frag()
-                d.wgt = frag.data_ptr()
-                if ws is not None:
-                    plan.keep.append(ws)
-                kind = "conv_wave%s" % ("<%s>" % ",".join(
-                    (["deform"] if om is not None else []) + (["splitk%d" % wsplits.value] if wsplits.value > 1 else []))
-                    if (om is not None or wsplits.value > 1) else "")
-                plan.ops.append((name, kind, flops_true, lambda st: _hip.check(L.m3d_conv_wave_forward(ref, st)), d))
-                return
-            d.splitk_ws, d.splitk_ws_bytes = None, 0
+                plan.ops.append((name + ".touch", "touch", 0.0,
+                                 lambda st: _hip.check(L.m3d_cache_touch(u44.data_ptr(), nbytes, st)), OpCost(nbytes)))
+        plan.w44_prev = (len(plan.ops), nxt)        # (_conv appends this layer's op next)
+        kpair = nb == 1 and (L.m3d_wino44_kpair(ctypes.byref(d)) == 1 if splits == 1 else W44_SPLIT_KPAIR)
+        ref = ctypes.byref(d)
+        return _Route("wino44", (16, 16 * nb), dict(splitk=splits, kpair=kpair),
+                      lambda st: _hip.check(L.m3d_wino44_conv3x3_forward_touch(ref, nb, nxt["ptr"], nxt["bytes"], st)),
+                      d, keep + [u44])
+
+    def _route_wino(self, d, pc):
+        """Winograd F(2x2,3x3): 2.25x fewer MFMA FLOPs for the plain 3x3 stride-1 layers on even maps.  The kernel works on
+        256-pixel x 32-channel tiles: a narrow layer (the 27-channel DCN offset / mask convs) on a small map yields fewer than
+        WINO_MIN_BLOCKS workgroups and is left to the routes behind this one."""
+        L = self.L
+        blocks = -(-(d.N * d.H * d.W) // 256) * (d.Cout_pad // 32)
+        if (pc is None or pc.wino is None or (d.kh, d.kw, d.stride, d.pad) != (3, 3, 1, 1) or d.dcn_offmask is not None
+                or d.H % 2 or d.W % 2 or blocks < WINO_MIN_BLOCKS):
+            return None
+        # (thin layers: the wave form split along K across waves, where the library recommends it)
+        splits, d, keep = self._splitk(L.m3d_wino_conv3x3_splitk_plan, desc_with(d, wgt=pc.wino.data_ptr()))
+        launch = self._launch(L.m3d_wino_conv3x3_forward, d)
+        if L.m3d_wino_conv3x3_variant(ctypes.byref(d)) == 1:
+            return _Route("wino_wave", (32, 32), dict(splitk=splits), launch, d, keep)
+        return _Route("wino_lds", (64, 32, 16), {}, launch, d, keep)
+
+    def _route_frag(self, name, d, wgt_frag):
+        """Explicit fragment-ordered (per-image) weights: the caller has already decided for the wave-granular kernel."""
+        if not wgt_frag:
+            return None
+        assert d.in_cs % 32 == 0 and d.inp % 128 == 0, name
+        if self.L.m3d_conv_wave_applicable(ctypes.byref(d)) <= 0:
+            raise RuntimeError("%s: fragment-ordered weights but the wave kernel does not apply" % name)
+        return _Route("conv_wave", (), {}, self._launch(self.L.m3d_conv_wave_forward, d), d, [])
+
+    def _route_wave(self, d, pc):
+        """Wave-granular kernel (csrc/dcn_wave.hip), plain or deformable.  Thin layers are split along K: across the waves of a
+        workgroup (no workspace), or across workgroups through a workspace."""
+        L = self.L
+        if (pc is None or not (USE_DCN_WAVE if d.dcn_offmask is not None else USE_CONV_WAVE) or d.in_cs % 32 or d.inp % 128
+                or pc.cin_pad != d.Cin):
+            return None
+
+        def wgsplit(splits):        # (a plan that splits has already passed the fill threshold WITH its split)
+            return splits > 1 and USE_CONV_WAVE_WGSPLIT and (d.Cout_pad % 64 == 0 or (USE_OFFMASK_WAVE and splits <= 4))
+
+        splits, dw, keep = self._splitk(L.m3d_conv_wave_splitk_plan, d, workspace=lambda s: not wgsplit(s))
+        if wgsplit(splits):
+            fn, options = L.m3d_conv_wave_forward_wgsplit, dict(wgsplit=splits)
+        elif L.m3d_conv_wave_applicable(ctypes.byref(dw)) > 0:
+            fn, options = L.m3d_conv_wave_forward, dict(splitk=splits)
+        else:
+            return None
+        dw = desc_with(dw, wgt=pc.frag().data_ptr())
+        return _Route("conv_wave", (), options, self._launch(fn, dw), dw, keep)
+
+    def _route_igemm(self, d):
+        """Implicit GEMM (m3d_conv2d_forward): takes every descriptor; layers with too few output tiles are split along K."""
+        L = self.L
         bm, bn, bk, grid = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _hip.check(L.m3d_conv2d_tile(ref, ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(bk), ctypes.byref(grid)))
-        splits, ws_bytes = ctypes.c_int(), ctypes.c_longlong()
-        _hip.check(L.m3d_conv2d_splitk_plan(ref, ctypes.byref(splits), ctypes.byref(ws_bytes)))
-        if splits.value > 1:
-            ws = torch.empty(ws_bytes.value // 4, device=self.device, dtype=torch.float32)
-            plan.keep.append(ws)
-            d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws_bytes.value
-        kind = "igemm<%d,%d,%d%s%s%s>" % (bm.value, bn.value, bk.value, ",deform" if om is not None else "",
-                                          ",planar" if planar is not None else "",
-                                          ",splitk%d" % splits.value if splits.value > 1 else "")
-        # algorithmic FLOPs of the layer: 2 * pixels * Cout * taps * Cin (true channel counts, no padding)
-        if cin_true is None:
-            cin_true = pc.cin if (pc is not None and wgt_ptr is None) else x.c
-        flops = 2.0 * x.n * d.Ho * d.Wo * d.Cout * kh * kw * cin_true
-        plan.ops.append((name, kind, flops, lambda st: _hip.check(L.m3d_conv2d_forward(ref, st)), d))
+        _hip.check(L.m3d_conv2d_tile(ctypes.byref(d), ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(bk), ctypes.byref(grid)))
+        splits, d, keep = self._splitk(L.m3d_conv2d_splitk_plan, d)
+        return _Route("igemm", (bm.value, bn.value, bk.value), dict(splitk=splits), self._launch(L.m3d_conv2d_forward, d), d, keep)
 
     def _op(self, plan, name, kind, fn, flops=0.0, nbytes=None):
         """A launch outside the conv / head descriptors: `flops` = arithmetic it executes, `nbytes` = the HBM bytes it has to
@@ -993,8 +1019,7 @@ class Engine:
         ctot, off = self.anab_ctot, self.anab_off
         qkvs = self._buf(plan, B, fh, fw, ctot, _rup(ctot, 32))          # 128-byte pixel rows: the wave kernel's gather map
         self._conv(plan, "anab.qkvs", P["anab.qkvs"], x, qkvs, 1, 0, act=0, sigmoid_from=off["s"], affine=False)
-        items, bin_scale, bin_slots, bin_inv = self._anab_items(fh, fw)
-        n_bins, max_slots = len(bin_scale), int(bin_slots.max())
+        n_bins = sum(s * s for s in PSP_SIZES)
         # the two per-image GEMMs go to the wave-granular kernel when they yield enough waves; their weights (pooled keys /
         # values) are then written in MFMA-fragment order by the pooling finish and the key count is padded to 128
         fused = FUSED_ANAB and ((self.cv == 128 and self.ck in (64, 128, 168)) or (self.cv == 256 and self.ck == 168)) \
@@ -1005,31 +1030,14 @@ class Engine:
         keys_pad = _rup(n_bins, 128) if wave_logits else _rup(n_bins, 32)
         wave_pv = wave_ok and keys_pad % 32 == 0 and nw * (self.cv // 128) >= 900
         frag = (1 if wave_logits else 0) | (2 if wave_pv else 0)
-        d_items = torch.from_numpy(items).to(self.device)
-        d_bscale = torch.from_numpy(bin_scale).to(self.device)
-        d_bslots = torch.from_numpy(bin_slots).to(self.device)
-        d_binv = torch.from_numpy(bin_inv).to(self.device)
         ckv = self.ck + self.cv
-        partial = torch.empty(B * n_bins * max_slots * ckv, device=self.device, dtype=torch.float32)
         khat = torch.zeros(B * keys_pad * self.ck_pad, device=self.device, dtype=torch.float32)
         vhatT = torch.zeros(B * self.cv * keys_pad, device=self.device, dtype=torch.float32)
-        plan.keep += [d_items, d_bscale, d_bslots, d_binv, partial, khat, vhatT]
+        plan.keep += [khat, vhatT]
         plan.named["anab.khat"], plan.named["anab.vhatT"] = khat, vhatT
         kvv, sv = qkvs.slice(off["k"], ckv), qkvs.slice(off["s"], self.ns)
-        if fh % 16 == 0 and fw % 16 == 0 and PSP_SIZES == (1, 4, 8, 16) and USE_ANAB_NESTED:
-            # the windows of the four scales nest: one pass over the features (csrc/rpn_kernels.hip)
-            scratch = torch.empty(L.m3d_anab_pool_nested_scratch_bytes(B, ckv) // 4, device=self.device, dtype=torch.float32)
-            plan.keep.append(scratch)
-            self._op(plan, "anab.pool_nested", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_nested(
-                kvv.ptr, kvv.cs, sv.ptr, sv.cs, B, fh, fw, self.ck, self.cv, scratch.data_ptr(), khat.data_ptr(), keys_pad,
-                self.ck_pad, vhatT.data_ptr(), frag, st)), nbytes=B * HW * (ckv + self.ns) * 4)
-        else:
-            self._op(plan, "anab.pool_partial", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_partial(
-                kvv.ptr, kvv.cs, sv.ptr, sv.cs, d_items.data_ptr(), items.shape[0], d_bscale.data_ptr(), n_bins,
-                partial.data_ptr(), max_slots, B, fh, fw, ckv, st)))
-            self._op(plan, "anab.pool_finish", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_finish(
-                partial.data_ptr(), d_bslots.data_ptr(), d_binv.data_ptr(), n_bins, max_slots, self.ck, self.cv,
-                khat.data_ptr(), keys_pad, self.ck_pad, vhatT.data_ptr(), B, frag, st)))
+        self._anab_pool(plan, kvv.ptr, kvv.cs, sv.ptr, sv.cs, B, fh, fw, khat, vhatT, keys_pad, frag, nested=USE_ANAB_NESTED,
+                        nested_nbytes=B * HW * (ckv + self.ns) * 4)
         qv = qkvs.slice(off["q"], self.ck_pad)
         if fused:
             # logits + softmax + P.V in one launch: the fp32 logits (7680 x 352 per image) never reach HBM
@@ -1064,12 +1072,11 @@ class Engine:
             sub = _Plan()
             for i in range(B):
                 self._conv(sub, name, None, image(inp, i), image(outv, i), 1, 0, res=None if res is None else image(res, i),
-                           wgt_ptr=wgt.data_ptr() + 4 * i * stride, kh=1, kw=1, **kw)
+                           wgt_ptr=wgt.data_ptr() + 4 * i * stride, kh=1, kw=1, per_image=True, **kw)
             assert len(sub.ops) == B and len({op[1] for op in sub.ops}) == 1, [op[:2] for op in sub.ops]
             plan.keep += sub.keep
             fns = [op[3] for op in sub.ops]
-            plan.ops.append((name, sub.ops[0][1][:-1] + ",per_image>", sum(op[2] for op in sub.ops),
-                             lambda st: [fn(st) for fn in fns], sub.ops[0][4]))
+            plan.ops.append((name, sub.ops[0][1], sum(op[2] for op in sub.ops), lambda st: [fn(st) for fn in fns], sub.ops[0][4]))
 
         logits = self._buf(plan, B, fh, fw, keys_pad)
         image_gemm("anab.logits", qv, logits, khat, keys_pad * self.ck_pad, wave_logits, act=0, affine=False, cout=n_bins,
@@ -1078,6 +1085,33 @@ class Engine:
             logits.ptr, B * HW, n_bins, keys_pad, st)), nbytes=B * HW * n_bins * 8)
         image_gemm("anab.pv", logits, out, vhatT, self.cv * keys_pad, wave_pv, res=x, act=act, res_mode=res_mode, cout=self.cv,
                    cout_pad=_rup(self.cv, 32), scale=scale, shift=shift, cin_true=n_bins)
+
+    def _anab_pool(self, plan, kv_ptr, kv_cs, s_ptr, s_cs, B, fh, fw, khat, vhatT, keys_pad, frag, nested=True, nested_nbytes=None):
+        """The gated pyramid pooling of ANAB in both plans: fp32 K|V (kv_ptr, pixel stride kv_cs) weighted by the gates (s_ptr, s_cs)
+        -> the pooled keys khat [B][keys_pad][ck_pad] and values vhatT [B][cv][keys_pad]; frag: bit 0 / bit 1 = khat / vhatT in
+        MFMA-fragment order.  One pass where the windows of the four scales nest and `nested` allows it (nested_nbytes: the cost slot
+        of that op), else partial sums per work item and a finish launch."""
+        L, ck, cv = self.L, self.ck, self.cv
+        if nested and fh % 16 == 0 and fw % 16 == 0 and PSP_SIZES == (1, 4, 8, 16):
+            # the windows of the four scales nest: one pass over the features (csrc/rpn_kernels.hip)
+            scratch = torch.empty(L.m3d_anab_pool_nested_scratch_bytes(B, ck + cv) // 4, device=self.device, dtype=torch.float32)
+            plan.keep.append(scratch)
+            self._op(plan, "anab.pool_nested", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_nested(
+                kv_ptr, kv_cs, s_ptr, s_cs, B, fh, fw, ck, cv, scratch.data_ptr(), khat.data_ptr(), keys_pad, self.ck_pad,
+                vhatT.data_ptr(), frag, st)), nbytes=nested_nbytes)
+            return
+        items, bin_scale, bin_slots, bin_inv = self._anab_items(fh, fw)
+        n_bins, max_slots = len(bin_scale), int(bin_slots.max())
+        d_items, d_bscale = torch.from_numpy(items).to(self.device), torch.from_numpy(bin_scale).to(self.device)
+        d_bslots, d_binv = torch.from_numpy(bin_slots).to(self.device), torch.from_numpy(bin_inv).to(self.device)
+        partial = torch.empty(B * n_bins * max_slots * (ck + cv), device=self.device, dtype=torch.float32)
+        plan.keep += [d_items, d_bscale, d_bslots, d_binv, partial]
+        self._op(plan, "anab.pool_partial", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_partial(
+            kv_ptr, kv_cs, s_ptr, s_cs, d_items.data_ptr(), items.shape[0], d_bscale.data_ptr(), n_bins, partial.data_ptr(),
+            max_slots, B, fh, fw, ck + cv, st)))
+        self._op(plan, "anab.pool_finish", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_finish(
+            partial.data_ptr(), d_bslots.data_ptr(), d_binv.data_ptr(), n_bins, max_slots, ck, cv, khat.data_ptr(), keys_pad,
+            self.ck_pad, vhatT.data_ptr(), B, frag, st)))
 
     @classmethod
     def anab_standalone(cls, mod, x):

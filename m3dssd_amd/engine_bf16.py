@@ -653,28 +653,8 @@ class EngineBF16(Engine):
             self._op(plan, "anab.pool_nested", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_nested_bf16_ex(
                 kvb.ptr, kvb.cs, sg.ptr, sg.cs, B, fh, fw, ck, cv, scratch.data_ptr(), khat.data_ptr(), keys_pad, ck_pad,
                 vhatT.data_ptr(), 0, khat16.data_ptr(), vhat16.data_ptr(), st)))
-        elif nested:      # the windows of the four scales nest (48x160 map): one pass over the features
-            kv_ptr, s_ptr = kvs.ptr, kvs.ptr + 4 * (ck + cv)
-            scratch = torch.empty(L.m3d_anab_pool_nested_scratch_bytes(B, ck + cv) // 4, device=self.device, dtype=torch.float32)
-            plan.keep.append(scratch)
-            self._op(plan, "anab.pool_nested", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_nested(
-                kv_ptr, kvs.cs, s_ptr, kvs.cs, B, fh, fw, ck, cv, scratch.data_ptr(), khat.data_ptr(), keys_pad, ck_pad,
-                vhatT.data_ptr(), 0, st)))
-        else:
-            kv_ptr, s_ptr = kvs.ptr, kvs.ptr + 4 * (ck + cv)
-            items, bin_scale, bin_slots, bin_inv = self._anab_items(fh, fw)
-            max_slots = int(bin_slots.max())
-            d_items, d_bscale = torch.from_numpy(items).to(self.device), torch.from_numpy(bin_scale).to(self.device)
-            d_bslots, d_binv = torch.from_numpy(bin_slots).to(self.device), torch.from_numpy(bin_inv).to(self.device)
-            partial = torch.empty(B * n_bins * max_slots * (ck + cv), device=self.device, dtype=torch.float32)
-            plan.keep += [d_items, d_bscale, d_bslots, d_binv, partial]
-            self._op(plan, "anab.pool_partial", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_partial(
-                kv_ptr, kvs.cs, s_ptr, kvs.cs, d_items.data_ptr(), items.shape[0], d_bscale.data_ptr(), n_bins,
-                partial.data_ptr(), max_slots, B, fh, fw, ck + cv, st)))
-            self._op(plan, "anab.pool_finish", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_finish(
-                partial.data_ptr(), d_bslots.data_ptr(), d_binv.data_ptr(), n_bins, max_slots, ck, cv, khat.data_ptr(),
-                keys_pad, ck_pad, vhatT.data_ptr(), B, 0, st)))
-        if not kv16:
+        else:             # fp32 K|V|S: the pooling of the fp32 plan, row-major khat / vhatT, then their bf16 twins
+            self._anab_pool(plan, kvs.ptr, kvs.cs, kvs.ptr + 4 * (ck + cv), kvs.cs, B, fh, fw, khat, vhatT, keys_pad, 0)
             self._op(plan, "anab.khat_bf16", "convert", lambda st: _hip.check(L.m3d_f32_to_bf16(
                 khat.data_ptr(), khat16.data_ptr(), khat.numel(), st)))
             self._op(plan, "anab.vhat_bf16", "convert", lambda st: _hip.check(L.m3d_f32_to_bf16(

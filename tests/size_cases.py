@@ -1,6 +1,7 @@
 """The image sizes of tests/test_sizes_host.py (CPU) and tests/test_gpu_sizes.py (GPU): one table, chosen from the thresholds of
-Engine._conv / Engine._anab_ops / EngineBF16._anab_bf16 so that every plan branch the two benched sizes (128x320, 384x1280) never
-take is taken by one of them, and with frames chosen on the CPU so that the oracle has no (or few) near-ties.
+the routes of Engine._conv (Engine._route_wino44 / _route_wino / _route_wave, the library's igemm split-K) and of Engine._anab_ops /
+Engine._anab_pool / EngineBF16._anab_bf16 so that every plan branch the two benched sizes (128x320, 384x1280) never take is taken
+by one of them, and with frames chosen on the CPU so that the oracle has no (or few) near-ties.
 
 A "near-tie pixel" of the free-running oracle: its top-1 minus top-2 foreground probability is below NEAR_TIE, or its top-1
 probability lies within NEAR_TIE of the hard-mask threshold 0.5.  NEAR_TIE is twice the 1e-4 within which
