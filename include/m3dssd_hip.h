@@ -26,6 +26,8 @@
  *   m3d_rpn_precompute_targets . Kitti_Dataset_torch._targets, lib/dataloader.py:1014-1144, for a whole batch
  *   m3d_rpn_target_stats ....... the per-image sums of compute_bbox_stats, lib/rpn_util.py:732-889 (it calls the numpy
  *                                 compute_targets twice per image of the imdb; float64 rois, unlike the loss)
+ *   m3d_optim_prepare / _step .. torch.optim.SGD / Adam / Adamax .step() as lib/core.py:76-99 constructs them, and the
+ *                                 `if total_loss > 0` of scripts/train_rpn_3d.py:208-218 as a device decision
  *   _nms / m3d_nms_sorted_dev .. void _nms(int* keep_out, int* num_out, const float* boxes_host,
  *                                 int boxes_num, int boxes_dim, float nms_overlap_thresh, int device_id)
  *                                 lib/nms/gpu_nms.hpp:1-2, lib/nms/nms_kernel.cu:91-144 (kernel :34-78)
@@ -99,7 +101,8 @@ const char *m3d_last_error(void);
  *                  m3d_refine_3d_host (additive);
  *                  m3d_rpn_target_stats, m3d_rpn_target_stats_workspace_bytes (additive);
  *                  m3d_dcn_v2_backward_det, m3d_dcn_v2_backward_det_bf16, m3d_dcn_v2_backward_det_workspace_bytes,
- *                  m3d_dcn_v2_backward_det_workspace_bytes_bf16 (additive). */
+ *                  m3d_dcn_v2_backward_det_workspace_bytes_bf16 (additive);
+ *                  m3d_optim_prepare, m3d_optim_step, m3d_optim_state_bytes (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -747,6 +750,56 @@ long long m3d_rpn_target_stats_workspace_bytes(int B, long long R);
 int m3d_rpn_target_stats(const double *anchors, int A, int H, int W, const double *conf, int n_conf, const double *gt_table, int B,
                          int Gmax, const double *center, double *out, void *workspace, long long workspace_bytes,
                          m3d_stream_t stream);
+
+/* The optimizer step on the device (csrc/optim.hip): torch.optim.SGD(lr, momentum, weight_decay), Adam(lr, weight_decay) and
+ * Adamax(lr, weight_decay) as lib/core.py:76-99 builds them, over a whole float32 parameter set, and the decision of
+ * scripts/train_rpn_3d.py:208-218 (`if total_loss > 0`) without the host.  kind: 0 SGD, 1 Adam, 2 Adamax.
+ *   table    device, n_entries records of M3D_OPTIM_ENTRY_BYTES: { float *p, *g, *s0, *s1; long long numel; int group, pad; }.
+ *            s0 = momentum_buffer (null: the group's momentum is 0) / exp_avg, s1 = exp_avg_sq / exp_inf (null for SGD); all float32,
+ *            contiguous, `numel` elements, 4-byte aligned (16-byte aligned tensors are accessed 16 bytes at a time); group <
+ *            n_groups.  The CONTENTS of the table are the caller's responsibility: the library cannot read them on the host.
+ *   chunks   device, n_chunks records { int entry, index; }: elements [index * M3D_OPTIM_CHUNK, min(numel, (index + 1) *
+ *            M3D_OPTIM_CHUNK)) of table[entry].  Every element of every tensor in exactly one chunk; one workgroup per chunk.
+ *   hyper    HOST, float64 [n_groups][M3D_OPTIM_HYPER_COLS]: lr, momentum, weight_decay, beta1, beta2, eps.  They travel as kernel
+ *            arguments (no upload); each float32 scalar of the update is the float64 expression rounded once (e.g. 1 - beta1).
+ *   state    device, m3d_optim_state_bytes(n_chunks) bytes, 16-byte aligned: a head of M3D_OPTIM_STATE_HEAD_BYTES (fields at the
+ *            M3D_OPTIM_STATE_* byte offsets) followed by the per-chunk partials.  The caller zeroes it once and sets the 2 x 8
+ *            running products to 1.0; afterwards it belongs to these calls (t, products) and may be read at any time.
+ * m3d_optim_prepare: grad_sq_sum = sum g*g over the table (float64; fixed order: per chunk in thread order and a fixed tree, then
+ * the chunk partials in chunk order, 256 consecutive runs combined by the same tree; no atomics: the same bits on every launch),
+ * grad_nonfinite = the number of inf / NaN gradient elements, do_step = (loss == null || *loss > 0) && (!skip_nonfinite ||
+ * grad_nonfinite == 0) -- `loss` is a device float32 scalar; NaN gives no step.  When do_step: t += 1, prod1[g] *= beta1,
+ * prod2[g] *= beta2 (float64), bc1 = 1 - prod1, bc2_sqrt = sqrt(1 - prod2), step_size = lr / bc1, rounded to float32 once (Adam,
+ * Adamax).  Otherwise t, the products and the derived scalars keep their bits.
+ * m3d_optim_step: nothing is written when do_step is clear.  Otherwise p and the state tensors are updated in place by the
+ * arithmetic stated at the top of csrc/optim.hip (one correctly rounded float32 operation at a time, no FMA; tests/optim_ref.py is
+ * the same in numpy), and with zero_grads != 0 every g is overwritten with zeros in the same pass.  Must follow a prepare on the
+ * same stream with the same table, kind and hyper.
+ * Errors (M3D_E_ARG, nothing launched): a null table / chunks / hyper / state, negative sizes, kind outside 0 .. 2, n_groups
+ * outside 1 .. M3D_OPTIM_MAX_GROUPS, a non-finite or negative setting, betas outside [0, 1), a state block below
+ * m3d_optim_state_bytes (the message carries both sizes).  m3d_optim_state_bytes returns -1 for n_chunks < 0. */
+#define M3D_OPTIM_CHUNK 4096
+#define M3D_OPTIM_MAX_GROUPS 8
+#define M3D_OPTIM_ENTRY_BYTES 48
+#define M3D_OPTIM_HYPER_COLS 6
+enum {
+    M3D_OPTIM_STATE_GRAD_SQ_SUM = 0, /* double */
+    M3D_OPTIM_STATE_NONFINITE = 8,   /* long long */
+    M3D_OPTIM_STATE_DO_STEP = 16,    /* int */
+    M3D_OPTIM_STATE_T = 24,          /* long long: taken steps */
+    M3D_OPTIM_STATE_PROD1 = 32,      /* double [M3D_OPTIM_MAX_GROUPS]: beta1^t */
+    M3D_OPTIM_STATE_PROD2 = 96,      /* double [M3D_OPTIM_MAX_GROUPS]: beta2^t */
+    M3D_OPTIM_STATE_BC1 = 160,       /* float [M3D_OPTIM_MAX_GROUPS] */
+    M3D_OPTIM_STATE_BC2_SQRT = 192,  /* float [M3D_OPTIM_MAX_GROUPS] */
+    M3D_OPTIM_STATE_STEP_SIZE = 224, /* float [M3D_OPTIM_MAX_GROUPS]: lr / bc1 */
+    M3D_OPTIM_STATE_HEAD_BYTES = 256
+};
+long long m3d_optim_state_bytes(int n_chunks);
+int m3d_optim_prepare(const void *table, int n_entries, const void *chunks, int n_chunks, int kind, const double *hyper,
+                      int n_groups, const float *loss, int skip_nonfinite, void *state, long long state_bytes,
+                      m3d_stream_t stream);
+int m3d_optim_step(const void *table, int n_entries, const void *chunks, int n_chunks, int kind, const double *hyper, int n_groups,
+                   int zero_grads, void *state, long long state_bytes, m3d_stream_t stream);
 
 /* Weight packing: [Cout, Cin, kh, kw] (torch layout) -> [Cout_pad, kh*kw*Cin_pad] (tap-major, zero pad). */
 int m3d_pack_conv_weight(const float *w, float *packed, int Cout, int Cout_pad, int Cin, int Cin_pad, int kh,

@@ -123,7 +123,9 @@ def bench_operator_bf16(a, dev, ck, cv, H=48, W=160):
     print(json.dumps(res), flush=True)
 
 
-def bench_iteration(a, dev, autocast=False):
+def iteration_case(dev):
+    """(net in train mode, conf, frames, imobjs, criterion) of the timed training iteration: anab_fullalign, DLA-34, B = 2 at
+    384x1280, eight ground truths per image (shared with tools/optim_bench.py)."""
     from m3dssd_amd import synth
     from m3dssd_amd.config import Conf
     from model.M3d_inference_align import build
@@ -150,7 +152,12 @@ def bench_iteration(a, dev, autocast=False):
             gts.append(Conf(cls=("Car", "Pedestrian", "Cyclist")[i % 3], ign=False, visibility=1.0, bbox_full=np.array([bx, by, w, h]),
                             bbox_3d=b3))
         imobjs.append(Conf(gts=gts, p2=np.eye(4), p2_inv=np.eye(4), scale_factor=1.0))
-    crit = RPN_3D_loss(conf)
+    return net, conf, x, imobjs, RPN_3D_loss(conf)
+
+
+def bench_iteration(a, dev, autocast=False):
+    net, conf, x, imobjs, crit = iteration_case(dev)
+    crop, B = (384, 1280), 2
     opt = torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9)
 
     def step():
