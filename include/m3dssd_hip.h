@@ -430,6 +430,7 @@ int m3d_anab_attend_bf16(const void *q, int q_cs, const void *khat, const void *
 int m3d_anab_attend_bf16_rows(const void *q, int q_cs, const void *khat, const void *vhatT, int B, int HW, int Ck_pad, int keys,
                               int keys_pad, int Cv, const void *res, int res_cs, const float *scale, const float *shift, int act,
                               void *out, int out_cs, const int *rows, const int *n_rows, m3d_stream_t stream);
+/* 2 x 2 max-pool, stride 2, odd H / W floored; H or W of 1 has no output element: M3D_OK, nothing launched (m3d_maxpool2x2 likewise). */
 int m3d_maxpool2x2_bf16(const void *in, int in_cs, void *out, int out_cs, int N, int H, int W, int C, m3d_stream_t stream);
 int m3d_upsample2x_add_bf16(const void *in, int in_cs, const float *wgt /*[4][4][C] fp32*/, const void *skip, int skip_cs,
                             void *out, int out_cs, int N, int H, int W, int C, m3d_stream_t stream);

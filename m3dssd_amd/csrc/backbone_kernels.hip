@@ -482,6 +482,7 @@ extern "C" int m3d_maxpool2x2(const float *in, int in_cs, float *out, int out_cs
 {
     M3D_REQUIRE(in && out && C % 4 == 0 && in_cs % 4 == 0 && out_cs % 4 == 0, "maxpool: C and strides must be x4");
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 4);
+    if (total <= 0) return M3D_OK;                               // H or W of 1: no output element, and a grid of 0 blocks is a launch error
     hipLaunchKernelGGL(maxpool2x2_kernel, dim3(imin(cdiv(total, 256), 8192)), dim3(256), 0, (hipStream_t)stream, in,
                        in_cs, out, out_cs, N, H, W, C / 4);
     M3D_LAUNCH_CHECK();

@@ -170,6 +170,7 @@ extern "C" int m3d_maxpool2x2_bf16(const void *in, int in_cs, void *out, int out
 {
     M3D_REQUIRE(in && out && C % 8 == 0 && in_cs % 8 == 0 && out_cs % 8 == 0, "maxpool_bf16: C and strides must be x8");
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 8);
+    if (total <= 0) return M3D_OK;                               // H or W of 1: no output element, and a grid of 0 blocks is a launch error
     hipLaunchKernelGGL(maxpool2x2_bf16_kernel, dim3(imin(cdiv(total, 256), 16384)), dim3(256), 0, (hipStream_t)stream,
                        (const __bf16 *)in, in_cs, (__bf16 *)out, out_cs, N, H, W, C / 8);
     M3D_LAUNCH_CHECK();
