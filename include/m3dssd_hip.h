@@ -102,7 +102,9 @@ const char *m3d_last_error(void);
  *                  m3d_rpn_target_stats, m3d_rpn_target_stats_workspace_bytes (additive);
  *                  m3d_dcn_v2_backward_det, m3d_dcn_v2_backward_det_bf16, m3d_dcn_v2_backward_det_workspace_bytes,
  *                  m3d_dcn_v2_backward_det_workspace_bytes_bf16 (additive);
- *                  m3d_optim_prepare, m3d_optim_step, m3d_optim_state_bytes (additive). */
+ *                  m3d_optim_prepare, m3d_optim_step, m3d_optim_state_bytes (additive);
+ *                  m3d_bn_act_train_forward, m3d_bn_act_train_backward, m3d_bn_act_train_workspace_bytes,
+ *                  m3d_bn_act_train_chunks (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -801,6 +803,43 @@ int m3d_optim_prepare(const void *table, int n_entries, const void *chunks, int 
                       m3d_stream_t stream);
 int m3d_optim_step(const void *table, int n_entries, const void *chunks, int n_chunks, int kind, const double *hyper, int n_groups,
                    int zero_grads, void *state, long long state_bytes, m3d_stream_t stream);
+
+/* BatchNorm2d with BATCH statistics + optional residual add + activation, for TRAINING (csrc/bn_train.hip): the chain behind every
+ * convolution of the training forward (model/pose_dla_dcn.py:107-121,261-269,379-389,482-485, M3d_inference_align.py:66-210) as one
+ * operator.  fp32, NCHW, contiguous: x, residual, y and the gradients [B, C, H, W]; gamma, beta, the running statistics, save_mean,
+ * save_invstd, grad_gamma, grad_beta [C]; N = B*H*W values per channel.  slope in [0, 1]: 0 = ReLU, a LeakyReLU's negative_slope,
+ * 1 = no activation.
+ *   forward   mean = sum(x) / N,   var = max(sum(x^2) / N - mean^2, 0)  (biased),   invstd = 1 / sqrt(var + eps)
+ *             z = (x - mean) * invstd * gamma + beta (+ residual),   y = z > 0 ? z : slope * z
+ *             running_mean = (1 - momentum) * running_mean + momentum * mean
+ *             running_var  = (1 - momentum) * running_var  + momentum * var * N / (N - 1)          (either may be NULL: not kept)
+ *             save_mean = mean, save_invstd = invstd, rounded once to float32: what the backward takes
+ *   backward  dz = grad_y * (y > 0 ? 1 : slope)   (the mask is taken from the saved OUTPUT y),   grad_residual = dz,
+ *             grad_beta = sum(dz),   grad_gamma = sum(dz * xhat) with xhat = (x - save_mean) * save_invstd,
+ *             grad_x = gamma * save_invstd * (dz - grad_beta / N - xhat * grad_gamma / N)
+ * Structure: a channel's N positions n = b * H*W + p are cut into m3d_bn_act_train_chunks(B, C, H, W) chunks of 4096 (the last one
+ * shorter), one workgroup per (channel, chunk).  Each direction is two launches: the first writes the two sums of every (channel,
+ * chunk) into the workspace, every workgroup of the second adds the partials of its channel in a fixed order and applies.  The four
+ * sums (x, x^2; dz, dz * xhat) are accumulated in float64 from the float32 values; the running statistics are evaluated in float64
+ * and rounded once.
+ * Semantics: no atomics and a fixed summation order -- the same bits on every launch; every word of the workspace that is read
+ * was written by the same call, so nothing depends on what it held; every non-NULL gradient is OVERWRITTEN, a NULL gradient is "not
+ * wanted" and skips the work only it needs, and a gradient has the same bits whichever others were asked for (all four NULL: nothing
+ * is launched).  16-byte accesses when H*W % 4 == 0 and x / residual / y / grad_y / grad_x / grad_residual are 16-byte aligned, one
+ * element per lane otherwise; all tensors 4-byte aligned.  y may not alias x or residual.
+ * Workspace: 16-byte aligned, m3d_bn_act_train_workspace_bytes(B, C, H, W) bytes (16 per channel and chunk; the same for both
+ * directions); -1 (and -1 chunks) for a shape that is not supported: a size < 1, N < 2, N beyond 2^31 - 8193.
+ * Errors (M3D_E_ARG with m3d_last_error, nothing launched): such a shape (N < 2: batch statistics of one value, torch raises there
+ * too), slope outside [0, 1] (NaN included), eps negative or not finite, a NULL required pointer (everything not marked NULL-able
+ * above, the workspace included), a workspace below the size asked for (the message carries both sizes) or not 16-byte aligned. */
+long long m3d_bn_act_train_workspace_bytes(int B, int C, int H, int W);
+int m3d_bn_act_train_chunks(int B, int C, int H, int W);
+int m3d_bn_act_train_forward(const float *x, const float *residual, const float *gamma, const float *beta, float *running_mean,
+                             float *running_var, float *y, float *save_mean, float *save_invstd, int B, int C, int H, int W, double eps,
+                             double momentum, float slope, void *workspace, long long workspace_bytes, m3d_stream_t stream);
+int m3d_bn_act_train_backward(const float *grad_y, const float *x, const float *y, const float *gamma, const float *save_mean,
+                              const float *save_invstd, float *grad_x, float *grad_residual, float *grad_gamma, float *grad_beta, int B,
+                              int C, int H, int W, float slope, void *workspace, long long workspace_bytes, m3d_stream_t stream);
 
 /* Weight packing: [Cout, Cin, kh, kw] (torch layout) -> [Cout_pad, kh*kw*Cin_pad] (tap-major, zero pad). */
 int m3d_pack_conv_weight(const float *w, float *packed, int Cout, int Cout_pad, int Cin, int Cin_pad, int kh,

@@ -157,8 +157,9 @@ class DeformConv(nn.Module):
 
     def forward(self, x):
         if self.training and torch.is_grad_enabled() and x.is_cuda:
-            # training form, model/pose_dla_dcn.py:482-485: differentiable DCN, torch BatchNorm with batch statistics
-            return self.actf(self.conv(x))
+            # training form, model/pose_dla_dcn.py:482-485: differentiable DCN, BatchNorm with batch statistics (torch's layers, or
+            # the fused operator behind train.set_fused_batchnorm)
+            return train.seq_forward(self.actf, self.conv(x))
         from .standalone import deform_conv_forward
         return deform_conv_forward(self, x)
 

@@ -459,6 +459,119 @@ def anab_attention_bf16(q, k, v, gates, B, H, W):
     return _ANABAttentionBf16.apply(q, k, v, gates, B, H, W)
 
 
+def _bn_check(name, named):
+    """The type rules of both calls: device tensors (NotImplementedError: no CPU fallback), float32 (RuntimeError naming the dtype)."""
+    _require_cuda(*(t for _, t in named))
+    for what, t in named:
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: %s is %s; only float32 is supported" % (name, what, t.dtype))
+
+
+def _bn_forward(x, residual, weight, bias, running_mean, running_var, momentum, eps, slope):
+    """m3d_bn_act_train_forward -> (y, save_mean, save_invstd, x and weight as handed over).  The running statistics are updated in
+    place."""
+    name = "bn_act_train_forward"
+    named = [("x", x), ("weight", weight), ("bias", bias)] + [(w, t) for w, t in (("residual", residual), (
+        "running_mean", running_mean), ("running_var", running_var)) if t is not None]
+    _bn_check(name, named)
+    if x.dim() != 4:
+        raise RuntimeError("%s: x must be [B, C, H, W] (got %s)" % (name, tuple(x.shape)))
+    B, C, H, W = x.shape
+    if residual is not None and residual.shape != x.shape:
+        raise RuntimeError("%s: residual %s does not match x %s" % (name, tuple(residual.shape), tuple(x.shape)))
+    for what, t in named[1:3] + [n for n in named[3:] if n[0] != "residual"]:
+        if tuple(t.shape) != (C,):
+            raise RuntimeError("%s: %s must be [C = %d] (got %s)" % (name, what, C, tuple(t.shape)))
+    for what, t in (("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError("%s: %s is written in place and has to be contiguous" % (name, what))
+    L = _hip.lib()
+    nbytes = L.m3d_bn_act_train_workspace_bytes(B, C, H, W)
+    if nbytes < 0:
+        # (torch: "Expected more than 1 value per channel when training")
+        raise RuntimeError("%s: unsupported shape %s (more than 1 value per channel is needed)" % (name, tuple(x.shape)))
+    x = x.detach().contiguous()
+    residual = None if residual is None else residual.detach().contiguous()
+    weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+    y = torch.empty_like(x)
+    save_mean = torch.empty(C, device=x.device, dtype=torch.float32)
+    save_invstd = torch.empty_like(save_mean)
+    ws, base = _workspace(nbytes, x.device)
+    with torch.cuda.device(x.device):
+        _hip.check(L.m3d_bn_act_train_forward(x.data_ptr(), None if residual is None else residual.data_ptr(), weight.data_ptr(),
+                                              bias.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
+                                              None if running_var is None else running_var.data_ptr(), y.data_ptr(),
+                                              save_mean.data_ptr(), save_invstd.data_ptr(), B, C, H, W, float(eps), float(momentum),
+                                              float(slope), base, nbytes, _stream()))
+    return y, save_mean, save_invstd, x, weight
+
+
+def bn_act_train_forward(x, residual, weight, bias, running_mean, running_var, momentum, eps, slope):
+    """m3d_bn_act_train_forward, value only: y = act(batch_norm(x; batch statistics) (+ residual)) with act(z) = z > 0 ? z : slope * z,
+    and the running statistics (either may be None) updated in place as nn.BatchNorm2d does with a float ``momentum``."""
+    return _bn_forward(x, residual, weight, bias, running_mean, running_var, momentum, eps, slope)[0]
+
+
+def _bn_backward(grad_y, x, y, weight, save_mean, save_invstd, slope, needs):
+    """m3d_bn_act_train_backward on operands the forward has checked and made contiguous; ``grad_y`` is autograd's."""
+    name = "bn_act_train_backward"
+    if not grad_y.is_cuda:
+        raise NotImplementedError("M3DSSD HIP ops need ROCm device tensors; there is no CPU fallback")
+    if grad_y.dtype != torch.float32 or grad_y.shape != x.shape:
+        raise RuntimeError("%s: grad_y is %s %s; float32 %s is needed" % (name, grad_y.dtype, tuple(grad_y.shape), tuple(x.shape)))
+    B, C, H, W = x.shape
+    L = _hip.lib()
+    nbytes = L.m3d_bn_act_train_workspace_bytes(B, C, H, W)
+    grad_y = grad_y.contiguous()                                 # (an expanded grad_y is copied)
+    grads = [torch.empty_like(x) if needs[0] else None, torch.empty_like(x) if needs[1] else None,
+             torch.empty_like(save_mean) if needs[2] else None, torch.empty_like(save_mean) if needs[3] else None]
+    ws, base = _workspace(nbytes, x.device)
+    with torch.cuda.device(x.device):
+        _hip.check(L.m3d_bn_act_train_backward(grad_y.data_ptr(), x.data_ptr(), y.data_ptr(), weight.data_ptr(), save_mean.data_ptr(),
+                                               save_invstd.data_ptr(), *(None if g is None else g.data_ptr() for g in grads), B, C, H, W,
+                                               float(slope), base, nbytes, _stream()))
+    return tuple(grads)
+
+
+def bn_act_train_backward(grad_y, x, y, weight, save_mean, save_invstd, slope, needs=(True, True, True, True)):
+    """m3d_bn_act_train_backward: (grad_x, grad_residual, grad_weight, grad_bias), freshly written and contiguous; an entry of
+    ``needs`` that is False gives None and skips the work only that gradient needs."""
+    name = "bn_act_train_backward"
+    _bn_check(name, (("grad_y", grad_y), ("x", x), ("y", y), ("weight", weight), ("save_mean", save_mean), ("save_invstd", save_invstd)))
+    if x.dim() != 4 or y.shape != x.shape or _hip.lib().m3d_bn_act_train_workspace_bytes(*x.shape) < 0:
+        raise RuntimeError("%s: x and y must be [B, C, H, W] of one supported shape (got %s, %s)" % (name, tuple(x.shape), tuple(y.shape)))
+    for what, t in (("weight", weight), ("save_mean", save_mean), ("save_invstd", save_invstd)):
+        if tuple(t.shape) != (x.shape[1],):
+            raise RuntimeError("%s: %s must be [C = %d] (got %s)" % (name, what, x.shape[1], tuple(t.shape)))
+    return _bn_backward(grad_y, x.contiguous(), y.contiguous(), weight.detach().contiguous(), save_mean.contiguous(),
+                        save_invstd.contiguous(), slope, needs)
+
+
+class _BNActTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, momentum, eps, slope):
+        y, save_mean, save_invstd, xc, wc = _bn_forward(x, residual, weight, bias, running_mean, running_var, momentum, eps, slope)
+        ctx.slope = slope
+        ctx.save_for_backward(xc, y, wc, save_mean, save_invstd)              # two activation tensors: the input and the OUTPUT
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, y, weight, save_mean, save_invstd = ctx.saved_tensors
+        grads = _bn_backward(grad_y, x, y, weight, save_mean, save_invstd, ctx.slope, ctx.needs_input_grad[:4])
+        return grads + (None,) * 5
+
+
+def bn_act_train(x, residual, weight, bias, running_mean, running_var, momentum, eps, slope):
+    """BatchNorm2d with batch statistics (+ ``residual``, which may be None) + activation (``slope``: 0 ReLU, a LeakyReLU's
+    negative_slope, 1 none) as one operator, differentiable in x, residual, weight and bias: m3d_bn_act_train_forward with
+    m3d_bn_act_train_backward behind it.  float32 NCHW device tensors (made contiguous); ``running_mean`` / ``running_var`` are
+    updated in place.  A host tensor raises NotImplementedError, another dtype RuntimeError (the checks of ``bn_act_train_forward``);
+    no torch fallback."""
+    return _BNActTrain.apply(x, residual, weight, bias, running_mean, running_var, momentum, eps, slope)
+
+
 def rpn_targets(cls, prob, anchors, conf_vec, gt_table, feat_size):
     """compute_targets (lib/rpn_util.py:430-532) for a whole batch on the device: m3d_rpn_targets.  ``anchors`` float64 device
     [A, 9], ``conf_vec`` from ``host.loss.pack_conf``, ``gt_table`` from ``host.loss.pack_gts``; see host/loss.py."""

@@ -7,7 +7,8 @@ computed by the HIP engine.
 In training mode (``build(conf, 'train')`` / ``.train()``) with grad enabled ``RPN.forward(x)`` returns the reference's training
 5-tuple ``(cls, prob, bbox_2d, bbox_3d, feat_size)`` from a differentiable forward (host/train.py): the backbone, the heads and
 BatchNorm with batch statistics are torch layers, DCNv2 (DeformConv, shape_align, center_align) and the ANAB attention core are
-HIP operators with hand-written backwards (``ops.dcn_v2``, ``ops.anab_attention``).  ``net(x)`` -> ``RPN_3D_loss`` ->
+HIP operators with hand-written backwards (``ops.dcn_v2``, ``ops.anab_attention``); ``train.set_fused_batchnorm(net)`` (opt-in)
+turns the BatchNorm + residual + LeakyReLU sites into one more (``ops.bn_act_train``).  ``net(x)`` -> ``RPN_3D_loss`` ->
 ``loss.backward()`` -> ``optimizer.step()`` -> ``net.eval()`` runs on the device; ``train()`` drops the packed engine, so the
 next eval forward packs the stepped parameters.  Single device: ``nn.DataParallel`` replicas in training mode are not part of it,
 and ``compute_dtype`` selects the eval engine only."""

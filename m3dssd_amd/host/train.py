@@ -1,8 +1,10 @@
 """The differentiable forwards: what the modules run in training mode with grad enabled on a device tensor (the rule DCNv2 /
 DeformConv follow).  Custom blocks go through the HIP operators with a backward (``ops.dcn_v2``, ``ops.anab_attention``); everything
-else is the layers PyTorch-ROCm has, so their gradients are autograd's.  Eval mode and no-grad calls never come here: they keep
-the fused inference launches (host/standalone.py, engine.py)."""
+else is the layers PyTorch-ROCm has, so their gradients are autograd's -- except that ``set_fused_batchnorm`` (opt-in) sends every
+BatchNorm2d + residual add + LeakyReLU site through one HIP operator too (``ops.bn_act_train``).  Eval mode and no-grad calls
+never come here: they keep the fused inference launches (host/standalone.py, engine.py)."""
 import torch
+from torch import nn
 
 from .. import _hip, rpn_util
 from . import ops
@@ -85,29 +87,89 @@ def center_align_forward(mod, x, bbox_x, bbox_y, prob):
     return mod.align(x.contiguous(), offset.contiguous(), mask.repeat(1, kk, 1, 1)) + x
 
 
+# ---- BatchNorm (batch statistics) + residual + activation as one operator (opt-in) ------------------------------------------------
+def set_fused_batchnorm(net, flag=True):
+    """Turns the fused training operator (``ops.bn_act_train``: BatchNorm2d with batch statistics + residual add + LeakyReLU in two
+    launches forward, two backward) on or off for every BatchNorm2d below ``net``; the default is off.  Returns the number of
+    BatchNorm sites set -- in an RPN every one of them is reached by the training forward.  A site keeps its torch layers while its
+    BatchNorm is in eval mode (a frozen layer), has ``momentum=None``, no affine parameters or no running statistics, while its
+    input is not float32, and inside a ``torch.autocast`` region (where a float32 input is the exception)."""
+    n = 0
+    for m in net.modules():
+        if isinstance(m, nn.BatchNorm2d):
+            m.fused_train = bool(flag)
+            n += 1
+    return n
+
+
+def _act_slope(act):
+    """The slope of ``ops.bn_act_train`` that stands for the activation module (None: no activation), or None when it has none."""
+    if act is None:
+        return 1.0
+    if type(act) is nn.LeakyReLU:
+        return float(act.negative_slope) if 0.0 <= act.negative_slope <= 1.0 else None
+    if type(act) is nn.ReLU:
+        return 0.0
+    return None
+
+
+def _fused(bn, x):
+    return (getattr(bn, "fused_train", False) and bn.training and bn.momentum is not None and bn.affine and bn.track_running_stats
+            and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda"))
+
+
+def bn_act(bn, x, act=None, residual=None):
+    """``act(bn(x) + residual)`` (``act`` / ``residual`` may be None): the torch layers, or ``ops.bn_act_train`` where
+    ``set_fused_batchnorm`` asked for it and the site qualifies."""
+    if _fused(bn, x) and (residual is None or residual.dtype == torch.float32):
+        slope = _act_slope(act)
+        if slope is not None:
+            bn.num_batches_tracked.add_(1)                        # as nn.BatchNorm2d.forward in training mode
+            return ops.bn_act_train(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, slope)
+    out = bn(x)
+    if residual is not None:
+        out = out + residual
+    return out if act is None else act(out)
+
+
+def seq_forward(seq, x):
+    """``seq(x)`` for an nn.Sequential; with the fused operator on, each BatchNorm2d is taken together with the activation module
+    that follows it (base_layer, level0 / level1, Tree.project, DeformConv.actf, the RPN heads, bbox_z3d_gl).  The walk then calls
+    the members itself: forward hooks of the Sequential and of a fused BatchNorm2d / activation do not run; the other members' do."""
+    mods = list(seq)
+    if not any(isinstance(m, nn.BatchNorm2d) and getattr(m, "fused_train", False) for m in mods):
+        return seq(x)
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.BatchNorm2d):
+            act = mods[i + 1] if i + 1 < len(mods) and _act_slope(mods[i + 1]) is not None else None
+            x = bn_act(m, x, act)
+            i += 1 if act is None else 2
+        else:
+            x = m(x)
+            i += 1
+    return x
+
+
 # ---- DLA (model/pose_dla_dcn.py; the line ranges are in host/dla.py) ---------------------------------------------------------------
 def basic_block_forward(mod, x, residual=None):
     if residual is None:
         residual = x
-    out = mod.relu(mod.bn1(mod.conv1(x)))
-    out = mod.bn2(mod.conv2(out))
-    return mod.relu(out + residual)
+    out = bn_act(mod.bn1, mod.conv1(x), mod.relu)
+    return bn_act(mod.bn2, mod.conv2(out), mod.relu, residual)
 
 
 def bottleneck_forward(mod, x, residual=None):
     if residual is None:
         residual = x
-    out = mod.relu(mod.bn1(mod.conv1(x)))
-    out = mod.relu(mod.bn2(mod.conv2(out)))
-    out = mod.bn3(mod.conv3(out))
-    return mod.relu(out + residual)
+    out = bn_act(mod.bn1, mod.conv1(x), mod.relu)
+    out = bn_act(mod.bn2, mod.conv2(out), mod.relu)
+    return bn_act(mod.bn3, mod.conv3(out), mod.relu, residual)
 
 
 def root_forward(mod, *xs):
-    out = mod.bn(mod.conv(torch.cat(xs, 1)))
-    if mod.residual:
-        out = out + xs[0]
-    return mod.relu(out)
+    return bn_act(mod.bn, mod.conv(torch.cat(xs, 1)), mod.relu, xs[0] if mod.residual else None)
 
 
 def tree_forward(mod, x, residual=None, children=None):
@@ -115,7 +177,7 @@ def tree_forward(mod, x, residual=None, children=None):
     bottom = mod.downsample(x) if mod.downsample is not None else x
     # (a Tree of more than one level hands this to tree1, itself a Tree, which computes its own: the value is dropped, as in the
     # reference -- the BatchNorm of the projection still sees the batch)
-    residual = mod.project(bottom) if mod.project is not None else bottom
+    residual = seq_forward(mod.project, bottom) if mod.project is not None else bottom
     if mod.level_root:
         children.append(bottom)
     x1 = mod.tree1(x, residual)
@@ -127,9 +189,10 @@ def tree_forward(mod, x, residual=None, children=None):
 
 def dla_forward(mod, x):
     y = []
-    x = mod.base_layer(x)
+    x = seq_forward(mod.base_layer, x)
     for i in range(6):
-        x = getattr(mod, "level%d" % i)(x)
+        level = getattr(mod, "level%d" % i)
+        x = seq_forward(level, x) if i < 2 else level(x)
         y.append(x)
     return y
 
@@ -163,27 +226,27 @@ def rpn_forward(mod, x):
     B = x.shape[0]
     x = mod.base(x.float())
     assert x.shape[2] == mod.feat_size[0], "x.shape is {}".format(x.shape)
-    cls = mod.cls(x)
+    cls = seq_forward(mod.cls, x)
     fh, fw, A = cls.shape[2], cls.shape[3], mod.num_anchors
     cls = cls.view(B, mod.num_classes, fh * A, fw)
     prob = mod.softmax(cls)
     fg_prob = (1 - prob.detach()[:, 0, :, :]).view(B, A, fh, fw)
     feats = mod.shape_align(x, fg_prob) if mod.shape_align is not None else x
-    bbox_x, bbox_y = mod.bbox_x(feats), mod.bbox_y(feats)
+    bbox_x, bbox_y = seq_forward(mod.bbox_x, feats), seq_forward(mod.bbox_y, feats)
     if mod.center_align2d is not None:
         feats_align2d = mod.center_align2d(feats, bbox_x.detach(), bbox_y.detach(), fg_prob)
     else:
         feats_align2d = feats
-    bbox_w, bbox_h = mod.bbox_w(feats_align2d), mod.bbox_h(feats_align2d)
-    bbox_x3d, bbox_y3d = mod.bbox_x3d(feats), mod.bbox_y3d(feats)
+    bbox_w, bbox_h = seq_forward(mod.bbox_w, feats_align2d), seq_forward(mod.bbox_h, feats_align2d)
+    bbox_x3d, bbox_y3d = seq_forward(mod.bbox_x3d, feats), seq_forward(mod.bbox_y3d, feats)
     if mod.center_align3d is not None:
         feats_align3d = mod.center_align3d(feats, bbox_x3d.detach(), bbox_y3d.detach(), fg_prob)
     else:
         feats_align3d = feats
-    bbox_w3d, bbox_h3d = mod.bbox_w3d(feats_align3d), mod.bbox_h3d(feats_align3d)
-    bbox_l3d, bbox_rY3d = mod.bbox_l3d(feats_align3d), mod.bbox_rY3d(feats_align3d)
-    feats_gl = mod.bbox_z3d_gl(feats_align3d) if getattr(mod, "bbox_z3d_gl", None) is not None else feats_align3d
-    bbox_z3d = mod.bbox_z3d(feats_gl)
+    bbox_w3d, bbox_h3d = seq_forward(mod.bbox_w3d, feats_align3d), seq_forward(mod.bbox_h3d, feats_align3d)
+    bbox_l3d, bbox_rY3d = seq_forward(mod.bbox_l3d, feats_align3d), seq_forward(mod.bbox_rY3d, feats_align3d)
+    feats_gl = seq_forward(mod.bbox_z3d_gl, feats_align3d) if getattr(mod, "bbox_z3d_gl", None) is not None else feats_align3d
+    bbox_z3d = seq_forward(mod.bbox_z3d, feats_gl)
 
     def flat(t):
         return rpn_util.flatten_tensor(t.view(B, 1, fh * A, fw))
