@@ -284,16 +284,23 @@ typedef struct m3d_conv_bf16_desc {
     const void *wgt_wave;
 } m3d_conv_bf16_desc;
 int m3d_conv_bf16_forward(const m3d_conv_bf16_desc *d, m3d_stream_t stream);
-/* Which kernel m3d_conv_bf16_forward launches for `d` (profiling labels; no launch): 0 = implicit-GEMM tile
- * (bf16_conv_kernel), 1 = 3x3 halo tile of 8 x 16 pixels, 2 = 3x3 halo tile of 8 x 32 pixels (bf16_conv3x3_halo_kernel),
- * 3 / 4 = deformable 3x3 with the sampling window in LDS, 8 x 16 / 16 x 16 pixel patches (bf16_dcn_patch_kernel; the
- * implicit-GEMM kernel is launched behind it and recomputes, on the device, the tiles whose offsets do not fit),
- * 5 = 3x3 with 128 x 128 wave tiles (bf16_conv3x3_wide_kernel; needs wgt_wave),
- * 6 = deformable 1x1, 128 -> 128 channels, bf16 NHWC output (bf16_dcn1x1_kernel: center_align, feturealign_mgpu.py:48-99),
- * 8 = 3x3 64 -> 64 channels on maps that tile 8 x 32 pixels, persistent workgroups with the weights resident in LDS
- *     (bf16_conv3x3_c64_kernel: DLA level2). */
 /* Bytes of dcn_ws the LDS-patch DCNv2 kernel needs for N x Ho x Wo output pixels (one flag word per pixel tile; 0 = the map does not tile). */
 long long m3d_conv_bf16_dcn_ws_bytes(int N, int Ho, int Wo);
+/* The kernel m3d_conv_bf16_forward launches for `d`, as m3d_conv_bf16_variant names it (profiling labels; no launch; -1 for a null
+ * descriptor).  Tests and tools pin the numbers; 7 belonged to a retired kernel and stays unused. */
+enum {
+    M3D_BF16_CONV_IGEMM = 0,       /* implicit-GEMM tile (bf16_conv_kernel)                                                     */
+    M3D_BF16_CONV_HALO16 = 1,      /* 3x3 halo tile of 8 x 16 pixels (bf16_conv3x3_halo_kernel)                                 */
+    M3D_BF16_CONV_HALO32 = 2,      /* 3x3 halo tile of 8 x 32 pixels (bf16_conv3x3_halo_kernel)                                 */
+    M3D_BF16_CONV_DCN_PATCH8 = 3,  /* deformable 3x3 with the sampling window in LDS, patches of 8 x 16 pixels ...               */
+    M3D_BF16_CONV_DCN_PATCH16 = 4, /* ... of 16 x 16 pixels (bf16_dcn_patch_kernel); behind either, the implicit-GEMM kernel is  */
+                                   /* launched and recomputes, on the device, the tiles whose offsets do not fit                */
+    M3D_BF16_CONV_WIDE = 5,        /* 3x3 with 128 x 128 wave tiles (bf16_conv3x3_wide_kernel; needs wgt_wave)                  */
+    M3D_BF16_CONV_DCN1X1 = 6,      /* deformable 1x1, 128 -> 128 channels, bf16 NHWC output (bf16_dcn1x1_kernel: center_align,  */
+                                   /* feturealign_mgpu.py:48-99)                                                                */
+    M3D_BF16_CONV_C64 = 8          /* 3x3 64 -> 64 channels on maps that tile 8 x 32 pixels, persistent workgroups with the     */
+                                   /* weights resident in LDS (bf16_conv3x3_c64_kernel: DLA level2)                             */
+};
 int m3d_conv_bf16_variant(const m3d_conv_bf16_desc *d);
 
 /* Entry of a DLA tree of the bf16 path in one launch (model/pose_dla_dcn.py:314-327, :107-121): bottom = MaxPool2d(2, 2)(x) (written

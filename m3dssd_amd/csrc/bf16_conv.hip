@@ -595,10 +595,9 @@ static int ilog2_exact(int v)
     return (1 << l) == v ? l : -1;
 }
 
-// Which kernel m3d_conv_bf16_forward runs for a descriptor (m3d_conv_bf16_variant: 3 / 4 = LDS-patch DCNv2 8 / 16 rows, 5 = wave tile,
-// 6 = the 1x1 DCNv2 kernel, 8 = the persistent 64 -> 64 kernel): 0 = generic implicit-GEMM tile, 1 = halo tile 8 x 16 pixels / 4
-// waves, 2 = halo tile 8 x 32 pixels / 8 waves.  3x3 / stride 1 / pad 1 on a 64-multiple of channels goes to the halo-tile
-// kernel when its patches tile the map well.
+// The halo rule: 3x3 / stride 1 / pad 1 on a 64-multiple of channels goes to the halo-tile kernel when its patches tile the map
+// well.  -> M3D_BF16_CONV_HALO16 (8 x 16 pixels / 4 waves) or _HALO32 (8 x 32 pixels / 8 waves) with the patches of the grid in
+// *tiles, or M3D_BF16_CONV_IGEMM (the generic tile).  bn = channels per workgroup (128 / 64 / 32).
 // M3D_BF16_HALO: 0 = generic kernel everywhere, 1 = default choice, 2 = 128-pixel patches only, +16 = identity lane map
 // (A/B of the LDS bank-conflict fix).  tools/bf16_conv_bench.py, TFLOP/s generic -> 8x16 patch / 4 waves -> 8x32 patch /
 // 8 waves: 64->64 @96x320 403 -> 599 -> 664; 128->128 @48x160 543 -> 712 -> 792; 256->256 @24x80 634 -> 845 -> 854
@@ -608,13 +607,12 @@ static int halo_env()
     static const int v = m3d_env_int("M3D_BF16_HALO", 1);
     return v;
 }
-static int conv_bf16_variant(const m3d_conv_bf16_desc *d, long long *tiles)
+static int conv_halo_rule(const m3d_conv_bf16_desc *d, int bn, long long *tiles)
 {
     const int halo_on = halo_env() & 15;
-    const int bn = d->Cout_pad % 128 == 0 ? 128 : (d->Cout_pad % 64 == 0 ? 64 : 32);
     if (!halo_on || d->dcn_offmask || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->Cin % 64 != 0 ||
         d->groups != 1 || d->wgt_img_stride != 0)
-        return 0;
+        return M3D_BF16_CONV_IGEMM;
     const int ho = d->H, wo = d->W;
     const long long M = (long long)d->N * ho * wo;
     const long long t16 = (long long)cdiv(wo, 16) * cdiv(ho, 8) * d->N, t32 = (long long)cdiv(wo, 32) * cdiv(ho, 8) * d->N;
@@ -623,21 +621,36 @@ static int conv_bf16_variant(const m3d_conv_bf16_desc *d, long long *tiles)
     // 128-channel tiles: the 8 x 16 patch with 32-channel weight half-steps runs three workgroups per CU and beats the 8 x 32 /
     // 8-wave tile (128 -> 128 @ 48x160: 904 vs 792 TFLOP/s); 64-channel tiles: 8 x 32 / 8 waves (708 vs 668)
     const bool big = halo_on != 2 && bn == 64 && e32 >= 0.9 * e16 && t32 * (d->Cout_pad / bn) >= 1024;
-    if ((big ? e32 : e16) < 0.8) return 0;
-    if (tiles) *tiles = big ? t32 : t16;
-    return big ? 2 : 1;
+    if ((big ? e32 : e16) < 0.8) return M3D_BF16_CONV_IGEMM;
+    *tiles = big ? t32 : t16;
+    return big ? M3D_BF16_CONV_HALO32 : M3D_BF16_CONV_HALO16;
+}
+
+// The kernel that serves a descriptor, decided HERE and nowhere else: m3d_conv_bf16_variant reports .code, m3d_conv_bf16_forward
+// switches on it.  The first family that takes the descriptor wins, in this order: wave tile, 1x1 DCNv2, persistent 64 -> 64, halo
+// tile, LDS-patch DCNv2, generic tile.  (Every *_applicable is also the backstop of its own launcher.)
+struct Bf16Route {
+    int code;              // M3D_BF16_CONV_*
+    int bn;                // generic and halo tiles: output channels per workgroup, 128 / 64 / 32
+    long long halo_tiles;  // halo tiles: pixel patches of the grid
+    int patch_rows;        // LDS-patch DCNv2: rows of the pixel patch, 8 / 16
+};
+static Bf16Route conv_bf16_route(const m3d_conv_bf16_desc *d)
+{
+    Bf16Route r = {M3D_BF16_CONV_IGEMM, d->Cout_pad % 128 == 0 ? 128 : (d->Cout_pad % 64 == 0 ? 64 : 32), 0, 0};
+    if (conv_wide_applicable(d)) r.code = M3D_BF16_CONV_WIDE;               // 128 x 128 wave tiles (bf16_conv_wide.hip)
+    else if (dcn1x1_applicable(d)) r.code = M3D_BF16_CONV_DCN1X1;           // 1x1 DCNv2 128 -> 128 (center_align; bf16_dcn1x1.hip)
+    else if (conv_c64_applicable(d)) r.code = M3D_BF16_CONV_C64;            // 3x3 64 -> 64, persistent workgroups (level2; bf16_conv_c64.hip)
+    else r.code = conv_halo_rule(d, r.bn, &r.halo_tiles);
+    if (r.code != M3D_BF16_CONV_IGEMM) return r;
+    // DCNv2 3x3 with an fp16 weight copy and a flag workspace: the LDS-patch kernel (bf16_dcn_patch.hip)
+    r.patch_rows = dcn_patch_variant(d);
+    if (r.patch_rows) r.code = r.patch_rows == 16 ? M3D_BF16_CONV_DCN_PATCH16 : M3D_BF16_CONV_DCN_PATCH8;
+    return r;
 }
 extern "C" int m3d_conv_bf16_variant(const m3d_conv_bf16_desc *d)
 {
-    if (!d) return -1;
-    if (d->dcn_offmask) {
-        if (dcn1x1_applicable(d)) return 6;
-        const int pv = dcn_patch_variant(d);
-        return pv == 16 ? 4 : (pv == 8 ? 3 : 0);
-    }
-    if (conv_wide_applicable(d)) return 5;
-    if (conv_c64_applicable(d)) return 8;
-    return conv_bf16_variant(d, nullptr);
+    return d ? conv_bf16_route(d).code : -1;
 }
 
 extern "C" int m3d_conv_bf16_forward(const m3d_conv_bf16_desc *d, m3d_stream_t stream)
@@ -675,28 +688,29 @@ extern "C" int m3d_conv_bf16_forward(const m3d_conv_bf16_desc *d, m3d_stream_t s
     a.pad = d->pad; a.Ho = ho; a.Wo = wo; a.HoWo = ho * wo; a.M = (int)M;
     a.out_cs = d->out_cs; a.res_cs = d->res_cs; a.om_cs = d->dcn_om_cs;
     a.out_mode = d->out_mode; a.res_mode = d->res_mode; a.act = d->act; a.sigmoid_from = d->sigmoid_from;
-    const int bn = d->Cout_pad % 128 == 0 ? 128 : (d->Cout_pad % 64 == 0 ? 64 : 32);
+    const Bf16Route route = conv_bf16_route(d);
+    const int bn = route.bn;
     a.tiles_m = cdiv(M, 128); a.tiles_n = d->Cout_pad / bn;
     a.uniform_k = (d->Cin % 64 == 0 && K % 64 == 0) ? 1 : 0;
     a.gate = nullptr; a.gate_th = a.gate_tpx = a.gate_tpy = 0;
+    a.lane_perm = (halo_env() & 16) ? 0 : 1;
 #ifdef BF16_TRACE
     a.trace = g_bf16_trace;
 #endif
     const dim3 grid(a.tiles_m * a.tiles_n, d->groups), block(256);
     hipStream_t st = (hipStream_t)stream;
     const bool deform = d->dcn_offmask != nullptr;
-    if (conv_wide_applicable(d)) return launch_conv_wide(a, d, st);      // 128 x 128 wave tiles (bf16_conv_wide.hip)
-    if (deform && dcn1x1_applicable(d)) return launch_dcn1x1(a, d, st);  // 1x1 DCNv2 128 -> 128 (center_align; bf16_dcn1x1.hip)
-    if (conv_c64_applicable(d)) return launch_conv_c64(a, d, st);        // 3x3 64 -> 64, persistent workgroups (level2; bf16_conv_c64.hip)
-    long long htiles = 0;
-    const int variant = conv_bf16_variant(d, &htiles);
-    a.lane_perm = (halo_env() & 16) ? 0 : 1;
-    if (variant) {
-        a.tiles_m = (int)htiles;
+    switch (route.code) {
+    case M3D_BF16_CONV_WIDE: return launch_conv_wide(a, d, st);
+    case M3D_BF16_CONV_DCN1X1: return launch_dcn1x1(a, d, st);
+    case M3D_BF16_CONV_C64: return launch_conv_c64(a, d, st);
+    case M3D_BF16_CONV_HALO16:
+    case M3D_BF16_CONV_HALO32: {
+        a.tiles_m = (int)route.halo_tiles;
         const dim3 hgrid(a.tiles_m * a.tiles_n);
 #define HLAUNCH(BN_, TW_, BM_, WV_, WK_) hipLaunchKernelGGL((bf16_conv3x3_halo_kernel<BN_, TW_, BM_, WV_, WK_>), hgrid, dim3(WV_ * 64), 0, st, a)
         static const int wk32 = m3d_env_int("M3D_BF16_HALO_WK", 32) != 64;   // =64: 64-channel weight steps for the 8 x 16 tile too (A/B)
-        if (variant == 2) HLAUNCH(64, 32, 256, 8, 64);
+        if (route.code == M3D_BF16_CONV_HALO32) HLAUNCH(64, 32, 256, 8, 64);
         else if (bn == 128) { if (wk32) HLAUNCH(128, 16, 128, 4, 32); else HLAUNCH(128, 16, 128, 4, 64); }
         else if (bn == 64) HLAUNCH(64, 16, 128, 4, 64);
         else HLAUNCH(32, 16, 128, 4, 64);
@@ -704,10 +718,11 @@ extern "C" int m3d_conv_bf16_forward(const m3d_conv_bf16_desc *d, m3d_stream_t s
         M3D_LAUNCH_CHECK();
         return M3D_OK;
     }
-    // DCNv2 3x3 with an fp16 weight copy and a flag workspace: the LDS-patch kernel, one word per patch tile ("my window did not fit"),
-    // and this file's implicit-GEMM kernel behind it for the tiles that carry the flag (bf16_dcn_patch.hip)
-    const int pvar = deform ? dcn_patch_variant(d) : 0;
-    if (pvar) {
+    case M3D_BF16_CONV_DCN_PATCH8:
+    case M3D_BF16_CONV_DCN_PATCH16: {
+        // the LDS-patch kernel, one word per patch tile ("my window did not fit"), and this file's implicit-GEMM kernel behind it
+        // for the tiles that carry the flag (bf16_dcn_patch.hip)
+        const int pvar = route.patch_rows;
         int rc;
         // a fallback workgroup recomputes its WHOLE 128-pixel tile when any patch tile it touches carries the flag: pixels the patch
         // kernel already wrote are written a second time (with this kernel's rounding), which is idempotent only while the
@@ -715,6 +730,12 @@ extern "C" int m3d_conv_bf16_forward(const m3d_conv_bf16_desc *d, m3d_stream_t s
         M3D_REQUIRE(d->res == nullptr || d->res != d->out, "m3d_conv_bf16_forward: the LDS-patch DCNv2 path needs res != out");
         if ((rc = launch_dcn_patch(a, d, pvar, st))) return rc;
         a.gate = (const unsigned *)d->dcn_ws; a.gate_th = pvar; a.gate_tpx = d->Wo / 16; a.gate_tpy = d->Ho / pvar;
+        [[fallthrough]];     // the gated implicit-GEMM launch
+    }
+    case M3D_BF16_CONV_IGEMM:
+        break;
+    default:
+        M3D_REQUIRE(false, "conv_bf16: route %d has no launcher", route.code);
     }
 #define LAUNCH(BN_, DF_) hipLaunchKernelGGL((bf16_conv_kernel<BN_, DF_>), grid, block, 0, st, a)
     if (bn == 128) { if (deform) LAUNCH(128, true); else LAUNCH(128, false); }

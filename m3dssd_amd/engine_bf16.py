@@ -218,6 +218,65 @@ class PackedBf16:
         self.has_affine = (bias is not None) or (bn is not None)
 
 
+def conv_bf16_desc(name, x, out=None, wgt=None, kpad=None, cout=None, cout_pad=None, kh=1, kw=1, stride=1, pad=0, scale=None, shift=None,
+                   act=0, res=None, res_mode=0, sigmoid_from=-1, om=None, out_mode=0, planar=None, wgt_img_stride=0, groups=1,
+                   in_goff=0, wgt_goff=0, out_goff=0, ss_goff=0, cin=None, wgt_f16=None, wgt_wave=None):
+    """The m3d_conv_bf16_desc of one launch.  x: View16 (bf16); out: View16 (bf16 or fp32 NHWC) or planar = (tensor, img_stride,
+    channel offset) for the fp32 planar staging of the head outputs; wgt: packed weights (tensor or address); om = the offset / mask
+    map of a deformable layer.  wgt_f16 (deformable) / wgt_wave (plain): the weight forms of the LDS-patch DCNv2 kernel and of the
+    128 x 128 wave-tile kernel, for the library to use where it finds them applicable."""
+    d = ConvBf16Desc()
+    d.inp, d.in_cs, d.N, d.H, d.W, d.Cin = x.ptr, x.cs, x.n, x.h, x.w, (x.c if cin is None else cin)
+    d.wgt, d.wgt_img_stride = wgt.data_ptr() if hasattr(wgt, "data_ptr") else wgt, wgt_img_stride
+    d.Cout, d.Cout_pad, d.Kpad = cout, cout_pad, kpad
+    d.kh, d.kw, d.stride, d.pad = kh, kw, stride, pad
+    d.Ho = (x.h + 2 * pad - kh) // stride + 1
+    d.Wo = (x.w + 2 * pad - kw) // stride + 1
+    if planar is not None:
+        t, img_stride, ch_off = planar
+        d.out, d.out_mode, d.out_img_stride = t.data_ptr() + 4 * ch_off * d.Ho * d.Wo, 2, img_stride
+    else:
+        assert out.h == d.Ho and out.w == d.Wo, (name, out.h, out.w, d.Ho, d.Wo)
+        d.out, d.out_cs, d.out_mode = out.ptr, out.cs, out_mode
+    if scale is not None:
+        d.scale = scale.data_ptr()
+    if shift is not None:
+        d.shift = shift.data_ptr()
+    if res is not None:
+        d.res, d.res_cs, d.res_mode = res.ptr, res.cs, res_mode
+    d.act, d.sigmoid_from = act, sigmoid_from
+    if om is not None:
+        d.dcn_offmask, d.dcn_om_cs = om.ptr, om.cs
+        if wgt_f16 is not None:
+            d.wgt_f16 = wgt_f16.data_ptr()
+    elif wgt_wave is not None:
+        d.wgt_wave = wgt_wave.data_ptr()
+    d.groups, d.in_group_off, d.wgt_group_off, d.out_group_off, d.ss_group_off = groups, in_goff, wgt_goff, out_goff, ss_goff
+    return d
+
+
+_C = _hip.CONSTANTS          # the header's #defines and enumerators
+# m3d_conv_bf16_variant's code -> the kind of the op; bn = the output channels per workgroup (bench.py and profiles/ key on the strings)
+BF16_CONV_KINDS = {
+    _C["M3D_BF16_CONV_IGEMM"]: "bf16_conv<{bn}{deform}>",
+    _C["M3D_BF16_CONV_HALO16"]: "bf16_halo<{bn},16>",
+    _C["M3D_BF16_CONV_HALO32"]: "bf16_halo<{bn},32>",
+    _C["M3D_BF16_CONV_DCN_PATCH8"]: "bf16_dcn_patch<8>",       # LDS-patch DCNv2 (+ the gated implicit-GEMM fallback behind it)
+    _C["M3D_BF16_CONV_DCN_PATCH16"]: "bf16_dcn_patch<16>",
+    _C["M3D_BF16_CONV_WIDE"]: "bf16_wide<128,128>",            # 3x3 with 128-pixel x 128-channel wave tiles
+    _C["M3D_BF16_CONV_DCN1X1"]: "bf16_dcn1x1",                 # 1x1 DCNv2 128 -> 128 (center_align; csrc/bf16_dcn1x1.hip)
+    _C["M3D_BF16_CONV_C64"]: "bf16_c64",                       # 3x3 64 -> 64, persistent workgroups, weights resident in LDS (level2)
+}
+
+
+def conv_bf16_kind(code, cout_pad, deform):
+    """The kind of a conv op from the kernel the library names for its descriptor (m3d_conv_bf16_variant)."""
+    if code not in BF16_CONV_KINDS:
+        raise ValueError("m3d_conv_bf16_variant answered %r: no kernel of this engine's labels" % (code,))
+    bn = 128 if cout_pad % 128 == 0 else (64 if cout_pad % 64 == 0 else 32)
+    return BF16_CONV_KINDS[code].format(bn=bn, deform=",deform" if deform else "")
+
+
 class EngineBF16(Engine):
     compute_dtype = "bf16"
 
@@ -259,62 +318,22 @@ class EngineBF16(Engine):
             plan.named[name] = v
         return v
 
-    def _conv16(self, plan, name, x, out=None, wgt=None, kpad=None, cout=None, cout_pad=None, kh=1, kw=1, stride=1, pad=0,
-                scale=None, shift=None, act=0, res=None, res_mode=0, sigmoid_from=-1, om=None, out_mode=0, planar=None,
-                wgt_img_stride=0, groups=1, in_goff=0, wgt_goff=0, out_goff=0, ss_goff=0, cin=None, flops_cin=None, wgt_f16=None, wgt_wave=None):
-        """One m3d_conv_bf16_forward launch appended to the plan.  x: View16 (bf16); out: View16 (bf16 or fp32 NHWC) or
-        planar = (tensor, img_stride, channel offset) for the fp32 planar staging of the head outputs."""
-        d = ConvBf16Desc()
-        cin = x.c if cin is None else cin
-        d.inp, d.in_cs, d.N, d.H, d.W, d.Cin = x.ptr, x.cs, x.n, x.h, x.w, cin
-        d.wgt, d.wgt_img_stride = wgt.data_ptr() if hasattr(wgt, "data_ptr") else wgt, wgt_img_stride
-        d.Cout, d.Cout_pad, d.Kpad = cout, cout_pad, kpad
-        d.kh, d.kw, d.stride, d.pad = kh, kw, stride, pad
-        d.Ho = (x.h + 2 * pad - kh) // stride + 1
-        d.Wo = (x.w + 2 * pad - kw) // stride + 1
-        if planar is not None:
-            t, img_stride, ch_off = planar
-            d.out, d.out_mode, d.out_img_stride = t.data_ptr() + 4 * ch_off * d.Ho * d.Wo, 2, img_stride
-        else:
-            assert out.h == d.Ho and out.w == d.Wo, (name, out.h, out.w, d.Ho, d.Wo)
-            d.out, d.out_cs, d.out_mode = out.ptr, out.cs, out_mode
-        if scale is not None:
-            d.scale = scale.data_ptr()
-        if shift is not None:
-            d.shift = shift.data_ptr()
-        plan.keep += [t for t in (scale, shift, wgt) if hasattr(t, "data_ptr")]
-        if res is not None:
-            d.res, d.res_cs, d.res_mode = res.ptr, res.cs, res_mode
-        d.act, d.sigmoid_from = act, sigmoid_from
-        if om is not None:
-            d.dcn_offmask, d.dcn_om_cs = om.ptr, om.cs
-            if wgt_f16 is not None:
-                # LDS-patch DCNv2 kernel (csrc/bf16_dcn_patch.hip): fp16 copy of the packed weights + one flag word per pixel tile; the
-                # library decides per tile, on the device, whether the sampling window fits
-                ws = torch.zeros(max(256, self.L.m3d_conv_bf16_dcn_ws_bytes(x.n, out.h, out.w) // 4), device=self.device, dtype=torch.int32)
-                plan.keep += [wgt_f16, ws]
-                d.wgt_f16, d.dcn_ws, d.dcn_ws_bytes = wgt_f16.data_ptr(), ws.data_ptr(), ws.numel() * 4
-        elif wgt_wave is not None:
-            plan.keep.append(wgt_wave)       # 128 x 128 wave-tile kernel (csrc/bf16_conv_wide.hip) where the library finds it applicable
-            d.wgt_wave = wgt_wave.data_ptr()
-        d.groups, d.in_group_off, d.wgt_group_off, d.out_group_off, d.ss_group_off = groups, in_goff, wgt_goff, out_goff, ss_goff
+    def _conv16(self, plan, name, x, out=None, flops_cin=None, **layer):
+        """One m3d_conv_bf16_forward launch appended to the plan: its descriptor (conv_bf16_desc takes `layer`), the patch workspace
+        where the layer brings the LDS-patch kernel's weights, and the kind of the kernel the library names for it.
+        flops_cin: the input channels the FLOPs count (default: the descriptor's)."""
         L = self.L
+        d = conv_bf16_desc(name, x, out, **layer)
+        plan.keep += [t for t in (layer.get(k) for k in ("scale", "shift", "wgt", "wgt_f16", "wgt_wave")) if hasattr(t, "data_ptr")]
+        if d.wgt_f16:
+            # LDS-patch DCNv2 kernel (csrc/bf16_dcn_patch.hip): fp16 copy of the packed weights + one flag word per pixel tile; the
+            # library decides per tile, on the device, whether the sampling window fits
+            ws = torch.zeros(max(256, L.m3d_conv_bf16_dcn_ws_bytes(d.N, d.Ho, d.Wo) // 4), device=self.device, dtype=torch.int32)
+            plan.keep.append(ws)
+            d.dcn_ws, d.dcn_ws_bytes = ws.data_ptr(), ws.numel() * 4
         ref = ctypes.byref(d)
-        flops = 2.0 * x.n * d.Ho * d.Wo * cout * kh * kw * (flops_cin if flops_cin is not None else cin) * groups
-        bn = 128 if cout_pad % 128 == 0 else (64 if cout_pad % 64 == 0 else 32)
-        variant = L.m3d_conv_bf16_variant(ref)          # which kernel the library runs for this descriptor
-        if variant == 5:
-            kind = "bf16_wide<128,128>"                           # 3x3 with 128-pixel x 128-channel wave tiles
-        elif variant == 8:
-            kind = "bf16_c64"                                     # 3x3 64 -> 64, persistent workgroups, weights resident in LDS (level2)
-        elif variant == 6:
-            kind = "bf16_dcn1x1"                                  # 1x1 DCNv2 128 -> 128 (center_align; csrc/bf16_dcn1x1.hip)
-        elif variant >= 3:
-            kind = "bf16_dcn_patch<%d>" % (8 * (variant - 2))     # LDS-patch DCNv2 (+ the gated implicit-GEMM fallback behind it)
-        elif variant:
-            kind = "bf16_halo<%d,%d>" % (bn, 16 * variant)
-        else:
-            kind = "bf16_conv<%d%s>" % (bn, ",deform" if om is not None else "")
+        flops = 2.0 * d.N * d.Ho * d.Wo * d.Cout * d.kh * d.kw * (flops_cin if flops_cin is not None else d.Cin) * d.groups
+        kind = conv_bf16_kind(L.m3d_conv_bf16_variant(ref), d.Cout_pad, deform=d.dcn_offmask is not None)    # the library decides, this labels
         plan.ops.append((name, kind, flops, lambda st: _hip.check(L.m3d_conv_bf16_forward(ref, st)), d))
 
     def _pconv(self, plan, name, pc, x, out, stride=1, pad=0, act=0, res=None, res_mode=0, sigmoid_from=-1, om=None, out_mode=0,

@@ -749,6 +749,11 @@ def test_cabi_scratch_contents_do_not_matter(entry):
 
 
 # ------------------------------------------------------------------------------------ C ABI: NaN in declared padding
+# n, c, h, w, co of the case of each variant (tests/test_bf16_conv_route_host.py asks the library about them without a GPU)
+BF16_CONV_SHAPES = {0: (2, 64, 12, 20, 64), 1: (2, 64, 15, 31, 64), 2: (128, 64, 24, 96, 64), 5: (1, 64, 8, 16, 128),
+                    8: (8, 64, 128, 256, 64), 6: (1, 128, 9, 13, 128), 3: (3, 64, 8, 16, 128), 4: (1, 32, 16, 16, 100)}
+
+
 def _bf16_conv_args(variant):
     """One case per bf16 convolution variant (m3d_conv_bf16_variant), the smallest of its test in tests/test_gpu_bf16.py, with
     in_cs = Cin + 8: the eight channels between Cin and in_cs belong to nobody."""
@@ -759,18 +764,17 @@ def _bf16_conv_args(variant):
         return (_r(torch.randn(n, c, h, w, generator=g)), _r(torch.randn(co, c, 3, 3, generator=g) / (c * 9) ** 0.5),
                 torch.randn(co, generator=g) * 0.1)
     if variant in (0, 1, 2, 5, 8):
-        n, c, h, w, co = {0: (2, 64, 12, 20, 64), 1: (2, 64, 15, 31, 64), 2: (128, 64, 24, 96, 64), 5: (1, 64, 8, 16, 128),
-                          8: (8, 64, 128, 256, 64)}[variant]
+        n, c, h, w, co = BF16_CONV_SHAPES[variant]
         x, wt, b = plain(n, c, h, w, co)
         return (x, wt, b, None, 1, 1, 1), dict(out_mode=1 if variant == 2 else 0, in_cs=c + 8, variant=variant, wide=variant == 5)
     if variant == 6:                                                  # 1x1 DCNv2 128 -> 128 on a ragged single tile
-        n, c, h, w = 1, 128, 9, 13
+        n, c, h, w, _ = BF16_CONV_SHAPES[variant]
         x = _r(torch.randn(n, c, h, w, generator=g) + 0.5)
         wt, b = _r(torch.randn(c, c, 1, 1, generator=g) / c ** 0.5), torch.randn(c, generator=g) * 0.1
         om = torch.cat([torch.randn(n, 2, h, w, generator=g) * 2.5, torch.rand(n, 1, h, w, generator=g), torch.zeros(n, 1, h, w)],
                        1).permute(0, 2, 3, 1).contiguous()
         return (x, wt, b, None, 1, 0, 0), dict(om=om, in_cs=c + 8, variant=6)
-    shape, std = {3: ((3, 64, 8, 16, 128), 0.3), 4: ((1, 32, 16, 16, 100), 1.0)}[variant]
+    shape, std = BF16_CONV_SHAPES[variant], {3: 0.3, 4: 1.0}[variant]
     x, wt, b, off, m, om = _dcn_case(shape, std, 1, None)
     return (x, wt, b, None, 1, 1, 0), dict(om=om, in_cs=shape[1] + 8, variant=variant, patch=True)
 

@@ -53,11 +53,11 @@ torch.cuda.synchronize()
 ms = e0.elapsed_time(e1)
 KT = kpad // 64
 t = trace.cpu().numpy().reshape(grid, 160)
-variant = L.m3d_conv_bf16_variant(ctypes.byref(d))
-if variant:
-    grid = ((H + 7) // 8) * ((W + 16 * variant - 1) // (16 * variant)) * B * (wp.shape[0] // bn)
+halo_tw = {_hip.CONSTANTS["M3D_BF16_CONV_HALO16"]: 16, _hip.CONSTANTS["M3D_BF16_CONV_HALO32"]: 32}.get(L.m3d_conv_bf16_variant(ctypes.byref(d)))
+if halo_tw:
+    grid = ((H + 7) // 8) * ((W + halo_tw - 1) // halo_tw) * B * (wp.shape[0] // bn)
     t = t[:grid]
-    print("halo-tile kernel, 8 x %d patches" % (16 * variant))
+    print("halo-tile kernel, 8 x %d patches" % halo_tw)
 fl = 2.0 * B * H * W * cout * k * k * cin
 n = min(KT, 38)
 dur = t[:, 1 + 4 * n] - t[:, 0] if 1 + 4 * n < 160 else t[:, 1 + 4 * (n - 1)] - t[:, 0]
