@@ -485,6 +485,8 @@ static int choose_tile(const m3d_conv_desc *d, TileChoice *t)
     static const int fbn = m3d_env_int("M3D_FORCE_BN", 0);            // tuning knob (experiments only)
     if (fbn && t->bk == 32 && t->bn > fbn && !d->out_nchw) t->bn = fbn;
     if (d->wgt_img_stride && (d->Ho * d->Wo) % t->bm != 0) {
+        // the 32-channel tiles are instantiated with 128 rows only: a 128-row tile over two images would take the weights of the first
+        if (t->bn < 64) return -1;
         t->bm = 64;
         if ((d->Ho * d->Wo) % 64 != 0) return -1;
     }
@@ -495,7 +497,7 @@ extern "C" int m3d_conv2d_splitk_plan(const m3d_conv_desc *d, int *splits, long 
 {
     TileChoice t;
     M3D_REQUIRE(d && splits && ws_bytes, "conv2d_splitk_plan: null pointer");
-    M3D_REQUIRE(choose_tile(d, &t) == 0, "per-image weights need Ho*Wo %% 64 == 0");
+    M3D_REQUIRE(choose_tile(d, &t) == 0, "per-image weights need Ho*Wo %% 64 == 0 (%% 128 on the 32-channel tiles)");
     int kt_per;
     *splits = choose_split(d, t, &kt_per);
     *ws_bytes = *splits > 1 ? (long long)*splits * d->N * d->Ho * d->Wo * d->Cout_pad * 4 : 0;
@@ -505,7 +507,7 @@ extern "C" int m3d_conv2d_splitk_plan(const m3d_conv_desc *d, int *splits, long 
 extern "C" int m3d_conv2d_tile(const m3d_conv_desc *d, int *bm, int *bn, int *bk, int *grid)
 {
     TileChoice t;
-    M3D_REQUIRE(choose_tile(d, &t) == 0, "per-image weights need Ho*Wo %% 64 == 0");
+    M3D_REQUIRE(choose_tile(d, &t) == 0, "per-image weights need Ho*Wo %% 64 == 0 (%% 128 on the 32-channel tiles)");
     const long long M = (long long)d->N * d->Ho * d->Wo;
     *bm = t.bm; *bn = t.bn; *bk = t.bk;
     *grid = cdiv(M, t.bm) * cdiv(d->Cout_pad, t.bn);
@@ -545,7 +547,7 @@ extern "C" int m3d_conv2d_forward(const m3d_conv_desc *d, m3d_stream_t stream_)
     if (d->out_nchw) M3D_REQUIRE(!d->res, "planar output does not take a residual");
 
     TileChoice t;
-    M3D_REQUIRE(choose_tile(d, &t) == 0, "per-image weights need Ho*Wo %% 64 == 0");
+    M3D_REQUIRE(choose_tile(d, &t) == 0, "per-image weights need Ho*Wo %% 64 == 0 (%% 128 on the 32-channel tiles)");
 
     IgemmArgs a;
     a.in = d->in; a.wgt = d->wgt; a.out = d->out; a.scale = d->scale; a.shift = d->shift; a.res = d->res;

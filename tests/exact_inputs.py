@@ -171,12 +171,13 @@ def _all_pixels(n, ho, wo):
     return nb.reshape(-1), yy.reshape(-1), xx.reshape(-1)
 
 
-def dcn_corner_terms(ops, pix=None, rnd=EXACT):
+def dcn_corner_terms(ops, pix=None, rnd=EXACT, dil=1):
     """The sampling of DCNv2 at the output pixels `pix` = (image, row, column index vectors; default: all, image-major): for
     every pixel P, tap t and deformable group the four corner weights (mask folded in) cw [P, dg, KK, 4] and the four corner
     values cv [P, KK, 4, C] (0 where the corner lies outside the image or the whole sample does).  Rules of
     dcn_v2_im2col_cuda.cu:129-178: the sample counts only if h_im > -1, w_im > -1, h_im < H, w_im < W (strict); a corner counts only
-    if its row and column are inside the image; weights (1-lh)(1-lw), (1-lh) lw, lh (1-lw), lh lw."""
+    if its row and column are inside the image; weights (1-lh)(1-lw), (1-lh) lw, lh (1-lw), lh lw.  `dil`: the dilation of the tap
+    grid (tap (i, j) sits at (i * dil, j * dil) before its offset is added)."""
     x, off, mask = ops["x"].to(F64), ops["off"].to(F64), ops["mask"].to(F64)
     n, c, h, w = x.shape
     kh, kw = ops["weight"].shape[2:]
@@ -188,8 +189,8 @@ def dcn_corner_terms(ops, pix=None, rnd=EXACT):
     m = mask[nb, :, yy, xx].view(P, dg, KK)
     ti = (torch.arange(KK) // kw).view(1, 1, KK).to(F64)
     tj = (torch.arange(KK) % kw).view(1, 1, KK).to(F64)
-    h_im = (yy * stride - pad).view(P, 1, 1).to(F64) + ti + o[..., 0]
-    w_im = (xx * stride - pad).view(P, 1, 1).to(F64) + tj + o[..., 1]
+    h_im = (yy * stride - pad).view(P, 1, 1).to(F64) + ti * dil + o[..., 0]
+    w_im = (xx * stride - pad).view(P, 1, 1).to(F64) + tj * dil + o[..., 1]
     inside = (h_im > -1) & (w_im > -1) & (h_im < h) & (w_im < w)
     hl, wl = torch.floor(h_im), torch.floor(w_im)
     lh, lw = h_im - hl, w_im - wl
