@@ -104,7 +104,8 @@ const char *m3d_last_error(void);
  *                  m3d_dcn_v2_backward_det_workspace_bytes_bf16 (additive);
  *                  m3d_optim_prepare, m3d_optim_step, m3d_optim_state_bytes (additive);
  *                  m3d_bn_act_train_forward, m3d_bn_act_train_backward, m3d_bn_act_train_workspace_bytes,
- *                  m3d_bn_act_train_chunks (additive). */
+ *                  m3d_bn_act_train_chunks (additive);
+ *                  m3d_topk_decode_planar_2d, m3d_post_rows, m3d_fill_post_3d (additive). */
 #define M3D_ABI_VERSION 5
 int m3d_abi_version(void);
 /* "file:sha256[:16];file:sha256[:16];..." of the sources (csrc .hip / .h files and this header) the loaded library was built from. */
@@ -1120,6 +1121,28 @@ int m3d_nms_sorted_dev(const float *boxes_dev, int B, int n, int box_stride, flo
  * message of the multi-GPU all-gather; counts [B] (optional) gets min(num_keep, post). */
 int m3d_select_post(const float *aboxes /*[B][n][14]*/, const int *keep /*[B][n]*/, const int *num_keep /*[B]*/, int B, int n,
                     int post, float *block, int *counts, m3d_stream_t stream);
+/* The 3-D size, depth and angle of a row (columns 8..12: z3d, w3d, h3d, l3d, ry3d) are read by nobody before the row is among
+ * the `post` rows per image that m3d_select_post copies (the NMS reads columns 0..4).  Three entry points let the heads behind
+ * those columns run at the pixels of the selected rows only:
+ *   m3d_topk_decode_planar_2d: m3d_topk_decode_planar (same arguments, workspace and limits) that does not read box planes 6..10
+ *     and writes +0 to columns 8..12; rows_out is required.  Every other column and rows_out are bit-equal to the full decode.
+ *   m3d_post_rows: rows_out [B][n] of that decode, keep [B][n] / num_keep [B] of the NMS -> rows: the distinct pixels
+ *     b*HW + rows_out[b][keep[b][j]] % HW of the first min(num_keep[b], post) kept rows of every image, ascending (the list
+ *     m3d_need_rows writes, for m3d_head_mlp_forward_rows / m3d_anab_attend_f32_rows), n_rows their number on the device.
+ *     rows holds min(B*post, B*HW) entries; entries at or past *n_rows are not written.  One launch whatever the data
+ *     (graph-capturable), nothing read back, nothing carried over between calls.  B*post <= 4096, else M3D_E_ARG.
+ *   m3d_fill_post_3d: columns 8..12 of rows [0, min(counts[b], post)) of block [B][post + 1][14] (as m3d_select_post wrote it
+ *     from the 2-D decode; counts: its counts) from box planes 6..10 at the staging row rows_out[b][keep[b][j]], with the
+ *     arithmetic of the full decode (the same bits).  Nothing else of the block is written. */
+int m3d_topk_decode_planar_2d(const unsigned int *score_bits, const float *cls_planar, const float *box_planar, const float *rois,
+                              const float *anchors, const float *means, const float *stds, const float *scale, float *aboxes,
+                              int *rows_out, void *workspace, long long workspace_bytes, int B, int A, int HW, int k,
+                              m3d_stream_t stream);
+int m3d_post_rows(const int *rows_out, const int *keep, const int *num_keep, int B, int n, int post, int HW, int *rows,
+                  int *n_rows, m3d_stream_t stream);
+int m3d_fill_post_3d(const float *box_planar, const float *rois, const float *anchors, const float *means, const float *stds,
+                     const int *rows_out, const int *keep, const int *counts, int B, int A, int HW, int n, int post, float *block,
+                     m3d_stream_t stream);
 /* Exact twin of the reference's _nms (lib/nms/gpu_nms.hpp): host pointers, synchronous. */
 void _nms(int *keep_out, int *num_out, const float *boxes_host, int boxes_num, int boxes_dim,
           float nms_overlap_thresh, int device_id);

@@ -23,20 +23,22 @@
 
 // Decode (lib/rpn_util.py:1442-1521 + bbox_transform_inv :1137-1186), scale_factor = 1.
 // Row layout out: x1,y1,x2,y2,score,cls,x3d,y3d,z3d,w3d,h3d,l3d,ry3d,anchor  (rpn_util.py:1550)
-__device__ __forceinline__ void decode_values(int row, const float *__restrict__ v2 /*[4]*/, const float *__restrict__ v3 /*[7]*/,
-                                              float p1, float p2, float p3, const float *__restrict__ rois,
-                                              const float *__restrict__ anchors, const float *__restrict__ means,
-                                              const float *__restrict__ stds, float *__restrict__ q)
+// In two parts: what the NMS and the post-NMS cut read (the 2-D box, score and class) with the projected centre and the anchor,
+// and the five columns that nobody reads before a row is among the nms_topN_post kept ones (m3d_fill_post_3d).
+// 2-D / centre part: columns 0..7 and 13.  vc = the x3d, y3d outputs.
+__device__ __forceinline__ void decode_values_2d(int row, const float *__restrict__ v2 /*[4]*/, const float *__restrict__ vc /*[2]*/,
+                                                 float p1, float p2, float p3, const float *__restrict__ rois,
+                                                 const float *__restrict__ means, const float *__restrict__ stds,
+                                                 float *__restrict__ q)
 {
     const float *ro = rois + (size_t)row * 5;
     const float x1 = ro[0], y1 = ro[1], x2 = ro[2], y2 = ro[3];
     const int tr = (int)ro[4];
-    const float *an = anchors + tr * 9;
     const float widths = x2 - x1 + 1.0f, heights = y2 - y1 + 1.0f;
     const float ctr_x = x1 + 0.5f * widths, ctr_y = y1 + 0.5f * heights;
-    float d3[7];
+    float d3[2];
 #pragma unroll
-    for (int k = 0; k < 7; ++k) d3[k] = v3[k] * stds[4 + k] + means[4 + k];
+    for (int k = 0; k < 2; ++k) d3[k] = vc[k] * stds[4 + k] + means[4 + k];
     const float dx = v2[0] * stds[0] + means[0];
     const float dy = v2[1] * stds[1] + means[1];
     const float dw = v2[2] * stds[2] + means[2];
@@ -55,12 +57,32 @@ __device__ __forceinline__ void decode_values(int row, const float *__restrict__
     q[5] = (float)cl;
     q[6] = d3[0] * widths + ctr_x;
     q[7] = d3[1] * heights + ctr_y;
-    q[8] = an[4] + d3[2];
-    q[9] = expf(d3[3]) * an[5];
-    q[10] = expf(d3[4]) * an[6];
-    q[11] = expf(d3[5]) * an[7];
-    q[12] = an[8] + d3[6];
     q[13] = (float)tr;
+}
+
+// deferred part: columns 8..12 (z3d, w3d, h3d, l3d, ry3d) of a row whose anchor is tr.  vd = the z3d .. rY3d outputs.
+__device__ __forceinline__ void decode_values_3d(int tr, const float *__restrict__ vd /*[5]*/, const float *__restrict__ anchors,
+                                                 const float *__restrict__ means, const float *__restrict__ stds,
+                                                 float *__restrict__ q)
+{
+    const float *an = anchors + tr * 9;
+    float d3[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) d3[k] = vd[k] * stds[6 + k] + means[6 + k];
+    q[8] = an[4] + d3[0];
+    q[9] = expf(d3[1]) * an[5];
+    q[10] = expf(d3[2]) * an[6];
+    q[11] = expf(d3[3]) * an[7];
+    q[12] = an[8] + d3[4];
+}
+
+__device__ __forceinline__ void decode_values(int row, const float *__restrict__ v2 /*[4]*/, const float *__restrict__ v3 /*[7]*/,
+                                              float p1, float p2, float p3, const float *__restrict__ rois,
+                                              const float *__restrict__ anchors, const float *__restrict__ means,
+                                              const float *__restrict__ stds, float *__restrict__ q)
+{
+    decode_values_2d(row, v2, v3, p1, p2, p3, rois, means, stds, q);
+    decode_values_3d((int)rois[(size_t)row * 5 + 4], v3 + 2, anchors, means, stds, q);
 }
 
 // rows of the bundled tensors prob [B][R][4], bbox_2d [B][R][4], bbox_3d [B][R][7]; o = img * R + row
@@ -78,11 +100,12 @@ __device__ __forceinline__ void decode_row(int row, size_t o, const float *__res
 }
 
 // the same row read from the planar staging the heads write (cls [B][4A][HW], box [B][11][A*HW]): the class probabilities are
-// recomputed from the four logits with the arithmetic of bundle_outputs (class_softmax4, common.h) -- the same bits
+// recomputed from the four logits with the arithmetic of bundle_outputs (class_softmax4, common.h) -- the same bits.
+// defer3d: box planes 6..10 are not read and columns 8..12 are +0 (m3d_topk_decode_planar_2d)
 __device__ __forceinline__ void decode_row_planar(int row, int img, int A, int HW, const float *__restrict__ cls_pl,
                                                   const float *__restrict__ box_pl, const float *__restrict__ rois,
                                                   const float *__restrict__ anchors, const float *__restrict__ means,
-                                                  const float *__restrict__ stds, float *__restrict__ q)
+                                                  const float *__restrict__ stds, bool defer3d, float *__restrict__ q)
 {
     const int R = A * HW;
     const int an = row / HW, p = row - an * HW;
@@ -95,6 +118,14 @@ __device__ __forceinline__ void decode_row_planar(int row, int img, int A, int H
     float v2[4], v3[7];
 #pragma unroll
     for (int k = 0; k < 4; ++k) v2[k] = bb[(size_t)k * R];
+    if (defer3d) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) v3[k] = bb[(size_t)(4 + k) * R];
+        decode_values_2d(row, v2, v3, pr[1], pr[2], pr[3], rois, means, stds, q);
+#pragma unroll
+        for (int c = 8; c < 13; ++c) q[c] = 0.0f;
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < 7; ++k) v3[k] = bb[(size_t)(4 + k) * R];
     decode_values(row, v2, v3, pr[1], pr[2], pr[3], rois, anchors, means, stds, q);
@@ -135,6 +166,7 @@ struct TopkArgs {
     const float *scale;               // [B] or null: test-time scale factor of each image (lib/rpn_util.py:1504-1506)
     int R, k;
     int A, HW;                        // planar form (A > 0): prob = cls planar [B][4A][HW], b2 = box planar [B][11][A*HW], b3 unused
+    int defer3d;                      // planar form: box planes 6..10 are not read, columns 8..12 are written as +0
     // multi-workgroup form (topk_mw_*): what the level-0 launches leave for the finishing one, behind `cand` in the workspace
     unsigned long long *mw_sel;       // [B][k] keys above the threshold bin (fewer than k by the definition of the bin)
     unsigned *mw_hist;                // [B][2048] histogram of the top 11 score bits
@@ -309,7 +341,7 @@ __global__ __launch_bounds__(TOPK_NT) void topk_decode_kernel(TopkArgs a)
         const int row = (int)(0xFFFFFFFFu - (unsigned)sel[i]);
         if (a.rows_out) a.rows_out[(size_t)img * k + i] = row;
         float *q = a.aboxes + ((size_t)img * k + i) * 14;
-        if (a.A > 0) decode_row_planar(row, img, a.A, a.HW, a.prob, a.b2, a.rois, a.anchors, a.means, a.stds, q);
+        if (a.A > 0) decode_row_planar(row, img, a.A, a.HW, a.prob, a.b2, a.rois, a.anchors, a.means, a.stds, a.defer3d != 0, q);
         else decode_row(row, (size_t)img * R + row, a.prob, a.b2, a.b3, a.rois, a.anchors, a.means, a.stds, q);
         if (a.scale) {
             // `coords_2d[:, 0:4] /= scale_factor; coords_3d[:, 0:2] /= scale_factor` BEFORE the sort and the NMS, as the reference
@@ -419,6 +451,19 @@ extern "C" int m3d_topk_decode_planar(const unsigned int *score_bits, const floa
     TopkArgs a;
     const int rc = topk_args(a, true, false, "topk_decode_planar", score_bits, cls_planar, box_planar, nullptr, rois, anchors, means,
                              stds, scale, aboxes, rows_out, workspace, workspace_bytes, B, A, HW, k);
+    return rc != M3D_OK ? rc : topk_launch<false>(a, B, (hipStream_t)stream);
+}
+
+extern "C" int m3d_topk_decode_planar_2d(const unsigned int *score_bits, const float *cls_planar, const float *box_planar,
+                                         const float *rois, const float *anchors, const float *means, const float *stds,
+                                         const float *scale, float *aboxes, int *rows_out, void *workspace,
+                                         long long workspace_bytes, int B, int A, int HW, int k, m3d_stream_t stream)
+{
+    M3D_REQUIRE(rows_out, "topk_decode_planar_2d: rows_out is required (m3d_fill_post_3d finds the staging rows through it)");
+    TopkArgs a;
+    const int rc = topk_args(a, true, false, "topk_decode_planar_2d", score_bits, cls_planar, box_planar, nullptr, rois, anchors,
+                             means, stds, scale, aboxes, rows_out, workspace, workspace_bytes, B, A, HW, k);
+    a.defer3d = 1;
     return rc != M3D_OK ? rc : topk_launch<false>(a, B, (hipStream_t)stream);
 }
 
@@ -746,6 +791,119 @@ extern "C" int m3d_select_post(const float *aboxes, const int *keep, const int *
     M3D_REQUIRE(aboxes && keep && num_keep && block && B >= 1 && n >= 1 && post >= 1, "select_post: bad arguments");
     hipLaunchKernelGGL(select_post_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, aboxes, keep, num_keep, n, post, block,
                        counts);
+    M3D_LAUNCH_CHECK();
+    return M3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The 3-D size, depth and angle of a row (columns 8..12) are read by nobody unless the row is among the `post` rows per image
+// that select_post_kernel copies: the heads behind them run at the pixels of those rows only.
+//  * post_rows_kernel: ONE workgroup.  Entry (b, j < min(num_keep[b], post)) is pixel b * HW + rows_out[b][keep[b][j]] % HW; the
+//    B * post entries (absent ones = INT_MAX) are sorted ascending in LDS (bitonic), every value that differs from its
+//    predecessor is kept, and an ordered scan places it: the list contract of m3d_need_rows (distinct, ascending, n_rows on the
+//    device, nothing written past it).  Nothing carries over between calls.
+//  * fill_post_3d_kernel: columns 8..12 of the selected rows from box planes 6..10, with decode_values_3d (the bits of the
+//    full decode).
+#define POST_ROWS_MAX 4096               // B * post entries of the sort (bs 64 x nms_topN_post 40 = 2560)
+#define POST_ROWS_NT 1024
+
+__global__ __launch_bounds__(POST_ROWS_NT) void post_rows_kernel(const int *__restrict__ rows_out, const int *__restrict__ keep,
+                                                                 const int *__restrict__ num, int B, int n, int post, int HW,
+                                                                 int *__restrict__ rows, int *__restrict__ n_rows)
+{
+    __shared__ int s[POST_ROWS_MAX];
+    __shared__ unsigned wave_tot[16];
+    const int tid = threadIdx.x;
+    const int total = B * post;
+    int P = 1;
+    while (P < total) P <<= 1;                                         // <= POST_ROWS_MAX (checked by the launcher)
+    for (int e = tid; e < P; e += POST_ROWS_NT) {
+        int v = 0x7FFFFFFF;
+        if (e < total) {
+            const int b = e / post, j = e - b * post;
+            if (j < min(num[b], post)) {
+                const int kp = keep[(size_t)b * n + j];
+                if (kp >= 0 && kp < n) {
+                    const int row = rows_out[(size_t)b * n + kp];
+                    if (row >= 0) v = b * HW + row % HW;
+                }
+            }
+        }
+        s[e] = v;
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (P >> 1); t += POST_ROWS_NT) {
+                const int lo = 2 * t - (t & (stride - 1));
+                const int hi = lo + stride;
+                const bool asc = ((lo & size) == 0);
+                const int x = s[lo], y = s[hi];
+                if ((x > y) == asc) { s[lo] = y; s[hi] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    // thread t owns the four sorted entries [4t, 4t + 4): P <= 4 * POST_ROWS_NT
+    int v[4];
+    unsigned f[4], c = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = 4 * tid + i;
+        v[i] = e < P ? s[e] : 0x7FFFFFFF;
+        f[i] = (v[i] != 0x7FFFFFFF && (e == 0 || s[e - 1] != v[i])) ? 1u : 0u;
+        c += f[i];
+    }
+    unsigned at = block_excl_scan(c, wave_tot, tid);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (f[i]) rows[at++] = v[i];
+    if (tid == POST_ROWS_NT - 1) *n_rows = (int)at;                    // (the last thread's end = the total)
+}
+
+extern "C" int m3d_post_rows(const int *rows_out, const int *keep, const int *num_keep, int B, int n, int post, int HW, int *rows,
+                             int *n_rows, m3d_stream_t stream)
+{
+    M3D_REQUIRE(rows_out && keep && num_keep && rows && n_rows, "post_rows: null pointer");
+    M3D_REQUIRE(B >= 1 && n >= 1 && post >= 1 && HW >= 1 && (long long)B * HW < (1ll << 31), "post_rows: bad B / n / post / HW (%d, %d, %d, %d)",
+                B, n, post, HW);
+    M3D_REQUIRE((long long)B * post <= POST_ROWS_MAX, "post_rows: B * post (%lld) must be at most %d", (long long)B * post,
+                POST_ROWS_MAX);
+    hipLaunchKernelGGL(post_rows_kernel, dim3(1), dim3(POST_ROWS_NT), 0, (hipStream_t)stream, rows_out, keep, num_keep, B, n, post,
+                       HW, rows, n_rows);
+    M3D_LAUNCH_CHECK();
+    return M3D_OK;
+}
+
+__global__ void fill_post_3d_kernel(const float *__restrict__ box_pl, const float *__restrict__ rois,
+                                    const float *__restrict__ anchors, const float *__restrict__ means,
+                                    const float *__restrict__ stds, const int *__restrict__ rows_out, const int *__restrict__ keep,
+                                    const int *__restrict__ counts, int R, int n, int post, float *__restrict__ block)
+{
+    const int b = blockIdx.x;
+    const int cnt = min(counts[b], post);
+    for (int j = threadIdx.x; j < cnt; j += blockDim.x) {
+        const int kp = keep[(size_t)b * n + j];
+        if (kp < 0 || kp >= n) continue;
+        const int row = rows_out[(size_t)b * n + kp];
+        if (row < 0 || row >= R) continue;
+        const float *bb = box_pl + (size_t)b * 11 * R + row;
+        float vd[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) vd[k] = bb[(size_t)(6 + k) * R];
+        decode_values_3d((int)rois[(size_t)row * 5 + 4], vd, anchors, means, stds, block + ((size_t)b * (post + 1) + j) * 14);
+    }
+}
+
+extern "C" int m3d_fill_post_3d(const float *box_planar, const float *rois, const float *anchors, const float *means,
+                                const float *stds, const int *rows_out, const int *keep, const int *counts, int B, int A, int HW,
+                                int n, int post, float *block, m3d_stream_t stream)
+{
+    M3D_REQUIRE(box_planar && rois && anchors && means && stds && rows_out && keep && counts && block, "fill_post_3d: null pointer");
+    M3D_REQUIRE(B >= 1 && A >= 1 && HW >= 1 && n >= 1 && post >= 1 && (long long)A * HW < (1 << 22),
+                "fill_post_3d: bad B / A / HW / n / post (%d, %d, %d, %d, %d)", B, A, HW, n, post);
+    hipLaunchKernelGGL(fill_post_3d_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, box_planar, rois, anchors, means, stds,
+                       rows_out, keep, counts, A * HW, n, post, block);
     M3D_LAUNCH_CHECK();
     return M3D_OK;
 }

@@ -242,10 +242,32 @@ class _Plan:
         # index into ops -> factory(rpn stage record) of the launch that stands in for that op in the tail (its row-list / gated
         # form), registered where the dense op is appended; the tail takes it for ops behind anchor_select (Engine._rpn_tail)
         self.sparse = {}
+        # The tail in two parts (Engine._rpn_post3d): tail_pre = the tail without the launches whose outputs feed columns 8..12 of
+        # a decoded row and nothing else, post3d = those launches on the list of the pixels that survive the NMS
+        # (plan.post_rows / plan.post_n_rows, written by m3d_post_rows).  None: the engine does not offer the split.
+        self.tail_pre = None
+        self.post3d = None
+        self.post_rows = self.post_n_rows = None
+        self.post3d_reads = []     # (tensor, index of the first op that writes it) of every map a post3d launch reads
+        # index into ops -> (pre, post, reads), registered where the dense op is appended: pre = the op's form in tail_pre (None:
+        # it has none there), post = its form in post3d, each (factory(rpn stage record), name, flops, desc) with None = the
+        # dense op's; reads = the tensors the post form reads
+        self.deferred = {}
+        self.post3d_declined = None    # why the builder of an op rules the split out, if it does
+        self.first_write = {}      # data_ptr of a buffer -> index of the first op that writes it (the buffers `wrote` was told of)
 
     def sparse_form(self, factory):
         """Register the detection-only form of the op appended last."""
         self.sparse[len(self.ops) - 1] = factory
+
+    def deferred_form(self, pre, post, reads):
+        """Register the two forms of the op appended last in the split tail (see `deferred`)."""
+        self.deferred[len(self.ops) - 1] = (pre, post, list(reads))
+
+    def wrote(self, *tensors):
+        """The op appended last writes these buffers."""
+        for t in tensors:
+            self.first_write.setdefault(t.data_ptr(), len(self.ops) - 1)
 
 
 class _RpnStage:
@@ -489,6 +511,7 @@ class Engine:
         flops = 2.0 * d.N * d.Ho * d.Wo * d.Cout * d.kh * d.kw * cin_true
         kind = conv_kind(route.family, route.tile, deform=d.dcn_offmask is not None, per_image=per_image, **route.options)
         plan.ops.append((name, kind, flops, route.launch, route.desc))
+        plan.wrote(out.t)
 
     def _launch(self, fn, d, *args):
         """The launch closure of a descriptor entry point: fn(d, *args, stream)."""
@@ -804,6 +827,9 @@ class Engine:
         with_shape, with_center, with_anab = self.flags
         # detection-only tail: bbox_x3d / bbox_y3d feed feats_align3d, which ANAB pools over the whole map: dense in every launch
         dense_heads = {"bbox_x3d", "bbox_y3d"} if with_center else set()
+        # box planes 6..10 (z3d, w3d, h3d, l3d, rY3d) feed columns 8..12 of a decoded row, which nobody reads before the row has
+        # survived the NMS and the post-NMS cut ("After the NMS"): the heads of the split tail's second part
+        deferred_heads = set(self.box_heads[6:])
 
         def head_desc(p, x, planar, first):
             t, img_stride, ch_off = planar
@@ -819,22 +845,46 @@ class Engine:
             flops = 2.0 * B * HW * ((x.c * 256 if first is not None else 0) + 256 * 256 + 256 * last.cout)
             return d, flops
 
-        def heads(items):
-            """1x1 heads with no mutual dependency as ONE fused-MLP launch (grid.y = head): items = [(p, x, planar)].  The 64-wide
-            launches have a row-list form for the tail: bit i of its mask = head i runs at the listed pixels only."""
+        def mlp_array(items):
+            """(descriptor array, flops, op name) of the heads items = [(p, x, planar)] as one fused-MLP launch."""
             arr = (MlpDesc * len(items))()
             flops = 0.0
             for i, (p, x, planar) in enumerate(items):
                 arr[i], f = head_desc(p, x, planar, P[p + ".0"])
                 flops += f
+            return arr, flops, "+".join(p for p, _, _ in items) + ".mlp"
+
+        def rows_form(items, arr, rows_of):
+            """The row-list launch of `arr` on the list rows_of(stage record) = (rows, n_rows); the dense heads stay dense."""
             n = len(items)
-            name = "+".join(p for p, _, _ in items) + ".mlp"
+            mask = sum(1 << i for i, (p, _, _) in enumerate(items) if p not in dense_heads)
+
+            def factory(r):
+                rows, n_rows = rows_of(r)
+                return lambda st: _hip.check(L.m3d_head_mlp_forward_rows(arr, n, rows.data_ptr(), n_rows.data_ptr(), mask, st))
+            return factory
+
+        def heads(items):
+            """1x1 heads with no mutual dependency as ONE fused-MLP launch (grid.y = head): items = [(p, x, planar)].  The 64-wide
+            launches have a row-list form for the tail: bit i of its mask = head i runs at the listed pixels only."""
+            arr, flops, name = mlp_array(items)
+            n = len(items)
             plan.ops.append((name, "head_mlp<3,%d>" % arr[0].Cout_pad, flops,
                              lambda st: _hip.check(L.m3d_head_mlp_forward_batched(arr, n, st)), arr))
             if arr[0].Cout_pad == 64:
-                mask = sum(1 << i for i, (p, _, _) in enumerate(items) if p not in dense_heads)
-                plan.sparse_form(lambda r: lambda st: _hip.check(L.m3d_head_mlp_forward_rows(
-                    arr, n, r.rows.data_ptr(), r.n_rows.data_ptr(), mask, st)))
+                plan.sparse_form(rows_form(items, arr, lambda r: (r.rows, r.n_rows)))
+                late = [it for it in items if it[0] in deferred_heads]
+                if late:
+                    # the split tail: the heads in front of the NMS on the needed pixels, the deferred ones on the survivors' pixels
+                    early = [it for it in items if it[0] not in deferred_heads]
+                    forms = []
+                    for part, rows_of in ((early, lambda r: (r.rows, r.n_rows)), (late, lambda r: (r.post_rows, r.post_n_rows))):
+                        if part:
+                            parr, pflops, pname = mlp_array(part)
+                            forms.append((rows_form(part, parr, rows_of), pname, pflops, parr))
+                        else:
+                            forms.append(None)
+                    plan.deferred_form(forms[0], forms[1], [x.t for _, x, _ in late])
 
         def head(p, x, planar, k0=1):
             """3-layer head.  A 1x1 head runs as one fused-MLP launch; the cls head runs its 3x3 conv through the
@@ -1009,6 +1059,52 @@ class Engine:
             op, sparse = plan.ops[i], plan.sparse.get(i)
             tail.append(op if sparse is None else op[:3] + (sparse(r), op[4]))
         plan.tail, plan.tail_start = tail, t0
+        self._rpn_post3d(plan, r, t0)
+
+    # entries of the sort inside m3d_post_rows (B * nms_topN_post)
+    POST_ROWS_MAX = 4096
+
+    def _rpn_post3d(self, plan, r, t0):
+        """The tail in two parts (plan.tail_pre, plan.post3d) where the plan's builders registered deferred forms.
+        Columns 8..12 of a decoded row come from box planes 6..10, and m3d_nms_sorted_dev and the post-NMS cut read columns 0..4:
+        the launches that feed those planes and nothing else are needed at the pixels of the at most nms_topN_post rows per image
+        that m3d_select_post copies.  A detector that runs detect(k-1) beside forward(k) issues post3d on that side branch, so
+        every map a post3d launch reads must still hold batch k-1 there: its first writer has to stand at or behind
+        `planar_first_op`, where the branch has joined.  That is decided from the buffers (plan.first_write); a map whose writer
+        was never recorded counts as written in front.  Declined (both lists stay None): nothing registered, a builder ruled it
+        out (the attention is not the one-launch row-list route), a map fails the rule, or B * nms_topN_post exceeds the sort."""
+        forms = {i: f for i, f in plan.deferred.items() if i >= t0}
+        if not forms or plan.post3d_declined is not None:
+            return
+        if r.B * int(self.conf.nms_topN_post) > self.POST_ROWS_MAX:
+            return
+        join = int(plan.named["planar_first_op"])
+        reads = {}
+        for _, _, rd in forms.values():
+            for t in rd:
+                reads[t.data_ptr()] = (t, plan.first_write.get(t.data_ptr(), -1))
+        if any(w < join for _, w in reads.values()):
+            return
+        # the survivors' pixels: zeroed for the same reason as the needed-pixel list above
+        r.post_rows = torch.zeros(r.B * r.HW, device=self.device, dtype=torch.int32)
+        r.post_n_rows = torch.zeros(1, device=self.device, dtype=torch.int32)
+        plan.keep += [r.post_rows, r.post_n_rows]
+        plan.post_rows, plan.post_n_rows = r.post_rows, r.post_n_rows      # (not in plan.named: its keys are pinned by the manifest)
+
+        def form(op, f):
+            factory, name, flops, desc = f
+            return (op[0] if name is None else name, op[1], op[2] if flops is None else flops, factory(r),
+                    op[4] if desc is None else desc)
+
+        pre = [plan.tail[0]]
+        for i in range(t0, len(plan.ops) - 1):
+            if i not in forms:
+                pre.append(plan.tail[1 + i - t0])
+            elif forms[i][0] is not None:
+                pre.append(form(plan.ops[i], forms[i][0]))
+        plan.tail_pre = pre
+        plan.post3d = [form(plan.ops[i], forms[i][1]) for i in sorted(forms)]
+        plan.post3d_reads = list(reads.values())
 
     def _anab_ops(self, plan, x, out, scale, shift, act, res_mode):
         """Append the ANAB launches: fused QKVS 1x1 conv -> weighted pyramid pooling -> logits GEMM (per-image
@@ -1053,9 +1149,17 @@ class Engine:
             self._op(plan, "anab.attend", "anab_attend", attend(L.m3d_anab_attend_f32),
                      flops=2.0 * B * HW * n_bins * (self.ck + self.cv),
                 nbytes=B * HW * (self.ck + 3 * self.cv) * 4 + B * keys_pad * (self.ck + self.cv) * 4)
+            plan.wrote(out.t)
             if ANAB_ROWS:
                 plan.sparse_form(lambda r: attend(L.m3d_anab_attend_f32_rows, r.rows.data_ptr(), r.n_rows.data_ptr()))
+                # split tail: `out` feeds bbox_z3d and nothing else, so the attention waits for the survivors' pixels
+                plan.deferred_form(None, (lambda r: attend(L.m3d_anab_attend_f32_rows, r.post_rows.data_ptr(),
+                                                           r.post_n_rows.data_ptr()), None, None, None),
+                                   [qkvs.t, khat, vhatT] + ([x.t] if x is not None else []))
+            else:
+                plan.post3d_declined = "the attention runs dense in the tail"
             return
+        plan.post3d_declined = "the attention is not the one-launch route"
 
         def image(v, i):
             return View(v.t, 1, v.h, v.w, v.c, v.cs, v.ptr + 4 * i * v.h * v.w * v.cs)
@@ -1099,6 +1203,7 @@ class Engine:
             self._op(plan, "anab.pool_nested", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_nested(
                 kv_ptr, kv_cs, s_ptr, s_cs, B, fh, fw, ck, cv, scratch.data_ptr(), khat.data_ptr(), keys_pad, self.ck_pad,
                 vhatT.data_ptr(), frag, st)), nbytes=nested_nbytes)
+            plan.wrote(khat, vhatT)
             return
         items, bin_scale, bin_slots, bin_inv = self._anab_items(fh, fw)
         n_bins, max_slots = len(bin_scale), int(bin_slots.max())
@@ -1112,6 +1217,7 @@ class Engine:
         self._op(plan, "anab.pool_finish", "anab_pool", lambda st: _hip.check(L.m3d_anab_pool_finish(
             partial.data_ptr(), d_bslots.data_ptr(), d_binv.data_ptr(), n_bins, max_slots, ck, cv, khat.data_ptr(), keys_pad,
             self.ck_pad, vhatT.data_ptr(), B, frag, st)))
+        plan.wrote(khat, vhatT)
 
     @classmethod
     def anab_standalone(cls, mod, x):
@@ -1228,17 +1334,32 @@ class Engine:
         tail=True: the detection-only form -- plan.ops[start:plan.tail_start], then plan.tail in place of everything behind it up
         to bundle_outputs (`end` must be the index of bundle_outputs), all on the current stream: side branches are not forked in
         this form.  The box staging is then written at the needed pixels only:
-        what follows may be the planar top-k decode, not bundle_outputs.  plan.named["sparse_k"][0] is the k of that decode."""
+        what follows may be the planar top-k decode, not bundle_outputs.  plan.named["sparse_k"][0] is the k of that decode.
+        tail="pre": plan.tail_pre in place of plan.tail -- box planes 6..10 are then not written at all; what follows is
+        m3d_topk_decode_planar_2d, the NMS, m3d_post_rows and run_post3d."""
         with torch.cuda.device(self.device):
             if not tail:
                 return self._run_plan(plan, start, end)
             if getattr(plan, "tail", None) is None:
                 raise RuntimeError("run_plan(tail=True): this plan has no detection-only tail")
+            tail_ops = plan.tail
+            if tail == "pre":
+                if getattr(plan, "tail_pre", None) is None:
+                    raise RuntimeError("run_plan(tail='pre'): this plan does not offer the split tail")
+                tail_ops = plan.tail_pre
             # (a plan with side branches -- the bf16 one, ANAB beside the size heads -- is issued in line here, on one stream)
             if end != len(plan.ops) - 1 or not 0 <= start <= plan.tail_start:
                 raise RuntimeError("run_plan(tail=True): ops [%r, %r) do not end in front of bundle_outputs (op %d) behind a start "
                                    "in [0, %d]" % (start, end, len(plan.ops) - 1, plan.tail_start))
-            self._run_plan(plan, start, end, plan.ops[start:plan.tail_start] + plan.tail)
+            self._run_plan(plan, start, end, plan.ops[start:plan.tail_start] + tail_ops)
+
+    def run_post3d(self, plan):
+        """Issue plan.post3d on the engine device's current stream: the deferred heads and the attention at the pixels that
+        m3d_post_rows listed (plan.post_rows / plan.post_n_rows), writing box planes 6..10 there."""
+        if getattr(plan, "post3d", None) is None:
+            raise RuntimeError("run_post3d: this plan does not offer the split tail")
+        with torch.cuda.device(self.device):
+            self._run_plan(plan, 0, 0, plan.post3d)
 
     def sparse_heads_default(self, plan, k):
         """The plan-time rule of a detector's sparse_heads=None for a decode of the k best rows per image."""

@@ -126,6 +126,47 @@ def detect_from_planar_mw(eng, plan, rois, conf, scale=None, wgs=None):
     return _detect_planar(eng, plan, rois, conf, scale, 0 if wgs is None else int(wgs))
 
 
+def detect_from_planar_2d(eng, plan, rois, conf, scale=None):
+    """detect_from_planar in front of a deferred 3-D part (``m3d_topk_decode_planar_2d``): box planes 6..10 of the staging are not
+    read, columns 8..12 of aboxes are zero, and the staging rows of the decoded rows come back for ``post_rows`` / ``fill_post_3d``.
+    -> (aboxes, keep, num_keep, rows_out [B, n_pre] int32)."""
+    L, P = _hip.lib(), eng.P
+    cls_pl, box_pl, bits = plan.named["cls_planar"], plan.named["box_planar"], plan.named["score_bits"]
+    B, R = bits.shape[0], bits.shape[1]
+    A = eng.A
+    k = min(int(conf.nms_topN_pre), R)
+    head = (bits.data_ptr(), cls_pl.data_ptr(), box_pl.data_ptr(), rois.data_ptr(), P["anchors"].data_ptr(), P["means"].data_ptr(),
+            P["stds"].data_ptr(), _ptr(scale))
+    nb = L.m3d_topk_decode_workspace_bytes(B, R)
+    rows_out = torch.empty(B, k, device=bits.device, dtype=torch.int32)
+    return _topk_nms(bits.device, B, k, conf, nb, lambda aboxes, ws, st: L.m3d_topk_decode_planar_2d(
+        *head, aboxes, rows_out.data_ptr(), ws, nb, B, A, R // A, k, st)) + (rows_out,)
+
+
+def post_rows(plan, rows_out, keep, num, conf):
+    """The pixels of the rows that ``select_block`` copies -> plan.post_rows / plan.post_n_rows (``m3d_post_rows``), the
+    list that ``Engine.run_post3d`` runs the deferred launches on."""
+    dev = rows_out.device
+    B, n = rows_out.shape[0], rows_out.shape[1]
+    HW = plan.feat[0] * plan.feat[1]
+    with torch.cuda.device(dev):
+        _hip.check(_hip.lib().m3d_post_rows(rows_out.data_ptr(), keep.data_ptr(), num.data_ptr(), B, n, int(conf.nms_topN_post), HW,
+                                            plan.post_rows.data_ptr(), plan.post_n_rows.data_ptr(), _stream(dev)))
+
+
+def fill_post_3d(eng, plan, rois, rows_out, keep, counts, block, conf):
+    """Columns 8..12 of the selected rows of ``block`` from box planes 6..10 of the staging (``m3d_fill_post_3d``), in place."""
+    P = eng.P
+    dev = block.device
+    B, n = rows_out.shape[0], rows_out.shape[1]
+    HW = plan.feat[0] * plan.feat[1]
+    with torch.cuda.device(dev):
+        _hip.check(_hip.lib().m3d_fill_post_3d(
+            plan.named["box_planar"].data_ptr(), rois.data_ptr(), P["anchors"].data_ptr(), P["means"].data_ptr(),
+            P["stds"].data_ptr(), rows_out.data_ptr(), keep.data_ptr(), counts.data_ptr(), B, eng.A, HW, n,
+            int(conf.nms_topN_post), block.data_ptr(), _stream(dev)))
+
+
 def score_keys_planar(eng, plan):
     """The launch that replaces bundle_outputs when only the detection stage follows: sort keys from the planar class logits."""
     bits = plan.named["score_bits"]

@@ -17,6 +17,12 @@ replaces ``m3d_bundle_outputs`` by the key-only pass and decodes from the planar
 bits); ``planar=False`` (or M3D_PIPE_PLANAR=0) is the bundled form: detect(k-1) beside forward(k), join, bundle(k).  In the
 planar form ``plan.named["prob" / "bbox_2d" / "bbox_3d" / "cls"]`` are NOT written by a replay.
 
+``defer_3d`` (default: on whenever the sparse heads are on and the plan offers ``post3d``; ``M3D_DEFER_3D=0`` or ``False``: off) moves
+what only the surviving boxes need out of the forward: the heads behind columns 8..12 of a row (z3d, w3d, h3d, l3d, rY3d) and the ANAB
+attention run on branch B, behind the NMS and ``m3d_select_post``, at the pixels of the at most ``nms_topN_post`` rows per image that
+were selected (``m3d_topk_decode_planar_2d`` -> NMS -> ``m3d_select_post`` -> ``m3d_post_rows`` -> ``plan.post3d`` ->
+``m3d_fill_post_3d``); the forward behind the join runs ``plan.tail_pre``.  Same bits (tests/test_gpu_post_nms_heads.py).
+
 ``u8_frame=(h, w)`` is the fed-input form (the reference pays ``im.cuda()`` per frame, lib/rpn_util.py:1427-1429,
 and preprocesses on the host, lib/dataloader.py:934-950, lib/augmentations.py:472-501): raw uint8 BGR frames [B, h, w, 3] sit in
 PINNED host memory; the graph of batch k carries, on its side branch, an upload KERNEL (``m3d_upload_indirect``) that streams
@@ -37,8 +43,8 @@ import os
 import torch
 
 from . import _hip
-from .host.detect import (detect_from_outputs, detect_from_planar, detect_from_planar_mw, score_keys_planar, select_block,
-                          unwrap)
+from .host.detect import (detect_from_outputs, detect_from_planar, detect_from_planar_2d, detect_from_planar_mw, fill_post_3d,
+                          post_rows, score_keys_planar, select_block, unwrap)
 from .host.refine import RefineMeta, refine_rows
 
 
@@ -79,6 +85,7 @@ class _Detector:
         if sparse_heads is None:
             sparse_heads = self.eng.sparse_heads_default(self.plan, conf.nms_topN_pre)
         self.sparse_heads = bool(sparse_heads) and bool(planar) and getattr(self.plan, "tail", None) is not None
+        self.defer_3d = False                           # (PipelinedDetector: the 3-D size, depth and angle heads behind the NMS)
         self._rois = net.rois.to(dev)
         # refine mode: calibration / scale / image size of the batch whose detections the next replay refines
         self._meta = RefineMeta(self.batch, dev) if self.refine else None
@@ -100,9 +107,12 @@ class _Detector:
         finally:
             self.plan.named["input_u8"][0] = 0
 
-    def _select(self, rows):
-        """(aboxes, keep, num) of a detect_from_* -> (block, counts, refined rows or None)."""
+    def _select(self, rows, fill=None):
+        """(aboxes, keep, num) of a detect_from_* -> (block, counts, refined rows or None).  fill(block, counts): what completes
+        the selected rows of the block in place, in front of the refinement."""
         block, counts = select_block(*rows, self.conf)
+        if fill is not None:
+            fill(block, counts)
         if not self.refine:
             return block, counts, None
         # the block's rows are the kept rows + the count row (past counts[b]: refined to zeros); the scale factors were applied
@@ -117,10 +127,16 @@ class _Detector:
 
 class PipelinedDetector(_Detector):
     def __init__(self, net, conf, batch, height, width, refine=False, score_thresh=0.75, step_r_init=0.3 * math.pi, r_lim=0.01,
-                 u8_frame=None, planar=None, sparse_heads=None):
+                 u8_frame=None, planar=None, sparse_heads=None, defer_3d=None):
         planar = (os.environ.get("M3D_PIPE_PLANAR", "1") != "0") if planar is None else bool(planar)
         super().__init__(net, conf, batch, height, width, refine, score_thresh, step_r_init, r_lim, u8_frame, 2, sparse_heads, planar)
         self.planar = planar
+        # the heads and the attention behind columns 8..12 of a row only at the pixels of the rows that survive the NMS, on the side
+        # branch (plan.tail_pre / plan.post3d): None = whenever the sparse heads are on and the plan offers the split
+        # (M3D_DEFER_3D=0: off), False = the one-part tail; a plan that does not offer it keeps that tail whatever is asked
+        if defer_3d is None:
+            defer_3d = os.environ.get("M3D_DEFER_3D", "1") != "0"
+        self.defer_3d = bool(defer_3d) and self.sparse_heads and getattr(self.plan, "post3d", None) is not None
         if self.u8_frame is not None:
             # slot i: address of the pinned-host frames that the graph reading buffer i uploads into buffer i ^ 1 (0 = nothing)
             self._slots = torch.zeros(2, dtype=torch.int64).pin_memory()
@@ -160,10 +176,26 @@ class PipelinedDetector(_Detector):
         if self.n_join > limit:
             raise AssertionError("PipelinedDetector: join at op %d, but op %d of the next forward writes what detect reads (%s)"
                                  % (self.n_join, limit, first_writer))
+        if self.defer_3d:
+            # the side branch also runs plan.post3d of batch k-1: every map those launches read (the engine recorded them with
+            # their first writers) must not be written by forward(k) in front of the join either
+            for t, w in self.plan.post3d_reads:
+                if w < self.n_join:
+                    raise AssertionError("PipelinedDetector: join at op %d, but op %d of the next forward writes a map the deferred "
+                                         "3-D launches read" % (self.n_join, w))
 
     def _detect(self):
         prob, b2, b3 = self._outs
         scale = self._meta.scale if self.refine else None
+        if self.defer_3d:
+            # 2-D top-k + NMS + selection, then the 3-D part of the forward at the survivors' pixels and their columns 8..12
+            aboxes, keep, num, rows_out = detect_from_planar_2d(self.eng, self.plan, self._rois, self.conf, scale)
+
+            def fill(block, counts):
+                post_rows(self.plan, rows_out, keep, num, self.conf)
+                self.eng.run_post3d(self.plan)
+                fill_post_3d(self.eng, self.plan, self._rois, rows_out, keep, counts, block, self.conf)
+            return self._select((aboxes, keep, num), fill)
         if self.planar:
             rows = detect_from_planar(self.eng, self.plan, self._rois, self.conf, scale)
         else:
@@ -174,7 +206,7 @@ class PipelinedDetector(_Detector):
         """The launches behind the join: the rest of the forward, then the key-only pass (planar) or the output bundling."""
         if self.planar:
             if self.n_join < self.n_fwd:
-                self._forward(self.n_join, self.n_fwd, buf, self.sparse_heads)
+                self._forward(self.n_join, self.n_fwd, buf, "pre" if self.defer_3d else self.sparse_heads)
             if not self.plan.named.get("keys_by_select"):    # else anchor_select wrote them on the way (engine: SELECT_KEYS)
                 score_keys_planar(self.eng, self.plan)
         else:
